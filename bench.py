@@ -11,9 +11,16 @@ alternated: 34.17k / 34.23k searches/s at 128, 34.38k / 34.43k at 160, 34.51k / 
 ranks.  Multi-GPU: one process per GPU (torchrun), every rank searches its own sources (weak scaling, no
 data-path collective); barrier + synchronize bracket the K timed steps and the max time over ranks is used.
 
-Also reported: the dominant kernel's roofline (HIP events around every launch on the library's stream, in a
-second pass of K steps over one context's share of the sources, so the timed pass carries no event overhead) and the
-CPU baseline (the oracle restatement, single thread, on a bounded sample of the same workload, rank 0 at N=1 only).
+A plain run sets up, warms up, times the K steps and prints the result line (``value``, ``ms_per_step`` = the
+milliseconds one timed step took, and figures that are arithmetic on the timed pass's own counters).  ``--dump-outputs
+DIR`` also writes what the last timed step returned (``dump_outputs``); the sources are seeded, so two builds run with
+the same arguments search identical inputs and their outputs compare file for file.
+
+``--full`` adds everything that takes work of its own: the single-search latency probe, a reference pass that the last
+timed pass must equal field for field, the dominant kernel's roofline (HIP events around every launch on the library's
+stream, in a second pass of K steps over one context's share of the sources, so the timed pass carries no event
+overhead), the check of every timed source against the parity oracle, and the CPU baseline (the oracle restatement,
+single thread, on a bounded sample of the same workload, rank 0 at N=1 only).
 ``roofline_issue`` puts the same kernel's instruction counters (committed SQ passes of the workload's kernel pass,
 scripts/pmc_bench.sh) against the chip's VALU issue, LDS-array and matrix-pipe cycles in its measured launch time.
 
@@ -139,10 +146,44 @@ def roofline_issue(kernel, workload, avg_s):
             "source": ISSUE_SOURCE.format(os.path.relpath(TRAFFIC_CSV[workload], REPO), workload)}
 
 
-def make_sources(templ, n, seed0):
+def make_sources(templ, n, seed0, w=4024, h=3036):
+    """The Src7 surrogate scenes of seeds seed0 .. seed0 + n - 1, each equal to synth.src7_scene(templ, w, h, seed)[0]
+    bit for bit.  The pasted copies do not depend on the seed, so they are rendered once (pasting over two different
+    constant backgrounds shows which pixels a paste writes) and only the background noise is drawn per scene, on the
+    host's cores (numpy releases the GIL in the generator and the element-wise passes)."""
+    from concurrent.futures import ThreadPoolExecutor
+
     from fastest_image_pattern_matching_amd import synth
 
-    return [synth.src7_scene(templ, seed=seed0 + i)[0] for i in range(n)]
+    lo, hi = np.zeros((h, w), np.uint8), np.full((h, w), 255, np.uint8)
+    for bg in (lo, hi):
+        for _, ang, cx, cy in synth.SRC7_POSES:
+            synth.paste_rotated(bg, templ, cx * w / 4024.0, cy * h / 3036.0, -ang)
+    pasted = lo == hi
+
+    def scene(i):
+        s = synth.noise(w, h, 235, 2, seed0 + i)
+        np.copyto(s, lo, where=pasted)
+        return s
+
+    with ThreadPoolExecutor(host_cores()) as pool:
+        return list(pool.map(scene, range(n)))
+
+
+def dump_outputs(out_dir, rows, rank=0, world=1):
+    """--dump-outputs: what the timed path returned in its last step, as its caller receives it -- per source the
+    number of results and the results themselves (the 12 s_SingleTargetMatch fields in order, `rows[source][i]`) -- as
+    counts.npy [sources] and results.npy [sources, most results of any source (at least 1), 12], float64, zero past a
+    source's count.  Several ranks write one pair each (`_rank<r>` before the suffix)."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = np.array([len(r) for r in rows], np.float64)
+    results = np.zeros((len(rows), max(1, int(counts.max(initial=0))), 12), np.float64)
+    for s_, r in enumerate(rows):
+        if r:
+            results[s_, :len(r)] = np.asarray(r, np.float64)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"counts{tag}.npy"), counts)
+    np.save(os.path.join(out_dir, f"results{tag}.npy"), results)
 
 
 def _time_oracle(templ, src, budget_s, params, lib_path=None, threads=1):
@@ -354,7 +395,16 @@ def main():
     ap.add_argument("--batch", type=int, default=192, help="src7: sources searched per GPU per step")
     ap.add_argument("--sources", type=int, default=C3_SOURCES,
                     help="config3: sources of the whole job per step, sharded over the ranks")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the single-search latency probe, the reference pass the timed "
+                         "results are compared with, the per-kernel pass with its rooflines, the check of every timed "
+                         "source against the CPU oracle and the CPU baseline (a plain run only sets up, warms up, "
+                         "times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step returned to DIR/counts.npy and "
+                         "DIR/results.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0,
+                    help="--full: seconds of CPU-baseline work (0 = skip the oracle check and the baseline)")
     ap.add_argument("--contexts", type=int, default=3, help="concurrent contexts (HIP streams) per GPU")
     ap.add_argument("--skip-latency", action="store_true",
                     help="skip the single-search latency probe (PMC runs: only batch dispatches)")
@@ -365,6 +415,8 @@ def main():
                          "kernel table + roofline: the command whose rocprofv3 --kernel-trace --stats averages are "
                          "directly comparable to roofline.avg_launch_us")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -438,7 +490,7 @@ def main():
         return
     # single-search latency (host upload included) for the record, after one warm call builds the plan
     lat_e2e = lat_split = None
-    if not args.skip_latency:
+    if args.full and not args.skip_latency:
         m.match(sources[0])
         lat, splits = [], []
         for _ in range(9):
@@ -462,9 +514,11 @@ def main():
         if c is not m:
             assert c.learnPattern(templ)
         c.stage(ch)
-    ref = [r for c in ctxs for r in c.match_staged()]   # object results once, for the report and checks
-    views = [c.match_staged_array() for c in ctxs]
-    assert [len(r) for r in ref] == [int(x) for cnt, _ in views for x in cnt]
+    ref = None
+    if args.full:
+        ref = [r for c in ctxs for r in c.match_staged()]   # object results once, for the checks
+        views = [c.match_staged_array() for c in ctxs]
+        assert [len(r) for r in ref] == [int(x) for cnt, _ in views for x in cnt]
 
     # config3 on several ranks: every step's results are all-gathered (RCCL) into the whole job's report inside the
     # timed region -- the report exchange SURVEY.md §8(e) names for the sharded batch
@@ -477,6 +531,8 @@ def main():
         # post-processing) the previous one, so the device never waits for the host between steps.  Returns every
         # context's last (counts, results) views (valid until that context's next pass).
         last = [None] * len(ctxs)
+        if k_steps < 1:
+            return last
         for c in ctxs:
             c.match_staged_launch()
         for k in range(k_steps):
@@ -488,12 +544,12 @@ def main():
                 gathered[:] = [sharding.gather_result_arrays(last, total, cap, device=torch.device("cuda", local))]
         return last
 
-    def verify(last):
-        """Every source's results of the last timed pass equal the reference pass's, field for field."""
+    def rows_of(last):
+        """Every source's results of a pass (the contexts' views, in source order) as tuples of the 12 fields."""
         got = []
         for cnt, arr in last:
             got += [[tuple(float(v) for v in arr[s_, i]) for i in range(int(cnt[s_]))] for s_ in range(len(cnt))]
-        return got == [[r.as_tuple() for r in rr] for rr in ref]
+        return got
 
     run(args.warmup)
     log(f"[rank {rank}] warm; timing {args.steps} steps x {args.batch} {what} sources over {G} context(s)")
@@ -503,26 +559,28 @@ def main():
     last = run(args.steps)   # K complete device passes + host finishes (C++) per context
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    # the work just timed must be the work reported: its last pass per context equals the reference pass
-    if not verify(last):
+    res = rows_of(last)   # what the last timed step returned, per source
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
+    # --full: the work just timed must be the work reported: its last pass per context equals the reference pass,
+    # field for field
+    if ref is not None and res != [[r.as_tuple() for r in rr] for rr in ref]:
         log(f"[rank {rank}] timed pass results differ from the reference pass")
         sys.exit(3)
-    res = ref
     dev_ms, host_ms, call_ms = m.profile_last()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the report exchange of the sharded path (sharding.gather_results of the reference pass, outside the timed
+    # the report exchange of the sharded path (sharding.gather_results of the last timed pass, outside the timed
     # region); config3's timed exchange of the last step must equal it
     if dist is not None:
-        full = sharding.gather_results([[r.as_tuple() for r in rr] for rr in res], total, cap=64,
-                                       device=torch.device("cuda", local))
-        n_matches = [len(r) for r in full]
+        report = sharding.gather_results(res, total, cap=64, device=torch.device("cuda", local))
+        n_matches = [len(r) for r in report]
         if exchange:
             cnt, arr = gathered[0]
-            if [[tuple(float(v) for v in arr[i, j]) for j in range(int(cnt[i]))] for i in range(total)] != full:
-                log(f"[rank {rank}] the timed all-gather differs from the reference pass's report")
+            if [[tuple(float(v) for v in arr[i, j]) for j in range(int(cnt[i]))] for i in range(total)] != report:
+                log(f"[rank {rank}] the timed all-gather differs from the last pass's report")
                 sys.exit(3)
     else:
         n_matches = [len(r) for r in res]
@@ -565,11 +623,13 @@ def main():
                                   "49 w_l h_l per live refinement ROI; 2 ops per MAC) / the timed wall time, vs the "
                                   "i8 MFMA dense peak"}
 
-    kern, roofline, issue = kernel_pass(m, chunks[0], args.steps, L, args.workload)
-    # the refinement correlation kernel (k_roi_corr: the layers whose template is too large for k_roi_small, the
-    # lowest ones) on its useful MACs per launch -- the banded GEMM also computes the (t, s) pairs outside the band
-    roofline_corr = None
-    if "roi_corr" in kern:
+    # --full: the per-kernel pass (a run of its own: K more eager steps of one context), and from its table the
+    # refinement correlation kernel (k_roi_corr: the layers whose template is too large for k_roi_small, the lowest
+    # ones) on its useful MACs per launch -- the banded GEMM also computes the (t, s) pairs outside the band
+    kern = roofline = issue = roofline_corr = None
+    if args.full:
+        kern, roofline, issue = kernel_pass(m, chunks[0], args.steps, L, args.workload)
+    if kern and "roi_corr" in kern:
         n_corr = kern["roi_corr"]["launches"] // args.steps
         _, mr = search_macs(m, src_wh, tmpl_wh, len(chunks[0]))
         if n_corr > 0:
@@ -630,23 +690,27 @@ def main():
         "ms_per_search": round(elapsed * 1e3 / (args.batch * args.steps), 4),
         "last_step_split_ms_ctx0": {"device": round(dev_ms, 4), "host_finish": round(host_ms, 4),
                                     "launch_to_finish": round(call_ms, 4)},
-        "single_search_ms_end_to_end": round(lat_e2e * 1e3, 3) if lat_e2e is not None else None,
-        "single_search_split_ms": lat_split,
-        "vs_baseline_latency": (round(readme_ms / (lat_e2e * 1e3), 2) if readme_ms and lat_e2e is not None
-                                else None),
-        "vs_baseline_note": ("vs_baseline_latency = README Src7 76 ms / this single search end to end (like for "
-                             "like); vs_baseline = batch throughput / (1 / 76 ms), not like for like" if readme_ms
+        "vs_baseline_note": ("vs_baseline_latency (--full) = README Src7 76 ms / this single search end to end (like "
+                             "for like); vs_baseline = batch throughput / (1 / 76 ms), not like for like" if readme_ms
                              else "no published number for this config"),
-        "timed_results_verified": True,
         "matches_per_search": n_matches,
-        "kernels": kern,
-        "roofline": roofline,
-        "roofline_issue": issue,
         "roofline_search": roofline_search,
         "roofline_mac": roofline_mac,
-        "roofline_corr": roofline_corr,
+        "full": args.full,
     }
-    if world == 1 and rank == 0 and args.cpu_budget > 0:
+    if args.full:
+        out.update({
+            "single_search_ms_end_to_end": round(lat_e2e * 1e3, 3) if lat_e2e is not None else None,
+            "single_search_split_ms": lat_split,
+            "vs_baseline_latency": (round(readme_ms / (lat_e2e * 1e3), 2) if readme_ms and lat_e2e is not None
+                                    else None),
+            "timed_results_verified": True,
+            "kernels": kern,
+            "roofline": roofline,
+            "roofline_issue": issue,
+            "roofline_corr": roofline_corr,
+        })
+    if args.full and world == 1 and rank == 0 and args.cpu_budget > 0:
         # the CPU leg first checks the timed work against the oracle: the reference pass (== the timed pass, verify)
         # equals the oracle on every timed source, field for field; exit 4 on any difference
         nver = oracle_verify(templ, sources, ref, params)   # exits 4 on a mismatch
@@ -659,7 +723,7 @@ def main():
         out["cpu_baseline"], out["cpu_baseline_variants"] = cpu_baseline(templ, sources[0], args.cpu_budget, params,
                                                                          what)
         out["cpu_baseline"].update(cpu_identity())
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -694,7 +758,9 @@ def run_config4(args, world, rank, local, dist, barrier_sync):
         assert m.learnPattern(templ)
         m.stage(sources)
     m = ctxs[0]
-    ref = [[r.as_tuple() for r in rr] for rr in m.match_staged()]   # the unsharded search of the set, for the checks
+    ref = None
+    if args.full:   # the unsharded search of the set, for the check of the timed results
+        ref = [[r.as_tuple() for r in rr] for rr in m.match_staged()]
     for c in ctxs:
         c.setAngleShard(rank, world)
     tw, th = templ.shape[1], templ.shape[0]
@@ -726,7 +792,9 @@ def run_config4(args, world, rank, local, dist, barrier_sync):
     res = run(args.steps)
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    if res != ref:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
+    if ref is not None and res != ref:
         log(f"[rank {rank}] the angle-sharded step's results differ from the unsharded search of the set")
         sys.exit(3)
     if dist is not None:
@@ -749,11 +817,13 @@ def run_config4(args, world, rank, local, dist, barrier_sync):
                                     f"over {G} contexts (one's device pass overlaps the other's exchange and merge)",
                    "contexts_per_gpu": G},
         "ms_per_search": round(elapsed * 1e3 / (len(sources) * args.steps), 4),
-        "timed_results_verified": True,
         "matches_per_search": [len(r) for r in res],
         "vs_baseline_note": "no published number for this config",
+        "full": args.full,
     }
-    if world == 1 and rank == 0 and args.cpu_budget > 0:
+    if args.full:
+        out["timed_results_verified"] = True
+    if args.full and world == 1 and rank == 0 and args.cpu_budget > 0:
         from fastest_image_pattern_matching_amd.matcher import SingleTargetMatch
 
         refs = [[SingleTargetMatch.from_row(np.array(r)) for r in rr] for rr in res]
@@ -763,7 +833,7 @@ def run_config4(args, world, rank, local, dist, barrier_sync):
         out["cpu_baseline"], out["cpu_baseline_variants"] = cpu_baseline(templ, sources[0], args.cpu_budget, params,
                                                                          "Src5 set")
         out["cpu_baseline"].update(cpu_identity())
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of an environment switch of the library: GPU tests with it on, then the bench's kernel pass under rocprofv3
-# --kernel-trace --stats with it off and on (per-launch-position times: scripts/layer_times.py), then the default bench
-# with it off and on.  usage: scripts/gpu_ab_env.sh VAR tag [tests]
+# --kernel-trace --stats with it off and on (per-launch-position times: scripts/layer_times.py), then the bench (--full, no CPU
+# leg or latency probe) with it off and on.  usage: scripts/gpu_ab_env.sh VAR tag [tests]
 VAR=$1; TAG=${2:-ab}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/ab_$TAG
@@ -15,6 +15,6 @@ for v in 0 1; do
   cd $ROOT && echo "== $VAR=$v" && python3 scripts/layer_times.py $OUT/p$v/run_kernel_trace.csv | head -8
 done
 for v in 0 1; do
-  env $VAR=$v timeout -k 10 300 python -u bench.py --cpu-budget 0 --skip-latency > $OUT/bench$v.json 2> $OUT/bench$v.log || exit 1
+  env $VAR=$v timeout -k 10 300 python -u bench.py --full --cpu-budget 0 --skip-latency > $OUT/bench$v.json 2> $OUT/bench$v.log || exit 1
   python3 -c "import json; d=json.load(open('$OUT/bench$v.json')); print('$VAR=$v bench', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'], d['timed_results_verified'])"
 done

@@ -21,5 +21,5 @@ for k, v in sorted(d["kernels"].items(), key=lambda x: -x[1]["ms_total"]):
 print("total us/pass", round(sum(v["ms_total"] for v in d["kernels"].values()) / st * 1000, 1), "roofline", d["roofline"]["frac"], d["roofline"]["avg_launch_us"])
 PY
 S=$(find $OUT/prof_$TAG -name '*kernel_stats.csv' | head -1); [ -n "$S" ] && cp $S $OUT/kernel_stats_$TAG.csv && cut -d, -f1-4 $S | head -16
-timeout -k 10 400 python -u bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.log || exit $?
+timeout -k 10 400 python -u bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.log || exit $?
 python3 -c "import json,sys; d=json.load(open('$OUT/bench_$TAG.json')); print('bench', d['value'], d['ms_per_step'], d['single_search_ms_end_to_end'], d['single_search_split_ms'], d['roofline']['frac'])"

@@ -1,10 +1,11 @@
 // TEST FIXTURE (tests/dropin): the OpenCV core types the drop-in TemplateMatcher_fpm.cpp and the reference's own
 // headers (include/DataStructures.h, TemplateMatcher.h, SIMDOptimization.h) name, so the drop-in translation unit
-// compiles -- against this directory's header excerpts on the GPU box, and against the unmodified reference headers
-// in tests/test_dropin_real_headers.py -- where no OpenCV exists.  Not OpenCV: the member functions are the ones
+// compiles -- against this directory's header excerpts in the tests, or against the unmodified reference headers on
+// a host that has them -- where no OpenCV exists.  Not OpenCV: the member functions are the ones
 // those files use, with OpenCV's meaning; the DATA LAYOUT of every type a reference struct holds by value is OpenCV
 // 4.x's on x86-64 (cv::Mat's 12 members, 96 bytes; Rect_ / Point_ / Size_ / Scalar_ / RotatedRect as in
-// core/types.hpp), so sizeof(TemplateMatcher) compiled here equals the reference build's.
+// core/types.hpp; tests/test_dropin_layout.py asserts these sizes), so sizeof(TemplateMatcher) compiled with the
+// reference's headers equals the reference build's.
 #pragma once
 #include <algorithm>
 #include <cstddef>

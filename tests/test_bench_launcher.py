@@ -82,6 +82,40 @@ def test_search_macs_follow_survey_formula():
     assert mr == [n * n3 * 49 * w * h for n, (w, h) in zip(live, layers)]
 
 
+def test_make_sources_equal_src7_scene():
+    """bench.make_sources renders the pasted copies once and draws only the noise per scene: every scene equals
+    synth.src7_scene of its seed bit for bit (half size here; the poses scale with the scene)."""
+    import numpy as np
+
+    from fastest_image_pattern_matching_amd import synth
+
+    b = _bench_module()
+    t = synth.load_templates()["Dst7"]
+    got = b.make_sources(t, 3, 1007, w=2012, h=1518)
+    assert len(got) == 3
+    for i, s in enumerate(got):
+        exp = synth.src7_scene(t, 2012, 1518, seed=1007 + i)[0]
+        assert s.dtype == np.uint8 and s.flags["C_CONTIGUOUS"] and np.array_equal(s, exp)
+
+
+def test_dump_outputs_layout(tmp_path):
+    """--dump-outputs: counts.npy [sources] and results.npy [sources, most results of a source, 12], float64, zero past
+    a source's count; one pair per rank when there are several."""
+    import numpy as np
+
+    b = _bench_module()
+    r0, r1 = tuple(float(i) + 0.25 for i in range(12)), tuple(-float(i) for i in range(12))
+    b.dump_outputs(str(tmp_path / "d"), [[r0, r1], [], [r1]])
+    cnt, res = np.load(tmp_path / "d" / "counts.npy"), np.load(tmp_path / "d" / "results.npy")
+    assert cnt.dtype == np.float64 and cnt.tolist() == [2.0, 0.0, 1.0]
+    assert res.dtype == np.float64 and res.shape == (3, 2, 12)
+    assert tuple(res[0, 0]) == r0 and tuple(res[0, 1]) == r1 and tuple(res[2, 0]) == r1
+    assert not res[1].any() and not res[2, 1].any()
+    b.dump_outputs(str(tmp_path / "e"), [[], []], rank=1, world=2)
+    assert np.load(tmp_path / "e" / "counts_rank1.npy").tolist() == [0.0, 0.0]
+    assert np.load(tmp_path / "e" / "results_rank1.npy").shape == (2, 1, 12)
+
+
 def test_config4_shards_angles_over_ranks():
     """--workload config4 (BASELINE.json configs[4]): the 8-image Src5 set searched on every rank, each rank its block
     of the top-layer angle list (angle shard rank / world)."""

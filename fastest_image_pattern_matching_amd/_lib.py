@@ -69,6 +69,13 @@ class Candidate(C.Structure):
                 ("kept", C.c_int32)]
 
 
+class RoiRecord(C.Structure):
+    """fpm_roi_record — what the search keeps of one refinement ROI's 7x7 map."""
+
+    _fields_ = [("score", C.c_float), ("mx", C.c_int32), ("my", C.c_int32), ("on_border", C.c_int32),
+                ("vec", C.c_float * 9)]
+
+
 # every symbol include/fpm.h declares, with (restype, argtypes)
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
@@ -96,6 +103,9 @@ SIGNATURES = {
                                      C.c_int32, C.c_int32, C.c_size_t, C.c_int32]),
     "fpm_op_ncc_map": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_float)]),
+    "fpm_op_refine": (C.c_int, [_P, C.POINTER(_U8P), C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_int32,
+                                C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.POINTER(RoiRecord), _U8P, C.POINTER(C.c_int32)]),
     "fpm_op_overlap_filter": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32, C.c_double,
                                         C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "fpm_template_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -163,6 +163,8 @@ struct fpm_ctx {
     uint64_t plan_gen = ~0ull;
     // op scratch
     DevBuf d_op_a, d_op_b, d_op_job;
+    // fpm_op_refine's per-ROI scratch (the plan's d_tab .. d_wsq belong to the recorded search)
+    DevBuf d_rf_tab, d_rf_tdesc, d_rf_roi, d_rf_rowsum, d_rf_wsum, d_rf_wsq;
     // filterWithRotatedRect on the device (overlap_filter_device): rectangles + counters; staging and mapped outputs
     DevBuf d_ov;
     PinBuf h_ov_in, h_ov_out;
@@ -301,6 +303,58 @@ AngleNode make_node(double angle) {
     n.c = std::cos(r); n.s = std::sin(r);
     n.cn = std::cos(-r); n.sn = std::sin(-r);
     return n;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// layouts the refinement kernels rely on, shared by the search (layout_sources, build_plan) and fpm_op_refine
+// ---------------------------------------------------------------------------------------------------------
+// One image of a source pyramid level in the device slab (off is the caller's).
+SrcLevel level_layout(int w, int h) {
+    SrcLevel s{};
+    s.w = w; s.h = h;
+    s.pitch = round_up(w + 4, 64);          // +4: aligned dword over-reads stay in the row
+    s.img_bytes = round_up((size_t)s.pitch * (h + 1), (size_t)256);   // one spare row per image
+    return s;
+}
+// Slack past the last image of a slab whose largest level has row pitch `pitch0`: the ROI sampler's footprint staging
+// reads whole 16-row groups, up to 15 rows past a box (k_roi_warp3), i.e. past the last image's spare row
+size_t level_slab_slack(int pitch0) { return 16 * (size_t)pitch0 + 256; }
+
+// Per-ROI refinement scratch (tables, tile descriptors, sampled ROI, row sums, window partials) sized for the largest
+// of the template levels lv[0 .. nlv).
+struct RoiScratchDims {
+    int tabw = 1, tabh = 1, roi_pitch = 1, tdesc_stride = 1;
+    size_t roi_stride = 0, max_rows = 1, max_chunks = 1;
+    size_t per_roi() const {
+        return sizeof(int32_t) * 2 * (tabw + tabh) + sizeof(int4) * tdesc_stride + roi_stride + max_rows * 49 * 4 +
+               max_chunks * 49 * 12;
+    }
+};
+RoiScratchDims roi_scratch_dims(const TmplLevel* lv, int nlv) {
+    RoiScratchDims d;
+    int max_w = 1;
+    for (int l = 0; l < nlv; ++l) {
+        d.tdesc_stride = std::max(d.tdesc_stride, roi_tiles_for(lv[l].w, lv[l].h));
+        const int rc = roi_pick_rc(lv[l].w, lv[l].h);
+        d.max_rows = std::max(d.max_rows, (size_t)lv[l].h);
+        d.max_chunks = std::max(d.max_chunks, (size_t)(lv[l].h + rc - 1) / rc);
+        max_w = std::max(max_w, lv[l].w);
+        d.roi_stride = std::max(d.roi_stride, roi_tiles_bytes(lv[l].w, lv[l].h));
+    }
+    d.roi_pitch = roi_pitch_for(max_w);
+    d.tabw = d.roi_pitch;
+    d.tabh = roi_tab_rows((int)d.max_rows);
+    return d;
+}
+hipError_t roi_scratch_ensure(const RoiScratchDims& d, size_t slots, DevBuf& tab, DevBuf& tdesc, DevBuf& roi,
+                              DevBuf& rowsum, DevBuf& wsum, DevBuf& wsq) {
+    hipError_t e = tab.ensure(slots * 2 * (d.tabw + d.tabh) * sizeof(int32_t));
+    if (e == hipSuccess) e = tdesc.ensure(slots * d.tdesc_stride * sizeof(int4));
+    if (e == hipSuccess) e = roi.ensure(slots * d.roi_stride);
+    if (e == hipSuccess) e = rowsum.ensure(slots * round_up(d.max_rows * 49, (size_t)4) * 4);
+    if (e == hipSuccess) e = wsum.ensure(slots * d.max_chunks * 49 * 4);
+    if (e == hipSuccess) e = wsq.ensure(slots * d.max_chunks * 49 * 8);
+    return e;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -592,24 +646,13 @@ int build_plan(fpm_ctx* ctx) {
     HIP_TRY(P.d_state2.ensure(sizeof(CandState) * (size_t)P.C));
     HIP_TRY(P.d_rec2.ensure(sizeof(RoiRecord) * (size_t)P.C * P.n3));
     {   // refinement scratch per ROI (tables, sampled ROI, row sums, window partials); bounded, rounds cover the rest
-        size_t max_rows = 1, max_chunks = 1;
-        int max_w = 1;
-        P.tdesc_stride = 1;
-        for (int l = 0; l < L; ++l) {
-            P.tdesc_stride = std::max(P.tdesc_stride, roi_tiles_for(ctx->tmpl[l].w, ctx->tmpl[l].h));
-            const int rc = roi_pick_rc(ctx->tmpl[l].w, ctx->tmpl[l].h);
-            max_rows = std::max(max_rows, (size_t)ctx->tmpl[l].h);
-            max_chunks = std::max(max_chunks, (size_t)(ctx->tmpl[l].h + rc - 1) / rc);
-            max_w = std::max(max_w, ctx->tmpl[l].w);
-        }
-        P.roi_pitch = roi_pitch_for(max_w);
-        P.tabw = P.roi_pitch;
-        P.tabh = roi_tab_rows((int)max_rows);
-        P.roi_stride = 0;
-        for (int l = 0; l < L; ++l)
-            P.roi_stride = std::max(P.roi_stride, roi_tiles_bytes(ctx->tmpl[l].w, ctx->tmpl[l].h));
-        const size_t per_roi = sizeof(int32_t) * 2 * (P.tabw + P.tabh) + sizeof(int4) * P.tdesc_stride + P.roi_stride + max_rows * 49 * 4 +
-                               max_chunks * 49 * 12;
+        const RoiScratchDims rd = roi_scratch_dims(ctx->tmpl.data(), L);
+        P.tdesc_stride = rd.tdesc_stride;
+        P.roi_pitch = rd.roi_pitch;
+        P.tabw = rd.tabw;
+        P.tabh = rd.tabh;
+        P.roi_stride = rd.roi_stride;
+        const size_t per_roi = rd.per_roi();
         // slots are sized for the worst case (every top candidate alive at every layer) so the captured graph needs
         // no host round trip; up to a sixth of the free HBM (<= 48 GB of 288; FPM_SCRATCH_MB caps it) holds them,
         // rounds only beyond that.  A floor of min(4 GB, half the free HBM) keeps a batch in few rounds when another
@@ -626,12 +669,8 @@ int build_plan(fpm_ctx* ctx) {
         // rounds hold whole candidates (k_roi_eval steps a candidate from its n3 records)
         P.slot_cap = (int)std::max<size_t>((size_t)P.n3, std::min(want, budget / per_roi) / P.n3 * P.n3);
         for (;;) {
-            hipError_t e = P.d_tab.ensure((size_t)P.slot_cap * 2 * (P.tabw + P.tabh) * sizeof(int32_t));
-            if (e == hipSuccess) e = P.d_tdesc.ensure((size_t)P.slot_cap * P.tdesc_stride * sizeof(int4));
-            if (e == hipSuccess) e = P.d_roi.ensure((size_t)P.slot_cap * P.roi_stride);
-            if (e == hipSuccess) e = P.d_rowsum.ensure((size_t)P.slot_cap * round_up(max_rows * 49, (size_t)4) * 4);
-            if (e == hipSuccess) e = P.d_wsum.ensure((size_t)P.slot_cap * max_chunks * 49 * 4);
-            if (e == hipSuccess) e = P.d_wsq.ensure((size_t)P.slot_cap * max_chunks * 49 * 8);
+            const hipError_t e = roi_scratch_ensure(rd, (size_t)P.slot_cap, P.d_tab, P.d_tdesc, P.d_roi, P.d_rowsum,
+                                                    P.d_wsum, P.d_wsq);
             if (e == hipSuccess) break;
             (void)hipGetLastError();   // clear the sticky allocation error
             if (e != hipErrorOutOfMemory || P.slot_cap <= P.n3) HIP_TRY(e);
@@ -733,17 +772,13 @@ int layout_sources(fpm_ctx* ctx, int count, int w, int h) {
     int lw = w, lh = h;
     for (int l = 0; l <= L; ++l) {
         SrcLevel& s = ctx->src[l];
-        s.w = lw; s.h = lh;
-        s.pitch = round_up(lw + 4, 64);          // +4: aligned dword over-reads stay in the row
-        s.img_bytes = round_up((size_t)s.pitch * (lh + 1), (size_t)256);
+        s = level_layout(lw, lh);
         s.off = off;
         off += s.img_bytes * count;
         lw = (lw + 1) / 2;
         lh = (lh + 1) / 2;
     }
-    // slack: the ROI sampler's footprint staging reads whole 16-row groups, up to 15 rows past a box (k_roi_warp3),
-    // i.e. past the last image's spare row
-    HIP_TRY(ctx->d_src.ensure(off + 16 * (size_t)ctx->src[0].pitch + 256));
+    HIP_TRY(ctx->d_src.ensure(off + level_slab_slack(ctx->src[0].pitch)));
     return FPM_OK;
 }
 
@@ -1639,6 +1674,8 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->plan.release();
     ctx->d_tmpl.release(); ctx->d_tmpl8.release(); ctx->d_tsum.release(); ctx->d_src.release();
     ctx->d_op_a.release(); ctx->d_op_b.release(); ctx->d_op_job.release();
+    for (DevBuf* b : {&ctx->d_rf_tab, &ctx->d_rf_tdesc, &ctx->d_rf_roi, &ctx->d_rf_rowsum, &ctx->d_rf_wsum, &ctx->d_rf_wsq})
+        b->release();
     ctx->d_ov.release(); ctx->h_ov_in.release(); ctx->h_ov_out.release();
     for (auto& k : ctx->kp)
         for (auto& e : k.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -2055,6 +2092,156 @@ int fpm_op_ncc_map(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, ctx->d_op_b.p, sizeof(float) * (size_t)ow * oh, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FPM_OK;
+}
+
+// One refinement layer on caller-supplied ROIs, by the search's own launches (enqueue_search's layer loop with
+// step = 0: no candidate step, no prologue, no next-layer tables).
+int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int32_t w, int32_t h, size_t stride,
+                  int32_t layer, const float* lt, const double* angles, int32_t n, int32_t n3, int32_t fold,
+                  int32_t round_rois, fpm_roi_record* rec, uint8_t* roi_pixels, int32_t* pixels_written) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (pixels_written) *pixels_written = 0;
+    if (!ctx->learned) { ctx->err = "template not learned"; return FPM_E_NOT_LEARNED; }
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    constexpr int kMaxCoord = 8192;      // ROI coordinates stay inside the samplers' 16.16 fixed-point tables
+    constexpr int64_t kMaxRois = 1 << 20;
+    if (!levels || !lt || !angles || !rec || !pixels_written || count <= 0 || w <= 0 || h <= 0 || w > kMaxCoord ||
+        h > kMaxCoord || stride < (size_t)w || n <= 0 || (int64_t)count * n * 3 > kMaxRois) {
+        ctx->err = "bad refine arguments";
+        return FPM_E_INVALID_ARG;
+    }
+    if (layer < 0 || layer >= (int)ctx->tmpl.size()) { ctx->err = "bad layer"; return FPM_E_INVALID_ARG; }
+    if (n3 != 1 && n3 != 3) { ctx->err = "n3 must be 1 or 3"; return FPM_E_INVALID_ARG; }
+    if (round_rois < 0 || round_rois % n3 != 0) {
+        ctx->err = "round_rois must be a multiple of n3";
+        return FPM_E_INVALID_ARG;
+    }
+    for (int i = 0; i < count; ++i)
+        if (!levels[i]) { ctx->err = "null level image"; return FPM_E_INVALID_ARG; }
+    const int C = count * n, total_rois = C * n3;
+    for (int i = 0; i < 2 * C; ++i)
+        if (!std::isfinite(lt[i]) || std::fabs(lt[i]) > (float)kMaxCoord) {
+            ctx->err = "ptLT not finite or out of range";
+            return FPM_E_INVALID_ARG;
+        }
+    for (int i = 0; i < total_rois; ++i)
+        if (!std::isfinite(angles[i])) { ctx->err = "angle not finite"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const TmplLevel& tl = ctx->tmpl[layer];
+    hipStream_t st = ctx->stream;
+    // the level images as a search's slab holds one level: the layout and the slack the samplers read into
+    const SrcLevel lv = level_layout(w, h);
+    HIP_TRY(ctx->d_op_a.ensure(lv.img_bytes * count + level_slab_slack(lv.pitch)));
+    for (int s = 0; s < count; ++s)
+        HIP_TRY(hipMemcpy2DAsync(ctx->d_op_a.as<uint8_t>() + lv.img_bytes * s, lv.pitch, levels[s], stride, w, h,
+                                 hipMemcpyHostToDevice, st));
+    // candidates: id = source * n + i, alive, its node = id; the kernels sample at state.lt * 2 (the search keeps ptLT at
+    // the layer above's resolution), so the state holds ptLT / 2 -- exact for a float (a power-of-two scaling; the
+    // values here are far from the subnormal range or zero), and the kernels see the caller's ptLT bit for bit
+    std::vector<CandState> hs(C);
+    std::vector<int32_t> hl(C + 1);
+    std::vector<AngleNode> hn((size_t)total_rois);
+    for (int i = 0; i < C; ++i) {
+        hs[i].lt = f2(lt[2 * i] / 2, lt[2 * i + 1] / 2);
+        hs[i].node = i; hs[i].alive = 1; hs[i].reached0 = 0; hs[i].pad = 0;
+        hl[i] = i;
+        for (int j = 0; j < n3; ++j) hn[(size_t)i * n3 + j] = make_node(angles[(size_t)i * n3 + j]);
+    }
+    hl[C] = C;   // the live count
+    const size_t o_state = 0, o_live = round_up(sizeof(CandState) * C, (size_t)256),
+                 o_nodes = o_live + round_up(sizeof(int32_t) * (C + 1), (size_t)256),
+                 o_rec = o_nodes + round_up(sizeof(AngleNode) * total_rois, (size_t)256);
+    HIP_TRY(ctx->d_op_b.ensure(o_rec + sizeof(RoiRecord) * (size_t)total_rois));
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_state), hs.data(), sizeof(CandState) * C, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_live), hl.data(), sizeof(int32_t) * (C + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_nodes), hn.data(), sizeof(AngleNode) * total_rois, hipMemcpyHostToDevice,
+                           st));
+    HIP_TRY(hipMemsetAsync(ctx->d_op_b.as<char>(o_rec), 0, sizeof(RoiRecord) * (size_t)total_rois, st));
+    const int slot_cap = round_rois > 0 ? std::min(round_rois, total_rois) : total_rois;
+    const bool small = roi_small_fits(tl.w, tl.h);   // the search's form rule
+    const RoiScratchDims rd = roi_scratch_dims(&tl, 1);
+    if (!small)
+        HIP_TRY(roi_scratch_ensure(rd, (size_t)slot_cap, ctx->d_rf_tab, ctx->d_rf_tdesc, ctx->d_rf_roi, ctx->d_rf_rowsum,
+                                   ctx->d_rf_wsum, ctx->d_rf_wsq));
+    RoiArgs ra{};
+    ra.level = ctx->d_op_a.as<uint8_t>(); ra.level_stride = lv.img_bytes;
+    ra.W = lv.w; ra.H = lv.h; ra.P = lv.pitch;
+    ra.tmpl = ctx->d_tmpl.as<uint8_t>() + tl.off; ra.tw = tl.w; ra.th = tl.h; ra.tp = tl.pitch;
+    ra.tmpl8 = ctx->d_tmpl8.as<int8_t>() + tl.off8; ra.tp8 = tl.p8; ra.nk = (tl.w + 63) / 64;
+    ra.tsum = ctx->d_tsum.as<int32_t>() + tl.tsum_off;
+    ra.n3 = n3;
+    ra.rc = roi_pick_rc(tl.w, tl.h);
+    ra.nchunk = (tl.h + ra.rc - 1) / ra.rc;
+    ra.fold = fold ? 1 : 0;
+    ra.equal1 = tl.equal1 ? 1 : 0;
+    ra.per_source = n;
+    ra.mean = tl.mean; ra.norm = tl.norm; ra.inv_area = tl.inv_area;
+    ra.live = ctx->d_op_b.as<int32_t>(o_live);
+    ra.live_count = ra.live + C;
+    ra.state = ctx->d_op_b.as<CandState>(o_state);
+    ra.nodes = ctx->d_op_b.as<AngleNode>(o_nodes);
+    ra.tab = ctx->d_rf_tab.as<int32_t>(); ra.tabw = roi_pitch_for(tl.w); ra.tabh = roi_tab_rows(tl.h);
+    ra.tdesc = ctx->d_rf_tdesc.as<int4>(); ra.tdesc_stride = rd.tdesc_stride;
+    ra.roi = ctx->d_rf_roi.as<uint8_t>(); ra.roi_pitch = roi_pitch_for(tl.w); ra.roi_stride = rd.roi_stride;
+    ra.rowsum = ctx->d_rf_rowsum.as<uint32_t>();
+    ra.wsum = ctx->d_rf_wsum.as<uint32_t>();
+    ra.wsq = ctx->d_rf_wsq.as<uint64_t>();
+    ra.rec = ctx->d_op_b.as<RoiRecord>(o_rec);
+    ra.step = 0;   // records only: no candidate step, no prev_rec prologue, no next-layer tables
+    const bool want_px = roi_pixels && !small && !tl.equal1;
+    const int RW = tl.w + 6, RH = tl.h + 6, txn = (RW + 31) / 32;
+    std::vector<uint8_t> tiles;
+    for (int base = 0; base < total_rois; base += slot_cap) {
+        ra.slot_base = base;
+        ra.slot_cap = std::min(slot_cap, total_rois - base);
+        if (small) {
+            ProfScope ps(ctx, FPM_K_ROI_SMALL, 0);
+            launch_roi_small(ra, st);
+            continue;
+        }
+        {
+            ProfScope ps(ctx, FPM_K_ROI_TABLES, 0);
+            launch_roi_tables(ra, st);
+        }
+        {
+            ProfScope ps(ctx, FPM_K_ROI_WARP, 0);
+            launch_roi_warp(ra, st);
+        }
+        {
+            ProfScope ps(ctx, FPM_K_ROI_CORR, 0);
+            launch_roi_corr(ra, st);
+        }
+        {
+            ProfScope ps(ctx, FPM_K_ROI_EVAL, 0);
+            launch_roi_eval(ra, st);
+        }
+        if (want_px) {   // this round's ROIs out of the tile-major scratch (32 x 32 tiles of 1 KB, bytes ^ 0x80)
+            tiles.resize((size_t)ra.slot_cap * rd.roi_stride);
+            HIP_TRY(hipMemcpyAsync(tiles.data(), ctx->d_rf_roi.p, tiles.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (int k = 0; k < ra.slot_cap; ++k) {
+                const uint8_t* t = tiles.data() + (size_t)k * rd.roi_stride;
+                uint8_t* o = roi_pixels + (size_t)(base + k) * RW * RH;
+                for (int y = 0; y < RH; ++y)
+                    for (int x = 0; x < RW; ++x)
+                        o[(size_t)y * RW + x] =
+                            t[((size_t)((y >> 5) * txn + (x >> 5)) << 10) + (y & 31) * 32 + (x & 31)] ^ 0x80;
+            }
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<RoiRecord> hr((size_t)total_rois);
+    HIP_TRY(hipMemcpyAsync(hr.data(), ctx->d_op_b.as<char>(o_rec), sizeof(RoiRecord) * hr.size(), hipMemcpyDeviceToHost,
+                           st));
+    HIP_TRY(hipStreamSynchronize(st));
+    prof_collect(ctx);
+    for (int i = 0; i < total_rois; ++i) {
+        fpm_roi_record& r = rec[i];
+        r.score = hr[i].score; r.mx = hr[i].mx; r.my = hr[i].my; r.on_border = hr[i].on_border;
+        std::copy(hr[i].vec, hr[i].vec + 9, r.vec);
+    }
+    *pixels_written = want_px ? 1 : 0;
     return FPM_OK;
 }
 

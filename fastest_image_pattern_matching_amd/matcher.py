@@ -57,6 +57,11 @@ CANDIDATE_DTYPE = np.dtype([("top_score", "<f8"), ("x", "<f8"), ("y", "<f8"), ("
 assert CANDIDATE_DTYPE.itemsize == C.sizeof(L.Candidate)
 
 
+# fpm_roi_record as a numpy record (include/fpm.h), 52 bytes
+ROI_RECORD_DTYPE = np.dtype([("score", "<f4"), ("mx", "<i4"), ("my", "<i4"), ("on_border", "<i4"), ("vec", "<f4", 9)])
+assert ROI_RECORD_DTYPE.itemsize == C.sizeof(L.RoiRecord)
+
+
 def merge_candidates(params: "L.Params", tmpl_w: int, tmpl_h: int, cands: np.ndarray) -> List[SingleTargetMatch]:
     """fpm_merge_candidates: the coupled tail of TemplateMatcher::match (TemplateMatcher.cpp:214, 262-432) over one
     source's candidate records in push order (all shards concatenated in shard order).  Host only (no device)."""
@@ -347,6 +352,36 @@ class TemplateMatcher:
         if rc != L.FPM_OK:
             raise ValueError(self.last_error())
         return out
+
+    def refine_rois(self, levels, layer: int, lt, angles, fold, round_rois: int = 0, pixels: bool = True):
+        """fpm_op_refine: one refinement layer of the search on caller-supplied ROIs.  levels: S same-size level
+        images; lt: (S, n, 2) ptLT in the level's coordinates; angles: (S, n, n3) degrees, n3 in (1, 3).  Returns
+        (records (S, n, n3) ROI_RECORD_DTYPE, ROI pixels (S, n, n3, th + 6, tw + 6) u8, or None where the form that
+        ran keeps the ROI on the chip)."""
+        gs = [_gray(g) for g in levels]
+        h, w = gs[0].shape
+        if any(g.shape != (h, w) or g.strides != gs[0].strides for g in gs):
+            raise ValueError("all level images must have the same size")
+        S = len(gs)
+        p = np.ascontiguousarray(lt, np.float32).reshape(S, -1, 2)
+        n = p.shape[1]
+        a = np.ascontiguousarray(angles, np.float64).reshape(S, n, -1)
+        n3 = a.shape[2]
+        rec = np.zeros((S, n, n3), ROI_RECORD_DTYPE)
+        px = None
+        if pixels and self.isPatternLearned() and 0 <= layer < self.template_info()[0]:
+            th, tw = self.template_level(layer)[0].shape
+            px = np.zeros((S, n, n3, th + 6, tw + 6), np.uint8)
+        wrote = C.c_int32()
+        ptrs = (L._U8P * S)(*[L.u8ptr(g) for g in gs])
+        rc = self._check(self._lib.fpm_op_refine(
+            self._ctx, ptrs, S, w, h, gs[0].strides[0], int(layer), p.ctypes.data_as(C.POINTER(C.c_float)),
+            a.ctypes.data_as(C.POINTER(C.c_double)), n, n3, 1 if fold else 0, int(round_rois),
+            rec.ctypes.data_as(C.POINTER(L.RoiRecord)), L.u8ptr(px) if px is not None else None, C.byref(wrote)),
+            "refine_rois")
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_op_refine failed with {rc}: {self.last_error()}")
+        return rec, (px if wrote.value else None)
 
     def overlap_filter(self, corners, scores, max_overlap: float, device: bool = True):
         """filterWithRotatedRect (TemplateMatcher.cpp:1133-1194) on rectangles given as rows (ltx, lty, rtx, rty, rbx,

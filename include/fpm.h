@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPM_ABI_VERSION 9
+#define FPM_ABI_VERSION 10
 
 /* status codes */
 #define FPM_OK 0
@@ -199,6 +199,26 @@ int fpm_op_ncc_map(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_
  * device pair-list entries. */
 int fpm_op_overlap_filter(fpm_ctx* ctx, const float* corners, const double* scores, int32_t n, double max_overlap,
                           int32_t mode, int32_t* keep, int32_t* n_keep, int32_t* stats);
+/* One refinement layer of the search (TemplateMatcher.cpp:299-328) on ROIs the caller supplies, through the search's
+ * own kernels and form selection (k_roi_small for small templates, else k_roi_tables -> k_roi_warp / k_roi_warp3 ->
+ * k_roi_corr -> k_roi_eval): for each ROI, getRotatedROI of a level image around a ptLT at an angle, the 7x7 map
+ * against pyramid level `layer` of the learned template, and what the search keeps of it. */
+typedef struct fpm_roi_record {
+    float score;          /* minMaxLoc maximum of the 7x7 map (the first one in row-major order)             */
+    int32_t mx, my;       /* its location                                                                    */
+    int32_t on_border;    /* bPosOnBorder (TemplateMatcher.cpp:321-322)                                      */
+    float vec[9];         /* vecResult[x+1][y+1] at [(x+1)*3 + (y+1)] (:323-328); zeros on the border        */
+} fpm_roi_record;
+/* levels: `count` level images of w x h (row stride `stride`).  lt: [count][n][2] ptLT (x, y) per candidate in the
+ * level's own coordinates (the value the search passes to getRotatedROI, its `lt * 2`; |x|, |y| <= 8192, as w and h:
+ * the range of the samplers' 16.16 fixed-point tables).  angles: [count][n][n3] degrees, n3 = 1 or 3.  fold as
+ * fpm_op_ncc_map.  round_rois: ROIs per round of launches (a multiple of n3; 0 = all in one round), the search's
+ * bounded-scratch rounds.  rec: [count][n][n3].  roi_pixels (may be NULL): [count][n][n3] dense (tw+6) x (th+6) u8
+ * sampled ROIs, written where the form materialises them (the k_roi_tables .. k_roi_eval path of a non-constant
+ * template; *pixels_written = 1), untouched otherwise (k_roi_small keeps the ROI in LDS; *pixels_written = 0). */
+int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int32_t w, int32_t h, size_t stride,
+                  int32_t layer, const float* lt, const double* angles, int32_t n, int32_t n3, int32_t fold,
+                  int32_t round_rois, fpm_roi_record* rec, uint8_t* roi_pixels, int32_t* pixels_written);
 /* Learned-template introspection: number of pyramid levels, per-level size and statistics
  * (s_TemplData, DataStructures.h:16-55). */
 int fpm_template_info(const fpm_ctx* ctx, int32_t* levels, int32_t* border_color);

@@ -469,10 +469,10 @@ struct SearchStats {
     std::vector<fpm_candidate> cands; // per push-order candidate: top score, angle index, peak rank, refined pose
     // per-layer refinement decisions (only when Matcher::trace is set; a diagnostic, no reference counterpart):
     // rows of kTraceCols doubles = origin, layer, n3, imax, then (angle, score, mx, my, runner-up score of the
-    // map) for j = 0..2
+    // map) for j = 0..2, then the ROIs' ptLT in the layer's coordinates (the `lt * 2` getRotatedROI is called with)
     std::vector<double> trace;
 };
-static const int kTraceCols = 19;
+static const int kTraceCols = 21;
 
 // ---------------------------------------------------------------------------------------------------
 // cv::matchTemplate(TM_CCORR) as OpenCV's CPU crossCorr computes it: float32 DFTs (SENSITIVITY MODE).
@@ -1132,6 +1132,7 @@ public:
                         row[4 + 5 * j] = nm[j].angle; row[5 + 5 * j] = nm[j].score;
                         row[6 + 5 * j] = nm[j].pt.x; row[7 + 5 * j] = nm[j].pt.y; row[8 + 5 * j] = second[j];
                     }
+                    row[19] = P2f(lt.x * 2, lt.y * 2).x; row[20] = P2f(lt.x * 2, lt.y * 2).y;
                     stats.trace.insert(stats.trace.end(), row, row + kTraceCols);
                 }
                 if (nm[imax].score < layer_score[l]) break;
@@ -1291,7 +1292,7 @@ int orc_cross_corr_f32(const uint8_t* img, int w, int h, size_t is, const uint8_
     return FPM_OK;
 }
 
-// refinement decision trace of the next matches (diagnostic): rows of 19 doubles, see SearchStats::trace
+// refinement decision trace of the next matches (diagnostic): rows of 21 doubles, see SearchStats::trace
 void orc_set_trace(void* h, int on) { ((orc::Matcher*)h)->trace = on != 0; }
 int orc_trace(void* h, double* out, int cap_rows) {
     auto* m = (orc::Matcher*)h;
@@ -1376,6 +1377,14 @@ void orc_warp_affine(const uint8_t* src, int w, int h, size_t ss, const double m
                      size_t ds, int border) {
     orc::Mat8 d = orc::warp_affine(orc::from_strided(src, w, h, ss), m, dw, dh, border);
     for (int y = 0; y < d.h; ++y) std::memcpy(dst + (size_t)y * ds, d.row(y), (size_t)d.w);
+}
+
+// getRotatedROI (TemplateMatcher.cpp:1074-1090) as the search calls it: the (tw + 6) x (th + 6) ROI around ptLT
+// (lt_x, lt_y) of `src` rotated by `angle` degrees; out is dense
+void orc_rotated_roi(const uint8_t* src, int w, int h, size_t ss, int tw, int th, float lt_x, float lt_y, double angle,
+                     uint8_t* out) {
+    orc::Mat8 d = orc::Matcher::rotated_roi(orc::from_strided(src, w, h, ss), tw, th, orc::P2f(lt_x, lt_y), angle);
+    for (int y = 0; y < d.h; ++y) std::memcpy(out + (size_t)y * d.w, d.row(y), (size_t)d.w);
 }
 
 void orc_rotation_matrix(float cx, float cy, double angle, double m[6]) {

@@ -11,8 +11,8 @@ def _scene_rotated(templates, name, poses, size, seed, bg=(128, 10)):
     return s, t
 
 
-def _run_both(hip, s, t, **prm):
-    o = oracle.OracleMatcher()
+def _run_both(hip, s, t, oracle_matcher=None, **prm):
+    o = oracle_matcher if oracle_matcher is not None else oracle.OracleMatcher()   # (pass one to read it afterwards)
     hip.resetParams()
     for k, v in prm.items():
         setattr(o.params, k, v)

@@ -22,7 +22,9 @@ _U8P = C.POINTER(C.c_uint8)
 _libs = {}
 TRACE_DTYPE = np.dtype([("origin", "<i4"), ("layer", "<i4"), ("n3", "<i4"), ("imax", "<i4"),
                         ("angle", "<f8", 3), ("score", "<f8", 3), ("x", "<f8", 3), ("y", "<f8", 3),
-                        ("second", "<f8", 3)])
+                        ("second", "<f8", 3), ("lt", "<f4", 2)])
+# the record a search keeps of one refinement ROI (fpm_roi_record / matcher.ROI_RECORD_DTYPE)
+ROI_RECORD_DTYPE = np.dtype([("score", "<f4"), ("mx", "<i4"), ("my", "<i4"), ("on_border", "<i4"), ("vec", "<f4", 9)])
 
 
 def load(path: str = ORACLE_LIB):
@@ -50,6 +52,8 @@ def load(path: str = ORACLE_LIB):
     lib.orc_pyr_down.argtypes = [_U8P, C.c_int, C.c_int, C.c_size_t, _U8P, C.c_size_t]
     lib.orc_warp_affine.argtypes = [_U8P, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), _U8P, C.c_int,
                                     C.c_int, C.c_size_t, C.c_int]
+    lib.orc_rotated_roi.argtypes = [_U8P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float,
+                                    C.c_double, _U8P]
     lib.orc_rotation_matrix.argtypes = [C.c_float, C.c_float, C.c_double, C.POINTER(C.c_double)]
     lib.orc_ncc_map.argtypes = [C.c_void_p, _U8P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                 C.POINTER(C.c_float)]
@@ -85,6 +89,34 @@ def warp_affine(img: np.ndarray, m, dsize, border: int = 0) -> np.ndarray:
     mm = (C.c_double * 6)(*np.asarray(m, np.float64).ravel().tolist())
     load().orc_warp_affine(_u8(img), w, h, img.strides[0], mm, _u8(out), dw, dh, out.strides[0], int(border))
     return out
+
+
+def rotated_roi(img: np.ndarray, tw: int, th: int, lt, angle: float) -> np.ndarray:
+    """getRotatedROI: the (th + 6, tw + 6) ROI of `img` around ptLT `lt` (the level's coordinates) at `angle` degrees."""
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    out = np.zeros((th + 6, tw + 6), np.uint8)
+    load().orc_rotated_roi(_u8(img), w, h, img.strides[0], tw, th, float(np.float32(lt[0])), float(np.float32(lt[1])),
+                           float(angle), _u8(out))
+    return out
+
+
+def roi_record(m: np.ndarray) -> np.ndarray:
+    """What the search keeps of a 7x7 refinement map (TemplateMatcher.cpp:316-328): the first maximum in row-major
+    order (cv::minMaxLoc), its location, bPosOnBorder, and off the border the 3x3 neighbourhood stored as
+    RoiRecord::vec, [(x + 1) * 3 + (y + 1)] (zeros on the border)."""
+    m = np.asarray(m, np.float32)
+    assert m.shape == (7, 7)
+    k = int(np.argmax(m))   # first occurrence of the maximum, row-major
+    my, mx = divmod(k, 7)
+    r = np.zeros((), ROI_RECORD_DTYPE)
+    r["score"], r["mx"], r["my"] = m[my, mx], mx, my
+    r["on_border"] = int(mx in (0, 6) or my in (0, 6))
+    if not r["on_border"]:
+        for x in (-1, 0, 1):
+            for y in (-1, 0, 1):
+                r["vec"][(x + 1) * 3 + (y + 1)] = m[my + y, mx + x]
+    return r
 
 
 def rotation_matrix(cx: float, cy: float, angle: float) -> np.ndarray:
@@ -198,16 +230,29 @@ class OracleMatcher:
     def trace(self) -> np.ndarray:
         """Refinement decisions of the last match (after set_trace): one structured row per (candidate, layer)
         with the candidate's push-order index, the layer, the chosen angle slot and the (angle, score, x, y) of
-        each of the up to 3 angles (TemplateMatcher.cpp:279-332), plus the runner-up value of each angle's map."""
+        each of the up to 3 angles (TemplateMatcher.cpp:279-332), plus the runner-up value of each angle's map and
+        the ROIs' ptLT in the layer's coordinates (`lt`, what getRotatedROI was called with)."""
         n = self._lib.orc_trace(self._h, None, 0)
-        buf = np.zeros((max(n, 1), 19), np.float64)
+        buf = np.zeros((max(n, 1), 21), np.float64)
         self._lib.orc_trace(self._h, buf.ctypes.data_as(C.POINTER(C.c_double)), n)
         buf = buf[:n]
         out = np.zeros(n, TRACE_DTYPE)
         out["origin"], out["layer"], out["n3"], out["imax"] = (buf[:, k].astype(np.int32) for k in range(4))
         for f, k in (("angle", 4), ("score", 5), ("x", 6), ("y", 7), ("second", 8)):
             out[f] = buf[:, k:19:5]
+        out["lt"] = buf[:, 19:21]
         return out
+
+    def refine_roi(self, level_img: np.ndarray, layer: int, lt, angle: float, fold):
+        """One refinement ROI as the search computes it (TemplateMatcher.cpp:299-328): getRotatedROI of `level_img`
+        around ptLT `lt` (the level's own coordinates, the search's `lt * 2`) at `angle` degrees, its 7x7 map against
+        template level `layer`, and the record the search keeps.  Returns (roi u8 (th+6, tw+6), map f32 (7, 7), record
+        ROI_RECORD_DTYPE scalar)."""
+        levels, _ = self.template_levels()
+        th, tw = levels[layer][0].shape
+        roi = rotated_roi(level_img, tw, th, lt, angle)
+        m = self.ncc_map(roi, layer, fold)
+        return roi, m, roi_record(m)
 
     def top_candidates(self):
         n = self._lib.orc_top_candidates(self._h, None, 0)

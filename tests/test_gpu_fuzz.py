@@ -57,3 +57,5 @@ def test_fuzz_parity(gpu_matcher_factory, seed):
     gpu = m.match(s)
     assert m.search_stats() == o.stats(), (seed, prm)
     assert_same_results(gpu, orc, f"fuzz{seed} {prm} t={t.shape} s={s.shape}")
+    # every top-layer candidate's refinement outcome, those a filter drops included
+    assert m.last_candidates(0).tobytes() == o.candidates().tobytes(), (seed, prm)

@@ -132,10 +132,13 @@ def test_ncc_map_tiled_multi_tile(hip, templates, shape):
 def test_match_parity(hip, templates, case):
     make, prm = CASES[case]
     s, t = make(templates)
-    gpu, orc, ostats, gstats = _run_both(hip, s, t, **prm)
+    o = oracle.OracleMatcher()
+    gpu, orc, ostats, gstats = _run_both(hip, s, t, oracle_matcher=o, **prm)
     assert gstats == ostats, (gstats, ostats)
     assert_same_results(gpu, orc, case)
     assert len(orc) >= 1
+    # every top-layer candidate's refinement outcome, those a filter drops included
+    assert hip.last_candidates(0).tobytes() == o.candidates().tobytes()
 
 
 def test_src7_full_search(hip, templates):

@@ -3116,6 +3116,90 @@ __device__ __forceinline__ void band_mfma_regs(const fpm_v4i* A, const uint8_t* 
     acc[0] = c0; acc[1] = c1; acc[2] = c2; acc[3] = c3; acc[4] = c4; acc[5] = c5; acc[6] = c6;
 }
 
+// Exact full-row sums of I and I^2 of one N tile (16 ROI rows staged in LDS as I' = I ^ 0x80 = I - 128) over nk k-steps
+// of 64 columns, on the matrix cores.  bp: the lane's row (lane & 15) at byte 16*(lane >> 4) of k-step 0, the dx = 0
+// B fragment of band_mfma*.  cs = ones x B: every D row holds the rows' sums of I'; cq = B x B (the A and B lane
+// layouts of this instruction coincide): the Gram matrix, whose diagonal holds the sums of I'^2 -- row n's in lane
+// (n, g = n >> 2), element n & 3.  Returned are the sums of the unsigned pixels over the C = 64 nk columns:
+// sum I = S1' + 128 C (in every lane of column n),  sum I^2 = S2' + 256 S1' + 16384 C (in the diagonal's lane only)
+// (mod 2^32; the true values < 2^31).  Every byte of the 16 rows' 64 nk columns must be defined.
+// VS: the sum of I' by v_dot4 over the lane's 16 bytes of every k-step (issued beside the Gram MFMA) and two
+// cross-lane adds, instead of the ones x B MFMA.  n = lane & 15.
+template <bool VS = false>
+__device__ __forceinline__ void tile_row_sums(const uint8_t* bp, int nk, int n, uint32_t& s1, uint32_t& s2) {
+    const fpm_v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+    fpm_v4i cs = {0, 0, 0, 0}, cq = cs;
+    int vs = 0;
+    auto dot16 = [](fpm_v4i b, int acc) {
+        acc = __builtin_amdgcn_sdot4(b[0], 0x01010101, acc, false);
+        acc = __builtin_amdgcn_sdot4(b[1], 0x01010101, acc, false);
+        acc = __builtin_amdgcn_sdot4(b[2], 0x01010101, acc, false);
+        return __builtin_amdgcn_sdot4(b[3], 0x01010101, acc, false);
+    };
+    int k = 0;
+    for (; k + 4 <= nk; k += 4) {   // 4 k-steps' LDS reads in flight
+        fpm_v4i b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) b[u] = *(const fpm_v4i*)__builtin_assume_aligned(bp + 64 * (k + u), 16);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (VS) vs = dot16(b[u], vs); else cs = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b[u], cs, 0, 0, 0);
+            cq = __builtin_amdgcn_mfma_i32_16x16x64_i8(b[u], b[u], cq, 0, 0, 0);
+        }
+    }
+    if (k + 2 <= nk) {
+        const fpm_v4i b0 = *(const fpm_v4i*)__builtin_assume_aligned(bp + 64 * k, 16);
+        const fpm_v4i b1 = *(const fpm_v4i*)__builtin_assume_aligned(bp + 64 * k + 64, 16);
+        if (VS) vs = dot16(b0, vs); else cs = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b0, cs, 0, 0, 0);
+        cq = __builtin_amdgcn_mfma_i32_16x16x64_i8(b0, b0, cq, 0, 0, 0);
+        if (VS) vs = dot16(b1, vs); else cs = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b1, cs, 0, 0, 0);
+        cq = __builtin_amdgcn_mfma_i32_16x16x64_i8(b1, b1, cq, 0, 0, 0);
+        k += 2;
+    }
+    if (k < nk) {
+        const fpm_v4i b0 = *(const fpm_v4i*)__builtin_assume_aligned(bp + 64 * k, 16);
+        if (VS) vs = dot16(b0, vs); else cs = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b0, cs, 0, 0, 0);
+        cq = __builtin_amdgcn_mfma_i32_16x16x64_i8(b0, b0, cq, 0, 0, 0);
+    }
+    const int e = n & 3;
+    if (VS) {
+        vs += __shfl_xor(vs, 16, 64);
+        vs += __shfl_xor(vs, 32, 64);
+    }
+    const uint32_t p1 = (uint32_t)(VS ? vs : cs[0]);
+    const uint32_t p2 = (uint32_t)(e == 0 ? cq[0] : e == 1 ? cq[1] : e == 2 ? cq[2] : cq[3]);
+    const uint32_t C = 64u * (uint32_t)nk;
+    s1 = p1 + 128u * C;
+    s2 = p2 + 256u * p1 + 16384u * C;
+}
+
+// The edge pixels of the window [dx, dx + tw) of a row whose full sums cover the columns [0, C): the sums of I and I^2
+// over the bytes that are in the full sum and not in the window, minus those in the window and not in the full sum.
+// lo: the row's bytes 0 .. 7, hi: its bytes tw .. tw + 7 (unsigned pixels); nf = min(6, C - tw) of the right-edge bytes
+// lie inside the full sum (C >= tw: 6 when the k-steps cover the whole row, fewer when RW = tw + 6 exceeds 64 nk).
+__device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, int nf, uint32_t& q1, uint32_t& q2) {
+    const uint64_t ldx = (1ull << (8 * dx)) - 1ull, lnf = (1ull << (8 * nf)) - 1ull;   // bytes < dx, bytes < nf
+    const uint64_t sl = lo & ldx;             // left: bytes < dx leave
+    const uint64_t sr = hi & lnf & ~ldx;      // right: bytes in [dx, nf) leave
+    const uint64_t ar = hi & ldx & ~lnf;      // right: bytes in [nf, dx) enter
+    const uint32_t a0 = (uint32_t)sl, a1 = (uint32_t)(sl >> 32), b0 = (uint32_t)sr, b1 = (uint32_t)(sr >> 32);
+    const uint32_t c0 = (uint32_t)ar, c1 = (uint32_t)(ar >> 32);
+    uint32_t p1 = __builtin_amdgcn_udot4(a0, 0x01010101u, 0u, false);
+    p1 = __builtin_amdgcn_udot4(a1, 0x01010101u, p1, false);
+    p1 = __builtin_amdgcn_udot4(b0, 0x01010101u, p1, false);
+    p1 = __builtin_amdgcn_udot4(b1, 0x01010101u, p1, false);
+    uint32_t m1 = __builtin_amdgcn_udot4(c0, 0x01010101u, 0u, false);
+    m1 = __builtin_amdgcn_udot4(c1, 0x01010101u, m1, false);
+    uint32_t p2 = __builtin_amdgcn_udot4(a0, a0, 0u, false);
+    p2 = __builtin_amdgcn_udot4(a1, a1, p2, false);
+    p2 = __builtin_amdgcn_udot4(b0, b0, p2, false);
+    p2 = __builtin_amdgcn_udot4(b1, b1, p2, false);
+    uint32_t m2 = __builtin_amdgcn_udot4(c0, c0, 0u, false);
+    m2 = __builtin_amdgcn_udot4(c1, c1, m2, false);
+    q1 = p1 - m1;
+    q2 = p2 - m2;
+}
+
 // MODE (profiling ablations in scripts/roi_microbench.hip; the product uses 0): 2 = no MFMA loop, 3 = no staging
 // (slot-major form only), 4 = no window-edge phase, 5 = no row-result stores, 6 = no window partials, 7 = no row sums
 // GA: A operand read from the global i8 slab (no template rows in LDS); WPE: register cap (waves per SIMD);
@@ -3123,7 +3207,13 @@ __device__ __forceinline__ void band_mfma_regs(const fpm_v4i* A, const uint8_t* 
 // PFR (register-A form): prefetch the next item's rows (false: load this item's rows at its start, fewer VGPRs)
 // RS: 1 = row statistics in one phase (a quad of lanes per row: its I / I^2 totals reduced by DPP, then the edge pixels
 // of each window subtracted by the same lanes; the window partials split over lane pairs), 0 = the earlier form (row
-// totals by LDS atomics, a separate edge phase, one thread per partial), 2 = as 1 with the partials before the GEMM
+// totals by LDS atomics, a separate edge phase, one thread per partial), 2 = as 1 with the partials before the GEMM,
+// 3 (the product up to 8 k-steps) = the full-row sums on the matrix cores (tile_row_sums: the owner wave of each N tile,
+// waves 0 / 1 / 3, reads its tile's dx = 0 B fragments as 16-byte LDS reads and issues 2 MFMAs per k-step, then
+// subtracts the window edges of its 16 rows itself: the same two barriers as 1, without its strided walk of 48 dwords
+// and 96 v_dot4 per lane at 12 k-steps), 4 (the product from 9 k-steps) = as 3 with the sum of I by v_dot4 beside the
+// one MFMA for I^2 (half the dependent MFMA chain, two cross-lane adds more: Src7 layer 0 346 -> 338 (3) -> 326 us (4)
+// per 64-source microbenchmark launch, layer 1 122 -> 117 (3) / 120 (4), profiles/rowstats_mfma/)
 // SE: the band's row results are written into LDS by the epilogue and copied to HBM as 16-byte runs during the next
 // item's staging (after the loads of its rows are issued, so waiting for those loads does not wait for these stores)
 // DMA (register-A form, no row prefetch): the item's ROI rows go global -> LDS by LDS-DMA (one global_load_lds_dwordx4
@@ -3144,6 +3234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     static_assert(!DB || DMA, "the double buffer is filled by LDS-DMA");
     static_assert(NK == 0 || (GA && MODE != 3), "the register-A form stages no template rows");
     static_assert(!SE || NK > 0, "the staged epilogue is flushed in the register-A form's staging phase");
+    static_assert(RS < 3 || NK > 0, "the matrix-core row sums read the register-A form's staged rows, every byte defined");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tw = a.tw, th = a.th, RW = tw + 6;
     const int SBp = a.roi_pitch;
@@ -3166,6 +3257,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const int g = lane >> 4, n = lane & 15;
     const int mt = wv & 1, nt = mt + (wv >> 1);                // this wave's (M, N) tile pair
     const int txn = (RW + ROI_T - 1) / ROI_T;
+    const int npad = max(0, (min(ROI_T * txn, 64 * a.nk) - 4 * nwr) >> 2);   // (RS >= 3) dwords inside the k-steps that no sampler writes (<= 7)
     const XcdSplit xs = xcd_split(items);   // the XCD group's contiguous range of items
     // NK = 0: items slot-major (an ROI's bands, which share rows, on one XCD group), grid-stride over the range.
     // NK > 0 (register-A form): items band-major (item = band * rois + slot) and each workgroup takes one
@@ -3203,6 +3295,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         }
     };
     if (NK > 0 && PFR && it_lo < it_hi) load_rows(it_lo);
+    if (RS >= 3 && DMA) {
+        // the LDS-DMA writes a row's chunks below 2 txn only; the matrix-core row sums read all 64 nk columns: the
+        // chunks past the ROI's tiles hold flipped zeros, written once (the DMA never overwrites them; the item loop's
+        // first barriers order these stores before the first read)
+        const int nfill = q4 - 2 * txn;
+        for (int b = 0; b < (DB ? 2 : 1); ++b)
+            for (int i = tid; i < kBandSrc * nfill; i += 256) {
+                const int r = i / nfill, c = 2 * txn + (i - r * nfill);
+                *(uint4*)((b ? SB1 : SB0) + (size_t)r * SBp + 16 * c) = make_uint4(kRoiFlip, kRoiFlip, kRoiFlip, kRoiFlip);
+            }
+    }
     // (SE) the previous item's row results: LDS -> its [rb][49] range of the ROI's series, 16-byte stores (the range
     // starts 16-byte aligned: slot stride and T0 * 49 are multiples of 4 words), the < 4-word tail by single words
     int pv_slot = -1, pv_T0 = 0, pv_rb = 0;
@@ -3306,7 +3409,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         }
         __syncthreads();
         if (DB && item + 1 < it_hi) dma_rows(item + 1, SB == SB0 ? SB1 : SB0);   // every wave is past the other buffer
-        if (RS >= 1 && MODE != 7 && tid < 4 * nsrc) {
+        if (RS >= 3 && MODE != 7 && wv != 2 && kMmaRows * nt < nsrc) {   // wave-uniform
+            // the owner waves of the three N tiles (wave 2 shares N tile 1 with wave 1): the tile's full-row sums, then
+            // the window edges of its 16 rows: every lane (n, g) holds row n's sum of I and fetches its sum of I^2 from
+            // the diagonal's lane (n, n >> 2); lane (n, g) then takes dx = g and g + 4 (window_edges).  No rall / rallq.
+            // (the lane index opaque: what derives from it is recomputed per item, not kept in registers across the
+            // item loop and the GEMM)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int g3 = ln >> 4, n3 = ln & 15, row = kMmaRows * nt + n3;
+            const int sr = row < nsrc ? row : 0;   // row outside the band: summed, never stored
+            uint32_t* rw = (uint32_t*)(SB + (size_t)sr * SBp);
+            if (npad > 0) {   // uniform
+                // the samplers leave the whole dwords past RW in the last column tile unwritten (the GEMM meets them
+                // with the template's zero padding): flipped zeros over those inside the k-steps, two by each of the
+                // row's four lanes, before this wave's own reads of the row (LDS operations of a wave stay in order)
+                if (g3 < npad) rw[nwr + g3] = kRoiFlip;
+                if (g3 + 4 < npad) rw[nwr + g3 + 4] = kRoiFlip;
+            }
+            const int wr = tw >> 2;
+            const uint32_t l0 = rw[0], l1 = rw[1], x0 = rw[wr], x1 = rw[wr + 1], x2 = rw[wr + 2];   // in flight with the MFMAs
+            uint32_t s1, s2;
+            tile_row_sums<RS == 4>((const uint8_t*)rw + 16 * g3, a.nk, n3, s1, s2);
+            s2 = (uint32_t)__shfl((int)s2, n3 + 16 * (n3 >> 2), 64);
+            const uint32_t e0 = __builtin_amdgcn_alignbyte(x1, x0, (uint32_t)tw) ^ 0x80808080u;
+            const uint32_t e1 = __builtin_amdgcn_alignbyte(x2, x1, (uint32_t)tw) ^ 0x80808080u;
+            const uint64_t lo = (uint64_t)(l0 ^ 0x80808080u) | ((uint64_t)(l1 ^ 0x80808080u) << 32);
+            const uint64_t hi = (uint64_t)e0 | ((uint64_t)e1 << 32);
+            const int nf = min(6, 64 * a.nk - tw);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int dx = g3 + 4 * h;
+                if (dx < 7 && row < nsrc) {
+                    uint32_t q1, q2;
+                    window_edges(lo, hi, dx, nf, q1, q2);
+                    wi[row * 7 + dx] = s1 - q1;
+                    wq[row * 7 + dx] = s2 - q2;
+                }
+            }
+        }
+        if ((RS == 1 || RS == 2) && MODE != 7 && tid < 4 * nsrc) {
             // row r's statistics by the quad of lanes 4r .. 4r + 3 (whole quads: DPP within the quad): exact full-row
             // sums of I and I^2 over the row's words (pixels past RW are zero), then each lane subtracts the window's
             // edge pixels for its dx (qq and qq + 4): window [dx, dx + tw) = row minus bytes [0, dx) and [dx + tw, RW)
@@ -3488,7 +3630,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
         if (FPM_CORR_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (RS == 1) partials();
+        if (RS == 1 || RS >= 3) partials();
         if (RS == 0 && MODE != 6 && tid < 2 * 49) {   // per-16-row-chunk partials of the window sums
             const int h = tid / 49, k = tid - h * 49;
             const int chunk = (T0 >> 4) + h;
@@ -4720,6 +4862,7 @@ constexpr int kCorrWaves = 3;
 constexpr int kCorrRunWaves = 2;
 template <int NK>
 static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream_t st) {
+    constexpr int kRS = NK > 8 ? 4 : 3;   // the row statistics' form (k_roi_corr's RS): measured per k-step count
     if constexpr (NK <= 12) {
         // up to 12 k-steps the A fragments fit 3 waves per SIMD (166 VGPRs) without the row prefetch; measured
         // faster than the prefetching 2-wave form (occupancy hides the staging latency better)
@@ -4729,7 +4872,7 @@ static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream
         // layer 1 107.7 -> 99.4 us per 43-source microbenchmark launch, profiles/r03_y)
         if (NK == 4 && lds * 4 <= kLdsPerCu) {
             const int grid = capped((int)std::min<long>(items, 4L * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, 1, true>), dim3(grid), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
             return;
         }
         // at 8 and 12 k-steps the source rows staged by LDS-DMA (no staging VGPRs) make room for 4 waves per SIMD
@@ -4737,16 +4880,16 @@ static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream
         // profiles/r04/mbl1_r04g.txt; host-checked)
         if ((NK == 8 || NK == 12) && lds * 4 <= kLdsPerCu) {
             const int grid = capped((int)std::min<long>(items, 4L * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, 1, true, true>), dim3(grid), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, kRS, true, true>), dim3(grid), dim3(256), lds, st, a);
             return;
         }
         // row results staged in LDS and flushed during the next item's staging (SE; Src7 microbenchmark at 43 sources:
         // layer 0 293.6 -> 264.4 us, layer 1 124.2 -> 115.4, bit-identical)
         const int grid = capped((int)std::min<long>(items, (long)kCorrWaves * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrWaves, NK, false, 1, true>), dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrWaves, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
     } else {
         const int grid = (int)std::min<long>(items, (long)kCorrRunWaves * device_cus());
-        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrRunWaves, NK>), dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrRunWaves, NK, true, kRS>), dim3(grid), dim3(256), lds, st, a);
     }
 }
 #ifdef FPM_EXPERIMENTAL

@@ -366,6 +366,12 @@ int main(int argc, char** argv) {
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no stores");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no partials");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no rowsums");
+        // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4 (again)");
         {
             const size_t lds_db = lds + 16 + (size_t)38 * a.roi_pitch;
             hipFuncSetAttribute((const void*)k_roi_corr<0, true, 2, 12, false, 1, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_db);
@@ -388,6 +394,13 @@ int main(int argc, char** argv) {
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 8, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 SE 3 waves");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE 4 waves");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w no rowsums");
+        // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4 (again)");
         {
             const size_t lds_db = lds + 16 + (size_t)38 * a.roi_pitch;
             hipFuncSetAttribute((const void*)k_roi_corr<0, true, 4, 8, false, 1, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_db);
@@ -395,6 +408,18 @@ int main(int argc, char** argv) {
             timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds_db, 0, a); }, "corrA8 SE DMA DB 4w");
         }
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 8, false, 0>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 RS0 3 waves");
+    }
+    if (TW <= 256) {   // 4 k-steps (the Src7 layer-2 product): register staging, 4 waves per SIMD
+        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc, true);
+        const long items = (long)a.slot_cap * ((TH + 31) / 32);
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w no rowsums");
+        // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4 (again)");
     }
     timeit([&] { launch_roi_eval(a, 0); }, "prod eval");
     {
@@ -414,9 +439,9 @@ int main(int argc, char** argv) {
             hipMemset(a.rowsum, 0xff, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4);
             const long items = (long)a.slot_cap * ((TH + 31) / 32);
             if (TW > 512 && TW <= 768)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
             else if (TW > 256 && TW <= 512)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
             printf("host check of the DMA form\n");
         }
         if (envi("MB_DB_CHECK", 0)) {   // the host check below then checks the double-buffered LDS-DMA form

@@ -125,7 +125,7 @@ struct RoiArgs {
     uint8_t* roi;            // [slot] sampled ROI, tile-major: 32 x 32 tiles of 1 KB, row of tiles by row
     int32_t roi_pitch;       // LDS row pitch of staged ROI rows (k_roi_corr)
     size_t roi_stride;
-    int32_t nparts;          // k_roi_fused: runs of bands per ROI (work unit = (ROI, run of bands))
+    int32_t nparts;          // the fused experiment only (scripts/roi_fused.hip): runs of bands per ROI
     uint32_t* rowsum;        // [slot][th][49] exact int32 per-row dot products
     uint32_t* wsum;          // [slot][nchunk][49] window-sum partials of I
     uint64_t* wsq;           // [slot][nchunk][49] window-sum partials of I^2
@@ -257,12 +257,6 @@ void launch_roi_tables(const RoiArgs& a, hipStream_t st);
 void launch_roi_warp(const RoiArgs& a, hipStream_t st);
 void launch_roi_corr(const RoiArgs& a, hipStream_t st);
 void launch_roi_eval(const RoiArgs& a, hipStream_t st);
-#ifdef FPM_EXPERIMENTAL   // measurement-only fused K6+K7 (scripts/fused_bench.hip; never in libfpm_hip.so)
-bool launch_roi_corr16(const RoiArgs& a, hipStream_t st);   // k_roi_corr16 (scripts/corr16_bench.hip)
-bool roi_fused_fits(int tw);           // the fused sampling + correlation kernel applies (templates <= 1024 wide)
-int roi_fused_parts(int th);           // runs of bands per ROI (work units per ROI) of k_roi_fused
-void launch_roi_fused(const RoiArgs& a, hipStream_t st);
-#endif
 bool roi_small_fits(int tw, int th);   // the single-kernel small-template refinement applies
 size_t roi_small_lds(int tw, int th);
 void launch_roi_small(const RoiArgs& a, hipStream_t st);
@@ -288,7 +282,7 @@ int roi_pitch_for(int tw);
 int roi_tab_rows(int th);   // rows of a ROI's X0 / Y0 tables: th + 6 rounded up to a 32-row tile
 size_t roi_tiles_bytes(int tw, int th);
 int roi_tiles_for(int tw, int th);   // 32x32 warp tiles of a (tw+6) x (th+6) ROI
-size_t roi_corr_lds(int roi_pitch, int tw, int rc, bool global_a);
+size_t roi_corr_lds(int roi_pitch, int tw, int rc);
 constexpr int kMmaRows = 16;   // template rows per MFMA correlation chunk (M of v_mfma_i32_16x16x64_i8)
 
 }  // namespace fpm

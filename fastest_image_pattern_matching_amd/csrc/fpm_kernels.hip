@@ -2135,10 +2135,11 @@ __host__ __device__ inline int tmpl_lds_pitch(int tp8) {
     return q * 16;
 }
 
-size_t roi_corr_lds(int roi_pitch, int tw, int /*rc*/, bool ga) {
+// (the 2 * src_rows words are dead layout: they held the rows' totals of the removed RS 0 form and are kept, like the
+// tw / rc parameters, so that the launched LDS size stays what it was; a change that may alter the LDS size drops them)
+size_t roi_corr_lds(int roi_pitch, int /*tw*/, int /*rc*/) {
     constexpr int src_rows = 2 * kMmaRows + 6;
-    const int tp8 = 64 * ((tw + 63) / 64);
-    return (size_t)src_rows * roi_pitch + (ga ? 0 : (size_t)2 * kMmaRows * tmpl_lds_pitch(tp8)) +
+    return (size_t)src_rows * roi_pitch +
            sizeof(uint32_t) * (2 * src_rows + 2 * 7 * src_rows + 2 * kMmaRows + 2 * kMmaRows * 49) + 64;
 }
 
@@ -2631,7 +2632,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             const uint32_t colmask = nvalid >= 4 ? 0xffffffffu : (1u << (8 * nvalid)) - 1u;
             const int xo = ((int)lds_offset_of(FT) - bxa) << kTabFrac, yo = -(by0 << kTabFrac);
             // one output row (4 pixels) at a time: all 16 tap reads issued before any arithmetic (measured: 126.8 ->
-            // 113.1 us per Src7 layer-0 launch at 8 sources with the folded addressing, scripts/warp_exp.hip; rows
+            // 113.1 us per Src7 layer-0 launch at 8 sources with the folded addressing, probe in git history; rows
             // past the tile repeat its last row's coordinates and are not stored)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -2745,7 +2746,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t box_rsrc(const uint8_t* base) 
 //  * PITCH: the footprint's LDS row pitch.  The product's 68 bytes (17 dwords) puts the 8 sampled rows of a wave's
 //    4 x 8-pixel block on distinct banks; at 64 bytes (one b128 store per 16-byte piece instead of 4 b32) rows r and
 //    r + 4 share banks and the tap reads conflict: 465 vs 384 us at layer 0 (43 sources, scripts/roi_microbench.hip,
-//    profiles/r04/mbw_r04f.txt; the round-3 form with per-row staging: 397 us).  STG 1 = the round-3 per-row staging;
+//    profiles/r04/mbw_r04f.txt; the round-3 form with per-row staging: 397 us);
 //  * per task, not per ROI: the lane's table offsets, the column mask and the row masks (the three ROIs share them);
 //  * the interior pixel: the tables' 16-fraction-bit scale (kTabShift) puts the integer tap coordinate in the high
 //    half-word, read by SDWA word selects, and the 16 tap reads and their wait are one asm statement.
@@ -2753,9 +2754,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t box_rsrc(const uint8_t* base) 
 // taps read but not interpolated (XOR-folded), 3 = interior addressing only (no tap reads), 4 = no ROI stores (a
 // never-true store kept), 5 = no interior rows (staging, tables and border tiles only), 6 = as 5 without staging,
 // 7 = as 6 without the table loads, 8 = as 7 without border tiles (descriptor loads and the task loop only)
-// PFT: the next ROI's tables are requested before this ROI's rows are sampled (16 more VGPRs); SLD: descriptors by
-// scalar loads
-template <int WPE, int PITCH = 64, int STG = 0, int ABL = 0, bool PFT = false, bool SLD = false>
+template <int WPE, int PITCH = 64, int ABL = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_roi_warp3(RoiArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t ft_all[4 * ROI_FT + 16];
     constexpr int ftw = PITCH;   // footprint row pitch
@@ -2780,10 +2779,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const uint32_t pitch_v = __builtin_amdgcn_readfirstlane(ftw);   // the LDS pitch as an SDWA operand
     auto stage = [&](int wpr, int fth, const uint8_t* gsrc) {
         if (ABL == 1 || ABL >= 6) return;
-        if (STG == 1) {
-            stage_footprint32<12, PITCH>(FT, wpr, fth, gsrc, P, lane);
-            return;
-        }
         const int n = (fth + 15) >> 4;   // wave-uniform, <= 4
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         u32x4 v[4];
@@ -2812,16 +2807,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         int bx[3], by[3], wp[3], fh[3], fl[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            // the descriptor through the scalar cache (a uniform address in the constant address space: one
-            // s_load_dwordx4, no vector load and no readfirstlane; k_roi_tables wrote it in an earlier launch)
-            int4 d;
-            if (SLD) {
-                typedef int sv4 __attribute__((ext_vector_type(4)));
-                const sv4 q = *(const __attribute__((address_space(4))) sv4*)(size_t)(a.tdesc + (size_t)(3 * cand + j) * a.tdesc_stride + rem);
-                d = make_int4(q.x, q.y, q.z, q.w);
-            } else {
-                d = a.tdesc[(size_t)(3 * cand + j) * a.tdesc_stride + rem];
-            }
+            const int4 d = a.tdesc[(size_t)(3 * cand + j) * a.tdesc_stride + rem];
             bx[j] = __builtin_amdgcn_readfirstlane(d.x);
             by[j] = __builtin_amdgcn_readfirstlane(d.y);
             const int dz = __builtin_amdgcn_readfirstlane(d.z);
@@ -2847,15 +2833,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                        oY = oX + 4u * a.tabh;
         const int nvalid = RW - c0;
         const uint32_t colmask = nvalid >= 4 ? 0xffffffffu : (1u << (8 * max(nvalid, 0))) - 1u;
-        int4 tA, tB, tX, tY, nA, nB, nX, nY;
-        bool nxt_ok = false;   // (PFT) nA .. nY hold the next non-empty ROI's tables
-        auto load_next = [&](int slot_) {
-            const int32_t* tb = a.tab + (size_t)slot_ * tab_stride;
-            nA = ld_at<int4>(tb, oA);
-            nB = ld_at<int4>(tb, oB);
-            nX = ld_at<int4>(tb, oX);
-            nY = ld_at<int4>(tb, oY);
-        };
+        int4 tA, tB, tX, tY;
         auto load_tabs = [&](int slot_) {
             if (ABL >= 7) {
                 tA = tB = tX = tY = make_int4(slot_, 0, 0, 0);
@@ -2886,18 +2864,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 if ((flags & kTileAny) && in_lds) stage(wp[j], fh[j], lvl + (size_t)by0 * P + bxa);
                 wave_sync();
             }
-            if (j > 0 && (flags & kTileAny)) {   // (an empty tile needs no tables)
-                if (PFT && nxt_ok) {
-                    tA = nA; tB = nB; tX = nX; tY = nY;
-                } else {
-                    load_tabs(slot);
-                }
-            }
-            nxt_ok = false;
-            if (PFT && j + 1 < 3 && (fl[j + 1] & kTileAny)) {
-                load_next(slot + 1);
-                nxt_ok = true;
-            }
+            if (j > 0 && (flags & kTileAny)) load_tabs(slot);   // (an empty tile needs no tables)
             const uint32_t adv[4] = {(uint32_t)tA.x, (uint32_t)tA.y, (uint32_t)tA.z, (uint32_t)tA.w};
             const uint32_t bdv[4] = {(uint32_t)tB.x, (uint32_t)tB.y, (uint32_t)tB.z, (uint32_t)tB.w};
             const uint32_t X0r[4] = {(uint32_t)tX.x, (uint32_t)tX.y, (uint32_t)tX.z, (uint32_t)tX.w};
@@ -3201,13 +3168,13 @@ __device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, i
 }
 
 // MODE (profiling ablations in scripts/roi_microbench.hip; the product uses 0): 2 = no MFMA loop, 3 = no staging
-// (slot-major form only), 4 = no window-edge phase, 5 = no row-result stores, 6 = no window partials, 7 = no row sums
-// GA: A operand read from the global i8 slab (no template rows in LDS); WPE: register cap (waves per SIMD);
-// NK > 0: register-A form (A fragments of nk <= NK k-steps held per wave, band-major item runs; needs GA)
+// (slot-major form only), 5 = no row-result stores, 6 = no window partials, 7 = no row sums (4, no window-edge phase,
+// went with the RS 0 form, the only one with such a phase)
+// The A operand is read from the global i8 slab (no template rows in LDS); WPE: register cap (waves per SIMD);
+// NK > 0: register-A form (A fragments of nk <= NK k-steps held per wave, band-major item runs)
 // PFR (register-A form): prefetch the next item's rows (false: load this item's rows at its start, fewer VGPRs)
-// RS: 1 = row statistics in one phase (a quad of lanes per row: its I / I^2 totals reduced by DPP, then the edge pixels
-// of each window subtracted by the same lanes; the window partials split over lane pairs), 0 = the earlier form (row
-// totals by LDS atomics, a separate edge phase, one thread per partial), 2 = as 1 with the partials before the GEMM,
+// RS: 1 (the slot-major form) = row statistics in one phase (a quad of lanes per row: its I / I^2 totals reduced by DPP,
+// then the edge pixels of each window subtracted by the same lanes; the window partials split over lane pairs),
 // 3 (the product up to 8 k-steps) = the full-row sums on the matrix cores (tile_row_sums: the owner wave of each N tile,
 // waves 0 / 1 / 3, reads its tile's dx = 0 B fragments as 16-byte LDS reads and issues 2 MFMAs per k-step, then
 // subtracts the window edges of its 16 rows itself: the same two barriers as 1, without its strided walk of 48 dwords
@@ -3218,8 +3185,6 @@ __device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, i
 // item's staging (after the loads of its rows are issued, so waiting for those loads does not wait for these stores)
 // DMA (register-A form, no row prefetch): the item's ROI rows go global -> LDS by LDS-DMA (one global_load_lds_dwordx4
 // per row and wave, the scratch already flipped): no staging registers and no VALU per staged row
-// DB (with DMA): two row buffers; the next item's rows are issued into the other buffer once this item's are in LDS,
-// so an item waits for rows requested one item earlier (the LDS holds a second kBandSrc x SBp buffer after the rest)
 // wave priority of the GEMM phase (s_setprio): 1 = the banded GEMM and its row-result epilogue at priority 1 (the
 // product: the item's matrix work is not held behind the co-resident waves' staging and statistics VALU; Src7 kernel
 // pass 196.5 -> 185.7 us per k_roi_corr launch averaged over the layers, profiles/r06_prio/), 2 = the GEMM alone,
@@ -3227,28 +3192,22 @@ __device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, i
 #ifndef FPM_CORR_PRIO
 #define FPM_CORR_PRIO 1
 #endif
-template <int MODE, bool GA, int WPE, int NK = 0, bool PFR = true, int RS = 1, bool SE = false, bool DMA = false,
-          bool DB = false>
+template <int MODE, int WPE, int NK = 0, bool PFR = true, int RS = 1, bool SE = false, bool DMA = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_roi_corr(RoiArgs a) {
     static_assert(!DMA || (NK > 0 && !PFR), "LDS-DMA staging replaces the register staging of the register-A form");
-    static_assert(!DB || DMA, "the double buffer is filled by LDS-DMA");
-    static_assert(NK == 0 || (GA && MODE != 3), "the register-A form stages no template rows");
+    static_assert(NK == 0 || MODE != 3, "the staging ablation belongs to the slot-major form");
+    static_assert(RS == 1 || RS == 3 || RS == 4, "the row statistics' forms");
     static_assert(!SE || NK > 0, "the staged epilogue is flushed in the register-A form's staging phase");
     static_assert(RS < 3 || NK > 0, "the matrix-core row sums read the register-A form's staged rows, every byte defined");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tw = a.tw, th = a.th, RW = tw + 6;
     const int SBp = a.roi_pitch;
-    const int TBp = tmpl_lds_pitch(a.tp8);
-    uint8_t* const SB0 = smem;                                 // kBandSrc rows x SBp, bytes ^ 0x80
-    uint8_t* SB = SB0;
-    uint8_t* TB = SB + (size_t)kBandSrc * SBp;                 // kBandRows template rows (i8) x TBp (!GA)
-    uint32_t* rall = (uint32_t*)(TB + (GA ? 0 : (size_t)kBandRows * TBp)); // full-row sums of I
-    uint32_t* rallq = rall + kBandSrc;                         // full-row sums of I^2
-    uint32_t* wi = rallq + kBandSrc;                           // [row][dx] window sums of I
+    uint8_t* const SB = smem;                                  // kBandSrc rows x SBp, bytes ^ 0x80
+    // (2 kBandSrc words after the rows stay free: roi_corr_lds's layout, once the rows' totals)
+    uint32_t* wi = (uint32_t*)(SB + (size_t)kBandSrc * SBp) + 2 * kBandSrc;   // [row][dx] window sums of I
     uint32_t* wq = wi + kBandSrc * 7;                          // [row][dx] window sums of I^2
     uint32_t* lts = wq + kBandSrc * 7;                         // the band's template-row sums (16-byte aligned)
     uint32_t* rsb = lts + 2 * kMmaRows;                        // (SE) the band's [rb][49] row results (16-byte aligned)
-    uint8_t* const SB1 = (uint8_t*)(((uintptr_t)(rsb + 2 * kMmaRows * 49) + 64 + 15) & ~(uintptr_t)15);   // (DB)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int nband = (th + kBandRows - 1) / kBandRows;
     const int rois = roi_count(a), items = rois * nband;
@@ -3300,11 +3259,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         // chunks past the ROI's tiles hold flipped zeros, written once (the DMA never overwrites them; the item loop's
         // first barriers order these stores before the first read)
         const int nfill = q4 - 2 * txn;
-        for (int b = 0; b < (DB ? 2 : 1); ++b)
-            for (int i = tid; i < kBandSrc * nfill; i += 256) {
-                const int r = i / nfill, c = 2 * txn + (i - r * nfill);
-                *(uint4*)((b ? SB1 : SB0) + (size_t)r * SBp + 16 * c) = make_uint4(kRoiFlip, kRoiFlip, kRoiFlip, kRoiFlip);
-            }
+        for (int i = tid; i < kBandSrc * nfill; i += 256) {
+            const int r = i / nfill, c = 2 * txn + (i - r * nfill);
+            *(uint4*)(SB + (size_t)r * SBp + 16 * c) = make_uint4(kRoiFlip, kRoiFlip, kRoiFlip, kRoiFlip);
+        }
     }
     // (SE) the previous item's row results: LDS -> its [rb][49] range of the ROI's series, 16-byte stores (the range
     // starts 16-byte aligned: slot stride and T0 * 49 are multiples of 4 words), the < 4-word tail by single words
@@ -3343,21 +3301,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         int slot, band;
         if (NK > 0) { band = item / rois; slot = item - band * rois; }
         else { slot = item / nband; band = item - slot * nband; }
-        SB = DB && ((item - it_lo) & 1) ? SB1 : SB0;
         const int T0 = band * kBandRows, rb = min(kBandRows, th - T0), nsrc = rb + 6;
-        __syncthreads();   // previous item done with SB / rall / wi
-        if (RS == 0 && tid < kBandSrc) { rall[tid] = 0; rallq[tid] = 0; }
+        __syncthreads();   // previous item done with SB / wi
         if (NK > 0) {
             // this item's rows (loaded during the previous item) ^ 0x80 into LDS; this wave's A fragments when the
             // band changes (workgroup-uniform); then the next item's row loads
             const bool in_roi = lane < 2 * txn;
-            if (DB) {
-                // this item's rows were issued during the previous item (the first item's now); wait, then start the
-                // previous item's row-result stores
-                if (item == it_lo) dma_rows(item, SB);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                flush();
-            } else if (DMA) {
+            if (DMA) {
                 dma_rows(item, SB);
                 flush();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3408,11 +3358,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
         __syncthreads();
-        if (DB && item + 1 < it_hi) dma_rows(item + 1, SB == SB0 ? SB1 : SB0);   // every wave is past the other buffer
         if (RS >= 3 && MODE != 7 && wv != 2 && kMmaRows * nt < nsrc) {   // wave-uniform
             // the owner waves of the three N tiles (wave 2 shares N tile 1 with wave 1): the tile's full-row sums, then
             // the window edges of its 16 rows: every lane (n, g) holds row n's sum of I and fetches its sum of I^2 from
-            // the diagonal's lane (n, n >> 2); lane (n, g) then takes dx = g and g + 4 (window_edges).  No rall / rallq.
+            // the diagonal's lane (n, n >> 2); lane (n, g) then takes dx = g and g + 4 (window_edges).
             // (the lane index opaque: what derives from it is recomputed per item, not kept in registers across the
             // item loop and the GEMM)
             int ln = lane;
@@ -3448,7 +3397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 }
             }
         }
-        if ((RS == 1 || RS == 2) && MODE != 7 && tid < 4 * nsrc) {
+        if (RS == 1 && MODE != 7 && tid < 4 * nsrc) {
             // row r's statistics by the quad of lanes 4r .. 4r + 3 (whole quads: DPP within the quad): exact full-row
             // sums of I and I^2 over the row's words (pixels past RW are zero), then each lane subtracts the window's
             // edge pixels for its dx (qq and qq + 4): window [dx, dx + tw) = row minus bytes [0, dx) and [dx + tw, RW)
@@ -3505,44 +3454,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 }
             }
         }
-        if (RS == 0 && MODE != 7 && tid < 4 * nsrc) {   // exact full-row sums of I and I^2: thread (row, quarter of the row's words)
-            const int r = tid >> 2, qq = tid & 3;
-            const int per = (nwr + 3) >> 2, k0 = qq * per, k1 = min(nwr, k0 + per);
-            const uint32_t* row = (const uint32_t*)(SB + (size_t)r * SBp);
-            uint32_t s1 = 0, s2 = 0;
-            int k = k0;
-            for (; k + 8 <= k1; k += 8) {
-                uint32_t x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = row[k + u] ^ 0x80808080u;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    s1 = __builtin_amdgcn_udot4(x[u], 0x01010101u, s1, false);
-                    s2 = __builtin_amdgcn_udot4(x[u], x[u], s2, false);
-                }
-            }
-            for (; k < k1; ++k) {
-                const uint32_t x = row[k] ^ 0x80808080u;
-                s1 = __builtin_amdgcn_udot4(x, 0x01010101u, s1, false);
-                s2 = __builtin_amdgcn_udot4(x, x, s2, false);
-            }
-            atomicAdd(&rall[r], s1);
-            atomicAdd(&rallq[r], s2);
-        }
-        if (!GA) {   // template rows T0 .. T0 + 16*ceil(rb/16) - 1 of the i8 slab
-            const int trows = (rb + kMmaRows - 1) / kMmaRows * kMmaRows;
-            stage_block16(TB, TBp, (const uint8_t*)a.tmpl8 + (size_t)T0 * a.tp8, a.tp8, trows, a.tp8 >> 4, tid, 256);
-        }
-        if (RS == 0) __syncthreads();
-        for (int i = tid; RS == 0 && MODE != 4 && i < nsrc * 7; i += 256) {   // window [dx, dx + tw): full row minus <= 6 edge pixels
-            const int r = i / 7, dx = i - r * 7;
-            const uint8_t* sbr = SB + (size_t)r * SBp;
-            uint32_t q1 = rall[r], q2 = rallq[r];
-            for (int c = 0; c < dx; ++c) { const uint32_t v = sbr[c] ^ 0x80u; q1 -= v; q2 -= v * v; }
-            for (int c = dx + tw; c < RW; ++c) { const uint32_t v = sbr[c] ^ 0x80u; q1 -= v; q2 -= v * v; }
-            wi[i] = q1;
-            wq[i] = q2;
-        }
         __syncthreads();
         // per-16-row-chunk partials of the window sums, 8 rows per lane (lane pairs, combined by DPP within the quad;
         // the 8 rows' LDS reads all in flight)
@@ -3579,7 +3490,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 a.wsq[wo] = s2;
             }
         };
-        if (RS == 2) partials();   // before the banded GEMM (the same wave's MFMA work follows)
         const bool active = kMmaRows * mt < rb && kMmaRows * nt < nsrc;   // wave-uniform
         if (FPM_CORR_PRIO == 1) __builtin_amdgcn_s_setprio(1);   // the GEMM and its epilogue
         if (MODE != 2 && active) {
@@ -3590,10 +3500,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             if (FPM_CORR_PRIO == 2) __builtin_amdgcn_s_setprio(1);
             if (NK > 0)
                 band_mfma_regs<NA>(Areg, bp, a.nk, acc);
-            else if (GA)
-                band_mfma_ga(a.tmpl8 + (size_t)(T0 + kMmaRows * mt + n) * a.tp8 + 16 * g, bp, a.nk, acc);
             else
-                band_mfma(TB + (size_t)(kMmaRows * mt + n) * TBp + 16 * g, bp, a.nk, acc);
+                band_mfma_ga(a.tmpl8 + (size_t)(T0 + kMmaRows * mt + n) * a.tp8 + 16 * g, bp, a.nk, acc);
             if (FPM_CORR_PRIO == 2) __builtin_amdgcn_s_setprio(0);
             // D_dx: col = lane & 15 -> source row 16*nt + n, row = 4*(lane >> 4) + r -> template row 16*mt + 4g + r
             uint32_t* rs_out = a.rowsum + (((size_t)th * 49 + 3) & ~(size_t)3) * slot + (size_t)T0 * 49;   // uniform
@@ -3630,23 +3538,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
         if (FPM_CORR_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (RS == 1 || RS >= 3) partials();
-        if (RS == 0 && MODE != 6 && tid < 2 * 49) {   // per-16-row-chunk partials of the window sums
-            const int h = tid / 49, k = tid - h * 49;
-            const int chunk = (T0 >> 4) + h;
-            const int tlo = kMmaRows * h, thi = min(tlo + kMmaRows, rb);
-            if (chunk < a.nchunk && tlo < thi) {
-                const int pdy = k / 7, ddx = k - pdy * 7;
-                uint32_t s1 = 0;
-                uint64_t s2 = 0;
-                for (int t = tlo; t < thi; ++t) {
-                    s1 += wi[(t + pdy) * 7 + ddx];
-                    s2 += wq[(t + pdy) * 7 + ddx];
-                }
-                a.wsum[((size_t)slot * a.nchunk + chunk) * 49 + k] = s1;
-                a.wsq[((size_t)slot * a.nchunk + chunk) * 49 + k] = s2;
-            }
-        }
+        partials();
         if (SE) { pv_slot = slot; pv_T0 = T0; pv_rb = rb; }
     }
     if (SE && pv_slot >= 0) {   // the last item's row results
@@ -3654,462 +3546,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         flush();
     }
 }
-
-#ifdef FPM_EXPERIMENTAL   // measured slower (bench 33.02k vs 34.10k searches/s): scripts/corr16_bench.hip only
-// ---- K7, round 5: the register-A / LDS-DMA correlation with items of ONE 16-row M tile (k_roi_corr's band is two).
-// A k_roi_corr item waits for its 38 ROI rows (one LDS-DMA round trip) and two barriers before its matrix work, and
-// its 40 KB of LDS allow 4 items in flight per CU.  Here an item is (ROI, 16 template rows = one window-sum chunk):
-// 22 ROI rows (18 KB), a 2-wave workgroup (wave w takes the N tile of ROI rows 16 w .. 16 w + 15, both waves the
-// band's A fragments), about 22 KB of LDS, so 7 items are in flight per CU at the same waves per SIMD.  The price is
-// 22 / 16 staged rows per template row instead of 38 / 32, and the same banded MFMA count (two N tiles per M tile).
-// Outputs are k_roi_corr's exactly: the row dot products [t][49] (exact u32, through LDS as 16-byte runs during the
-// next item, SE), and the window-sum partial of the item's chunk (one 16-row chunk per item).
-constexpr int kB16Rows = kMmaRows, kB16Src = kB16Rows + 6;
-__host__ __device__ inline size_t roi_corr16_lds(int roi_pitch) {
-    return (size_t)kB16Src * roi_pitch + sizeof(uint32_t) * (2 * 7 * kB16Src + kB16Rows + kB16Rows * 49) + 64;
-}
-template <int NK, int WPE>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE))) void k_roi_corr16(RoiArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int NT = 128;
-    const int tw = a.tw, th = a.th, RW = tw + 6;
-    const int SBp = a.roi_pitch;
-    uint8_t* const SB = smem;                                   // kB16Src rows x SBp, bytes ^ 0x80
-    uint32_t* wi = (uint32_t*)(SB + (size_t)kB16Src * SBp);     // [row][dx] window sums of I
-    uint32_t* wq = wi + kB16Src * 7;                            // [row][dx] window sums of I^2
-    uint32_t* lts = wq + kB16Src * 7;                           // the band's template-row sums
-    uint32_t* rsb = lts + kB16Rows;                             // the band's [t][49] row results (16-byte aligned)
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nband = (th + kB16Rows - 1) / kB16Rows;
-    const int rois = roi_count(a), items = rois * nband;
-    const int nwr = (RW + 3) >> 2;
-    const int g = lane >> 4, n = lane & 15;
-    const int txn = (RW + ROI_T - 1) / ROI_T;
-    const XcdSplit xs = xcd_split(items);
-    const int64_t span = xs.hi - xs.lo;
-    const int it_lo = xs.lo + (int)(span * xs.k / xs.nk), it_hi = xs.lo + (int)(span * (xs.k + 1) / xs.nk);
-    fpm_v4i Areg[NK];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) Areg[k] = fpm_v4i{0, 0, 0, 0};
-    int a_band = -1;
-    int pv_slot = -1, pv_T0 = 0, pv_rb = 0;
-    auto flush = [&]() {   // the previous item's row results: LDS -> its [rb][49] range of the ROI's series
-        if (pv_slot < 0) return;
-        uint32_t* dst = a.rowsum + (((size_t)th * 49 + 3) & ~(size_t)3) * pv_slot + (size_t)pv_T0 * 49;
-        const int nw = pv_rb * 49, n16 = nw >> 2;
-        for (int i = tid; i < n16; i += NT) *(uint4*)(dst + 4 * i) = *(const uint4*)(rsb + 4 * i);
-        if (tid < (nw & 3)) dst[4 * n16 + tid] = rsb[4 * n16 + tid];
-    };
-    // item it's ROI rows wv + 2 i -> SB by LDS-DMA (one global_load_lds_dwordx4 per row and wave; lanes past the ROI
-    // width idle: those LDS chunks meet the template's zero padding only)
-    auto dma_rows = [&](int it) {
-        const int bd = it / rois, sl = it - bd * rois;
-        const int T0n = bd * kB16Rows, nsn = min(kB16Rows, th - T0n) + 6;
-        const uint8_t* rsrc = a.roi + (size_t)sl * a.roi_stride;
-        const uint32_t lane_off = ((uint32_t)(lane >> 1) << 10) + 16u * (uint32_t)(lane & 1);
-        const int wvu = __builtin_amdgcn_readfirstlane(wv);
-        const bool in_roi = lane < 2 * txn;
-#pragma unroll
-        for (int i = 0; i < (kB16Src + 1) / 2; ++i) {
-            const int r = wvu + 2 * i;
-            if (r < nsn && in_roi) {
-                const int R = T0n + r;
-                const uint8_t* gp = rsrc + ((size_t)((R >> 5) * txn) << 10) + (R & 31) * ROI_T + lane_off;
-                const uint32_t ldsa = __builtin_amdgcn_readfirstlane(lds_offset_of(SB + (size_t)r * SBp));
-                uint32_t keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                             "s_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(gp), "s"(ldsa) : "memory");
-            }
-        }
-    };
-    for (int item = it_lo; item < it_hi; ++item) {
-        const int band = item / rois, slot = item - band * rois;
-        const int T0 = band * kB16Rows, rb = min(kB16Rows, th - T0), nsrc = rb + 6;
-        __syncthreads();   // the previous item is done with SB / wi / rsb
-        dma_rows(item);
-        flush();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (band != a_band) {   // this band's A fragments (both waves: the item's one M tile) and template-row sums
-            a_band = band;
-            if (tid < kB16Rows) lts[tid] = tid < rb ? (uint32_t)a.tsum[T0 + tid] : 0u;
-            const int8_t* ap = a.tmpl8 + (size_t)(T0 + n) * a.tp8 + 16 * g;
-#pragma unroll
-            for (int k = 0; k < NK; ++k)
-                if (k < a.nk) Areg[k] = *(const fpm_v4i*)(ap + 64 * k);
-        }
-        __syncthreads();
-        if (tid < 4 * nsrc) {
-            // row r's window sums by the quad of lanes 4r .. 4r + 3 (k_roi_corr's RS 1 form): full-row sums of I and I^2
-            // reduced by DPP within the quad, each lane subtracting the edge pixels of its windows dx = q, q + 4
-            const int r = tid >> 2, qq = tid & 3;
-            const int per = (nwr + 3) >> 2, k0 = qq * per, k1 = min(nwr, k0 + per);
-            const uint32_t* row = (const uint32_t*)(SB + (size_t)r * SBp);
-            uint32_t s1 = 0, s2 = 0;
-            int k = k0;
-            for (; k + 8 <= k1; k += 8) {
-                uint32_t x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = row[k + u] ^ 0x80808080u;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    s1 = __builtin_amdgcn_udot4(x[u], 0x01010101u, s1, false);
-                    s2 = __builtin_amdgcn_udot4(x[u], x[u], s2, false);
-                }
-            }
-            for (; k < k1; ++k) {
-                const uint32_t x = row[k] ^ 0x80808080u;
-                s1 = __builtin_amdgcn_udot4(x, 0x01010101u, s1, false);
-                s2 = __builtin_amdgcn_udot4(x, x, s2, false);
-            }
-            const uint32_t l0 = row[0] ^ 0x80808080u, l1 = row[1] ^ 0x80808080u;
-            const int wr = tw >> 2;
-            const uint32_t x0 = row[wr], x1 = row[wr + 1], x2 = row[wr + 2];
-            const uint32_t e0 = __builtin_amdgcn_alignbyte(x1, x0, (uint32_t)tw) ^ 0x80808080u;
-            const uint32_t e1 = __builtin_amdgcn_alignbyte(x2, x1, (uint32_t)tw) ^ 0x80808080u;
-            s1 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-            s2 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s2, 0xB1, 0xF, 0xF, false);
-            s1 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-            s2 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s2, 0x4E, 0xF, 0xF, false);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int dx = qq + 4 * h;
-                if (dx < 7) {
-                    const uint32_t ml0 = dx >= 4 ? 0xffffffffu : (1u << (8 * dx)) - 1u;
-                    const uint32_t ml1 = dx <= 4 ? 0u : (1u << (8 * (dx - 4))) - 1u;
-                    const uint32_t mr0 = dx >= 4 ? 0u : ~((1u << (8 * dx)) - 1u);
-                    const uint32_t mr1 = dx <= 4 ? 0xffffu : dx == 5 ? 0xff00u : 0u;
-                    const uint32_t a0 = l0 & ml0, a1 = l1 & ml1, b0 = e0 & mr0, b1 = e1 & mr1;
-                    uint32_t q1 = __builtin_amdgcn_udot4(a0, 0x01010101u, 0u, false);
-                    q1 = __builtin_amdgcn_udot4(a1, 0x01010101u, q1, false);
-                    q1 = __builtin_amdgcn_udot4(b0, 0x01010101u, q1, false);
-                    q1 = __builtin_amdgcn_udot4(b1, 0x01010101u, q1, false);
-                    uint32_t q2 = __builtin_amdgcn_udot4(a0, a0, 0u, false);
-                    q2 = __builtin_amdgcn_udot4(a1, a1, q2, false);
-                    q2 = __builtin_amdgcn_udot4(b0, b0, q2, false);
-                    q2 = __builtin_amdgcn_udot4(b1, b1, q2, false);
-                    wi[r * 7 + dx] = s1 - q1;
-                    wq[r * 7 + dx] = s2 - q2;
-                }
-            }
-        }
-        __syncthreads();
-        if (kMmaRows * wv < nsrc) {   // wave-uniform: wave 1's N tile exists
-            int sr = kMmaRows * wv + n;
-            if (sr >= nsrc) sr = 0;   // column outside the band: computed, never stored
-            const uint8_t* bp = SB + (size_t)sr * SBp + 16 * g;
-            fpm_v4i acc[7];
-            band_mfma_regs<NK>(Areg, bp, a.nk, acc);
-            const uint32_t kFix = 16384u * (uint32_t)tw;
-            int t0 = 4 * g;
-            asm volatile("" : "+v"(t0));
-            const int s_ = kMmaRows * wv + n;
-            const uint4 ts4 = *(const uint4*)(lts + t0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = t0 + r, dy = s_ - t;
-                if (t < rb && s_ < nsrc && dy >= 0 && dy < 7) {
-                    const uint32_t ts = r == 0 ? ts4.x : r == 1 ? ts4.y : r == 2 ? ts4.z : ts4.w;
-                    const uint32_t o = (uint32_t)(t * 49 + dy * 7);
-#pragma unroll
-                    for (int d = 0; d < 7; ++d) rsb[o + d] = (uint32_t)acc[d][r] + 128u * (wi[s_ * 7 + d] + ts) - kFix;
-                }
-            }
-        }
-        // the item's chunk partial of the window sums (positions k by lane pairs, 8 rows each, combined by DPP)
-        if (tid < 2 * 49) {
-            const int k = tid >> 1, half = tid & 1;
-            const int chunk = T0 >> 4;
-            const int pdy = k / 7, ddx = k - pdy * 7;
-            const int t0 = 8 * half, n8 = min(8, rb - t0);
-            uint32_t s1 = 0, x[8], y[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = (t0 + u + pdy) * 7 + ddx;
-                x[u] = u < n8 ? wi[i] : 0u;
-                y[u] = u < n8 ? wq[i] : 0u;
-            }
-            uint64_t s2 = 0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s1 += x[u]; s2 += y[u]; }
-            s1 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xF, 0xF, false);
-            const uint32_t lo = (uint32_t)s2, hi = (uint32_t)(s2 >> 32);
-            s2 += (uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)lo, 0xB1, 0xF, 0xF, false) |
-                  ((uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)hi, 0xB1, 0xF, 0xF, false) << 32);
-            if (half == 0 && chunk < a.nchunk) {
-                uint32_t kk = (uint32_t)k;
-                asm volatile("" : "+v"(kk));
-                const uint32_t wo = ((uint32_t)slot * (uint32_t)a.nchunk + (uint32_t)chunk) * 49u + kk;
-                a.wsum[wo] = s1;
-                a.wsq[wo] = s2;
-            }
-        }
-        pv_slot = slot; pv_T0 = T0; pv_rb = rb;
-    }
-    if (pv_slot >= 0) {   // the last item's row results
-        __syncthreads();
-        flush();
-    }
-}
-
-#endif   // FPM_EXPERIMENTAL (k_roi_corr16)
-
-#ifdef FPM_EXPERIMENTAL   // measurement-only kernel (scripts/fused_bench.hip); the product Makefile never defines it
-// ---- K6+K7 fused (templates too large for k_roi_small): the ROI never leaves the CU.  A work unit is one ROI and
-// one run of consecutive 32-row template bands; a workgroup walks its run band by band:
-//   the band's new ROI rows are sampled straight into an LDS ring of kBandSrc rows (32x32 tiles: the tile's
-//   source footprint staged in wave-private LDS, the bilinear taps gathered from it — K6b's sampler, with the
-//   warp tables computed in LDS instead of read from HBM), their exact row sums of I and I^2 reduced on the fly;
-//   the 6 rows a band shares with the next stay in the ring (ring slot = ROI row mod kBandSrc);
-//   then K7's banded GEMM on the matrix cores (A fragments of the band in registers, loaded during the sampling)
-//   and its epilogue: the exact per-row dot products and the per-16-row window-sum partials, exactly k_roi_corr's
-//   outputs, so K8 (k_roi_eval) folds them unchanged.
-// Only the first band of a run samples its 6 leading rows again (runs of ~3.5 bands: ~4.5 % extra sampling), the
-// ~0.4 MB sampled ROI of a layer-0 Src7 candidate is neither written to nor re-read from HBM, and the per-ROI warp
-// tables / tile descriptors need no kernel of their own.
-constexpr int kFuseFt = 3072;                  // per-wave footprint: any <= 32x32 interior tile box is <= 56 x 49 B
-constexpr int kFuseFtStride = kFuseFt + 64;    // + over-read slack
-constexpr int kFuseWgs = 256 * 3;              // 3 workgroups per CU (LDS ~52 KB, <= 168 VGPRs at layer 0)
-
-struct FuseLayout {
-    int sbp, ft, tab, rt, sums, mat, total;
-};
-__host__ __device__ inline FuseLayout fuse_layout(int tw) {
-    FuseLayout L;
-    const int txn = (tw + 6 + ROI_T - 1) / ROI_T;
-    L.sbp = roi_pitch_calc(tw);
-    L.ft = kBandSrc * L.sbp;                   // ring of kBandSrc ROI rows (i8: I ^ 0x80), pitch sbp
-    L.tab = L.ft + 4 * kFuseFtStride;          // ad[32 txn], bd[32 txn] (int32)
-    L.rt = L.tab + 8 * ROI_T * txn;            // x0[32], y0[32] of the row block being sampled
-    L.sums = L.rt + 8 * ROI_T;                 // rall, rallq [kBandSrc], wi, wq [kBandSrc][7] (ring slots)
-    L.mat = L.sums + 4 * 16 * kBandSrc;        // the ROI's affine map (6 doubles)
-    L.total = L.mat + 8 * 6;
-    return L;
-}
-bool roi_fused_fits(int tw) { return (tw + 63) / 64 <= 16 && 3 * (size_t)fuse_layout(tw).total <= 160 * 1024; }
-int roi_fused_parts(int th) {
-    const int nband = (th + kBandRows - 1) / kBandRows;
-    const int p = (2 * nband + 3) / 7;         // runs of ~3.5 bands
-    return p < 1 ? 1 : p;
-}
-
-// sum over each aligned group of 8 lanes, in every lane of the group: quad_perm [1,0,3,2], [2,3,0,1], then
-// row_half_mirror (lane i <-> 7 - i of the 8) — three DPP adds, no LDS traffic
-__device__ __forceinline__ uint32_t sum8_dpp(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, false);
-    return v;
-}
-
-template <int NK>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_roi_fused(RoiArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int tw = a.tw, th = a.th, RW = tw + 6, W = a.W, H = a.H;
-    const FuseLayout LY = fuse_layout(tw);
-    const int SBp = LY.sbp;
-    const int txn = (RW + ROI_T - 1) / ROI_T;
-    uint8_t* SB = smem;
-    int32_t* lad = (int32_t*)(smem + LY.tab);
-    int32_t* lbd = lad + ROI_T * txn;
-    int32_t* lx0 = (int32_t*)(smem + LY.rt);
-    int32_t* ly0 = lx0 + ROI_T;
-    uint32_t* rall = (uint32_t*)(smem + LY.sums);
-    uint32_t* rallq = rall + kBandSrc;
-    uint32_t* wi = rallq + kBandSrc;
-    uint32_t* wq = wi + kBandSrc * 7;
-    double* lM = (double*)(smem + LY.mat);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint8_t* FT = smem + LY.ft + wv * kFuseFtStride;
-    const int nband = (th + kBandRows - 1) / kBandRows;
-    const int nparts = a.nparts;
-    const int units = roi_count(a) * nparts;
-    const int g = lane >> 4, n = lane & 15;
-    const int mt = wv & 1, nt = mt + (wv >> 1);   // this wave's (M, N) tile pair (k_roi_corr)
-    const int lr = lane >> 3, lg = lane & 7;      // sampling: rows lr + 8i, columns 4 lg .. 4 lg + 3 of a tile
-    const uint32_t kFix = 16384u * (uint32_t)tw;
-    auto ring = [](int r) { return r % kBandSrc; };
-    const XcdSplit xs = xcd_split(units);         // an XCD group takes a contiguous run of units (an ROI's runs
-                                                  // and the candidate's other angles share source lines in L2)
-    for (int u = xs.lo + xs.k; u < xs.hi; u += xs.nk) {
-        const int slot = u / nparts, part = u - slot * nparts;
-        const int b0 = part * nband / nparts, b1 = (part + 1) * nband / nparts;
-        int id, jj;
-        roi_slot(a, slot, id, jj);
-        const uint8_t* lvl = a.level + (size_t)(id / a.per_source) * a.level_stride;
-        __syncthreads();   // the previous unit is done with every LDS array
-        {
-            double M[6];
-            const CandState st = a.state[id];
-            const AngleNode nd = a.nodes[st.node * a.n3 + jj];
-            roi_matrix(W, H, f2(st.lt.x * 2, st.lt.y * 2), nd.c, nd.s, M);   // getRotatedROI :1074-1090
-            for (int x = tid; x < ROI_T * txn; x += 256) {   // warpAffine's adelta / bdelta (k_roi_tables)
-                lad[x] = rint_i(M[0] * x * kAbScale);
-                lbd[x] = rint_i(M[3] * x * kAbScale);
-            }
-            if (tid < 6) lM[tid] = M[tid];   // the row terms are computed per row block (below)
-        }
-        uint32_t* rs_out = a.rowsum + (((size_t)th * 49 + 3) & ~(size_t)3) * slot;
-        for (int b = b0; b < b1; ++b) {
-            const int T0 = b * kBandRows, rb = min(kBandRows, th - T0), nsrc = rb + 6;
-            const int rlo = b == b0 ? 0 : 6;       // ring rows T0 .. T0 + 5 carried from the previous band
-            // new rows T0 + rlo .. T0 + nsrc - 1, in row blocks of <= 32 (one tile row each)
-            for (int rb0 = rlo; rb0 < nsrc; rb0 += ROI_T) {
-                const int nr = min(ROI_T, nsrc - rb0), R0 = T0 + rb0;   // ROI rows R0 .. R0 + nr - 1
-                __syncthreads();   // the previous block's sampling is done with x0 / y0; (first block) the previous
-                                   // band's MFMA is done with the ring rows and window sums overwritten here
-                if (tid < nr) {
-                    const int y = R0 + tid;
-                    lx0[tid] = rint_i((lM[1] * y + lM[2]) * kAbScale) + kRoundDelta;
-                    ly0[tid] = rint_i((lM[4] * y + lM[5]) * kAbScale) + kRoundDelta;
-                    rall[ring(y)] = 0u;
-                    rallq[ring(y)] = 0u;
-                }
-                __syncthreads();
-                for (int tx = wv; tx < txn; tx += 4) {
-                    const int cx0 = tx * ROI_T, cx1 = min(cx0 + ROI_T, RW) - 1;
-                    // the tile's source footprint box from its corner samples (+-1 px, see k_roi_tables)
-                    int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int c = (k & 1) ? cx1 : cx0, r = (k & 2) ? nr - 1 : 0;
-                        const int X = (lx0[r] + lad[c]) >> (kAbBits - kInterBits);
-                        const int Y = (ly0[r] + lbd[c]) >> (kAbBits - kInterBits);
-                        bx0 = min(bx0, X >> kInterBits); bx1 = max(bx1, X >> kInterBits);
-                        by0 = min(by0, Y >> kInterBits); by1 = max(by1, Y >> kInterBits);
-                    }
-                    const bool interior = bx0 - 1 >= 0 && bx1 + 1 <= W - 2 && by0 - 1 >= 0 && by1 + 1 <= H - 2;
-                    bx0 = max(bx0 - 1, 0); by0 = max(by0 - 1, 0);
-                    bx1 = min(bx1 + 2, W - 1); by1 = min(by1 + 2, H - 1);
-                    const bool any = bx0 <= bx1 && by0 <= by1;
-                    const int bxa = bx0 & ~3;
-                    int ftw = any ? ((bx1 - bxa + 4) & ~3) : 0;
-                    if (((ftw >> 2) & 1) == 0) ftw += 4;    // odd dword pitch: spread gather banks
-                    const int fth = any ? by1 - by0 + 1 : 0;
-                    const int wpr = ftw >> 2;
-                    const bool in_lds = wpr <= 16 && ftw * fth <= kFuseFt;
-                    wave_sync();   // the previous tile's gathers are done with FT
-                    if (any && in_lds) stage_footprint<2>(FT, ftw, wpr, fth, lvl + (size_t)by0 * a.P + bxa, a.P, bxa, a.P, lane);
-                    wave_sync();
-                    const int c0 = cx0 + 4 * lg;
-                    int adv[4], bdv[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { adv[q] = lad[c0 + q]; bdv[q] = lbd[c0 + q]; }
-                    const int nvalid = RW - c0;
-                    const uint32_t colmask = nvalid >= 4 ? 0xffffffffu : (nvalid <= 0 ? 0u : (1u << (8 * nvalid)) - 1u);
-                    const int xo = ((int)lds_offset_of(FT) - bxa) << kAbBits, yo = -(by0 << kAbBits);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int rr = lr + 8 * i;
-                        const int rc = rr < nr ? rr : nr - 1;   // rows past the block repeat its last row, unstored
-                        uint32_t pk = 0;
-                        if (interior && in_lds) {   // folded LDS addressing, the row's 16 tap reads before arithmetic
-                            const int x0r = lx0[rc] + xo, y0r = ly0[rc] + yo;
-                            uint32_t off[4];
-                            int fxv[4], fyv[4], v[4][4];
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const int sxv = x0r + adv[q], syv = y0r + bdv[q];
-                                fxv[q] = __builtin_amdgcn_ubfe(sxv, kAbBits - kInterBits, kInterBits);
-                                fyv[q] = __builtin_amdgcn_ubfe(syv, kAbBits - kInterBits, kInterBits);
-                                off[q] = (uint32_t)mad24(syv >> kAbBits, ftw, sxv >> kAbBits);
-                            }
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) lds_taps(off[q], ftw, v[q]);
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) pk |= (uint32_t)bilerp24(v[q], fxv[q], fyv[q]) << (8 * q);
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const int X = (lx0[rc] + adv[q]) >> (kAbBits - kInterBits);
-                                const int Y = (ly0[rc] + bdv[q]) >> (kAbBits - kInterBits);
-                                const int v = !any ? 0 : in_lds ? ft_tap_general(FT, ftw, bxa, by0, W, H, X, Y)
-                                                                : roi_tap(lvl, W, H, a.P, X, Y);
-                                pk |= (uint32_t)v << (8 * q);
-                            }
-                        }
-                        pk &= colmask;
-                        // exact row sums of I and I^2 over the row's 32 tile columns (8 lanes), one LDS atomic each
-                        uint32_t s1 = __builtin_amdgcn_udot4(pk, 0x01010101u, 0u, false);
-                        uint32_t s2 = __builtin_amdgcn_udot4(pk, pk, 0u, false);
-                        s1 = sum8_dpp(s1);
-                        s2 = sum8_dpp(s2);
-                        if (rr < nr) {
-                            const int slotr = ring(R0 + rr);
-                            *(uint32_t*)(SB + (size_t)slotr * SBp + c0) = pk ^ 0x80808080u;
-                            if (lg == 0) {
-                                atomicAdd(&rall[slotr], s1);
-                                atomicAdd(&rallq[slotr], s2);
-                            }
-                        }
-                    }
-                }
-            }
-            __syncthreads();   // the band's rows and row sums are complete
-            // this band's A fragments (L2-resident slab; rows past the template are the slab's zero padding), in
-            // flight during the edge sums
-            fpm_v4i Areg[NK];
-            {
-                const int8_t* ap = a.tmpl8 + (size_t)(T0 + kMmaRows * mt + n) * a.tp8 + 16 * g;
-#pragma unroll
-                for (int k = 0; k < NK; ++k)
-                    Areg[k] = k < a.nk ? *(const fpm_v4i*)(ap + 64 * k) : fpm_v4i{0, 0, 0, 0};
-            }
-            for (int i = tid; i < (nsrc - rlo) * 7; i += 256) {   // window [dx, dx + tw): full row minus edges
-                const int r = ring(T0 + rlo + i / 7), dx = i % 7;
-                const uint8_t* sbr = SB + (size_t)r * SBp;
-                uint32_t q1 = rall[r], q2 = rallq[r];
-                for (int c = 0; c < dx; ++c) { const uint32_t v = sbr[c] ^ 0x80u; q1 -= v; q2 -= v * v; }
-                for (int c = dx + tw; c < RW; ++c) { const uint32_t v = sbr[c] ^ 0x80u; q1 -= v; q2 -= v * v; }
-                wi[r * 7 + dx] = q1;
-                wq[r * 7 + dx] = q2;
-            }
-            __syncthreads();
-            if (kMmaRows * mt < rb && kMmaRows * nt < nsrc) {   // wave-uniform
-                int sr = kMmaRows * nt + n;
-                if (sr >= nsrc) sr = 0;   // column outside the band: computed, never stored
-                const uint8_t* bp = SB + (size_t)ring(T0 + sr) * SBp + 16 * g;
-                const uint4 ts4 = ld_at<uint4>(a.tsum, 4u * (T0 + kMmaRows * mt + 4 * g));   // (see k_roi_corr)
-                fpm_v4i acc[7];
-                band_mfma_regs<NK>(Areg, bp, a.nk, acc);
-                // D_dx: col = lane & 15 -> source row 16*nt + n, row = 4*(lane >> 4) + r -> template row 16*mt + 4g + r
-                const int s_ = kMmaRows * nt + n;
-                const uint32_t* wr = wi + ring(T0 + (s_ < nsrc ? s_ : 0)) * 7;
-                // element (template row tb + r, dy = s_ - tb - r, dx = d) of the band's [t][49] block sits at
-                // ob[42 r + d]: one pointer per lane, immediate offsets
-                const int tb = kMmaRows * mt + 4 * g;
-                uint32_t* ob = rs_out + (size_t)(T0 + tb) * 49 + (s_ - tb) * 7;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int t = tb + r, dy = s_ - t;
-                    if (t < rb && s_ < nsrc && dy >= 0 && dy < 7) {
-                        const uint32_t ts = r == 0 ? ts4.x : r == 1 ? ts4.y : r == 2 ? ts4.z : ts4.w;
-#pragma unroll
-                        for (int d = 0; d < 7; ++d) ob[42 * r + d] = (uint32_t)acc[d][r] + 128u * (wr[d] + ts) - kFix;
-                    }
-                }
-            }
-            if (tid < 2 * 49) {   // per-16-row-chunk partials of the window sums (k_roi_corr)
-                const int h = tid / 49, k = tid - h * 49;
-                const int chunk = (T0 >> 4) + h;
-                const int tlo = kMmaRows * h, thi = min(tlo + kMmaRows, rb);
-                if (chunk < a.nchunk && tlo < thi) {
-                    const int pdy = k / 7, ddx = k - pdy * 7;
-                    uint32_t s1 = 0;
-                    uint64_t s2 = 0;
-                    for (int t = tlo; t < thi; ++t) {
-                        const int r = ring(T0 + t + pdy) * 7 + ddx;
-                        s1 += wi[r];
-                        s2 += wq[r];
-                    }
-                    a.wsum[((size_t)slot * a.nchunk + chunk) * 49 + k] = s1;
-                    a.wsq[((size_t)slot * a.nchunk + chunk) * 49 + k] = s2;
-                }
-            }
-        }
-    }
-}
-#endif   // FPM_EXPERIMENTAL
 
 // candidate step of :329-366 as a pure function of the state and the n3 records (k_cand_step, k_roi_eval, the
 // k_roi_small prologue)
@@ -4847,7 +4283,7 @@ void launch_roi_warp(const RoiArgs& a, hipStream_t st) {
         // persistent grid's static task ranges, r05j)
         const int srcs = a.slot_cap / std::max(1, a.per_source * a.n3);
         const int dflt_cap = srcs <= 2 ? 7 * device_cus() : 0;
-        hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch, 0>), dim3(capped((int)(want3 < 16384 ? want3 : 16384), grid_cap_env(getenv("FPM_GRID_WARP"), dflt_cap))),
+        hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch>), dim3(capped((int)(want3 < 16384 ? want3 : 16384), grid_cap_env(getenv("FPM_GRID_WARP"), dflt_cap))),
                            dim3(256), 0, st, a);
         return;
     }
@@ -4855,7 +4291,6 @@ void launch_roi_warp(const RoiArgs& a, hipStream_t st) {
 }
 
 constexpr size_t kLdsPerCu = 160 * 1024;   // MI355X (gfx950) LDS per CU
-constexpr bool kCorrGlobalA = true;   // measured in scripts/roi_microbench.hip
 constexpr int kCorrWaves = 3;
 // register-A form at 13-16 k-steps: 2 waves per SIMD (A fragments + prefetched rows: 221 VGPRs), one workgroup per
 // resident slot (MI355X: 256 CUs)
@@ -4872,7 +4307,7 @@ static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream
         // layer 1 107.7 -> 99.4 us per 43-source microbenchmark launch, profiles/r03_y)
         if (NK == 4 && lds * 4 <= kLdsPerCu) {
             const int grid = capped((int)std::min<long>(items, 4L * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_roi_corr<0, 4, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
             return;
         }
         // at 8 and 12 k-steps the source rows staged by LDS-DMA (no staging VGPRs) make room for 4 waves per SIMD
@@ -4880,38 +4315,21 @@ static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream
         // profiles/r04/mbl1_r04g.txt; host-checked)
         if ((NK == 8 || NK == 12) && lds * 4 <= kLdsPerCu) {
             const int grid = capped((int)std::min<long>(items, 4L * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-            hipLaunchKernelGGL((k_roi_corr<0, true, 4, NK, false, kRS, true, true>), dim3(grid), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_roi_corr<0, 4, NK, false, kRS, true, true>), dim3(grid), dim3(256), lds, st, a);
             return;
         }
         // row results staged in LDS and flushed during the next item's staging (SE; Src7 microbenchmark at 43 sources:
         // layer 0 293.6 -> 264.4 us, layer 1 124.2 -> 115.4, bit-identical)
         const int grid = capped((int)std::min<long>(items, (long)kCorrWaves * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrWaves, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((k_roi_corr<0, kCorrWaves, NK, false, kRS, true>), dim3(grid), dim3(256), lds, st, a);
     } else {
         const int grid = (int)std::min<long>(items, (long)kCorrRunWaves * device_cus());
-        hipLaunchKernelGGL((k_roi_corr<0, true, kCorrRunWaves, NK, true, kRS>), dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((k_roi_corr<0, kCorrRunWaves, NK, true, kRS>), dim3(grid), dim3(256), lds, st, a);
     }
 }
-#ifdef FPM_EXPERIMENTAL
-// k_roi_corr16 (16-row items, 2-wave workgroups): as many workgroups as the LDS holds per CU, persistent
-bool launch_roi_corr16(const RoiArgs& a, hipStream_t st) {
-    if (a.nk > 12 || (a.roi_pitch >> 4) > 64) return false;
-    const size_t lds = roi_corr16_lds(a.roi_pitch);
-    const int per_cu = (int)std::min<size_t>(8, kLdsPerCu / lds);
-    if (per_cu < 1) return false;
-    const long items = (long)a.slot_cap * ((a.th + kB16Rows - 1) / kB16Rows);
-    const int grid = capped((int)std::min<long>(items, (long)per_cu * device_cus()), grid_cap_env(getenv("FPM_GRID_CORR"), 0));
-    if (a.nk <= 4) hipLaunchKernelGGL((k_roi_corr16<4, 4>), dim3(grid), dim3(128), lds, st, a);
-    else if (a.nk <= 8) hipLaunchKernelGGL((k_roi_corr16<8, 4>), dim3(grid), dim3(128), lds, st, a);
-    else hipLaunchKernelGGL((k_roi_corr16<12, 4>), dim3(grid), dim3(128), lds, st, a);
-    return true;
-}
-
-#endif
-
 void launch_roi_corr(const RoiArgs& a, hipStream_t st) {
     if (a.slot_cap <= 0 || a.equal1) return;
-    const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc, kCorrGlobalA);
+    const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
     // register-A form where its staged rows fit one 64-lane pass and A fits 16 k-steps (templates <= 1024 wide);
     // the slot-major form below serves wider templates
     if ((a.roi_pitch >> 4) <= 64 && a.nk <= 16 && lds <= 65536) {
@@ -4922,24 +4340,11 @@ void launch_roi_corr(const RoiArgs& a, hipStream_t st) {
         else launch_corr_regs<16>(a, items, lds, st);
         return;
     }
-    ensure_lds_attr((const void*)k_roi_corr<0, kCorrGlobalA, kCorrWaves>, lds);
+    ensure_lds_attr((const void*)k_roi_corr<0, kCorrWaves>, lds);
     const long items = (long)a.slot_cap * ((a.th + kBandRows - 1) / kBandRows);
     const int grid = (int)(items < 16384 ? items : 16384);
-    hipLaunchKernelGGL((k_roi_corr<0, kCorrGlobalA, kCorrWaves>), dim3(grid), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((k_roi_corr<0, kCorrWaves>), dim3(grid), dim3(256), lds, st, a);
 }
-
-#ifdef FPM_EXPERIMENTAL
-void launch_roi_fused(const RoiArgs& a, hipStream_t st) {
-    if (a.slot_cap <= 0 || a.equal1) return;
-    const size_t lds = (size_t)fuse_layout(a.tw).total;
-    const long units = (long)a.slot_cap * a.nparts;
-    const int grid = (int)(units < kFuseWgs ? units : kFuseWgs);
-    if (a.nk <= 4) hipLaunchKernelGGL(k_roi_fused<4>, dim3(grid), dim3(256), lds, st, a);
-    else if (a.nk <= 8) hipLaunchKernelGGL(k_roi_fused<8>, dim3(grid), dim3(256), lds, st, a);
-    else if (a.nk <= 12) hipLaunchKernelGGL(k_roi_fused<12>, dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(k_roi_fused<16>, dim3(grid), dim3(256), lds, st, a);
-}
-#endif
 
 void launch_roi_eval(const RoiArgs& a, hipStream_t st) {
     if (a.slot_cap <= 0) return;

@@ -5,8 +5,8 @@
 // row dot products and window-sum partials (k_roi_eval's inputs) and the records k_roi_eval makes of them are
 // identical, then times both.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off scripts/fused_bench.hip -o build/fused_bench
-#define FPM_EXPERIMENTAL 1
 #include "../fastest_image_pattern_matching_amd/csrc/fpm_kernels.hip"
+#include "roi_fused.hip"   // k_roi_fused is compiled only into this harness
 
 #include <cstdio>
 #include <cstdlib>

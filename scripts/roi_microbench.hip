@@ -249,7 +249,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&a.wsum, (size_t)C * n3 * a.nchunk * 49 * 4));
     CK(hipMalloc(&a.wsq, (size_t)C * n3 * a.nchunk * 49 * 8));
     CK(hipMalloc(&a.rec, sizeof(RoiRecord) * C * n3));
-        printf("rois %d rc %d chunks %d corr lds %zu / %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc, false), roi_corr_lds(roi_pitch_for(TW), TW, a.rc, true));
+        printf("rois %d rc %d chunks %d corr lds %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc));
     // ---- product kernels (tables -> warp -> corr -> eval) --------------------------------------------------
     a.tabw = roi_pitch_for(TW); a.tabh = roi_tab_rows(TH);
     a.roi_pitch = roi_pitch_for(TW); a.roi_stride = roi_tiles_bytes(TW, TH);
@@ -296,21 +296,16 @@ int main(int argc, char** argv) {
             timeit([&] { hipLaunchKernelGGL((k_roi_warp3<8>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 8w");
             timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w");
             timeit([&] { hipLaunchKernelGGL((k_roi_warp3<6>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 6w");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w p68");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 1>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w p68 r03stg");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<8, 68, 0>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 8w p68");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 1>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no staging");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 2>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no lerp");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 3>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl addr only");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 4>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no stores");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 5>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no interior");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 0, false, true>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w sld");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 0, true>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w pft");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<6, 68, 0, 0, true>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 6w pft");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 6>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -stage");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 7>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -tables");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 8>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -border");
-            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 64, 1>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w p64 r03stg");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 7w p68");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<8, 68>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 8w p68");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 1>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no staging");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 2>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no lerp");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 3>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl addr only");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 4>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no stores");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 5>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl no interior");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 6>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -stage");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 7>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -tables");
+            timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 8>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 abl -border");
             {   // every warp3 form writes the same ROI bytes as the round-3 form
                 const size_t nb = (size_t)a.slot_cap * a.roi_stride;
                 std::vector<uint8_t> ref(nb), got(nb);
@@ -328,10 +323,7 @@ int main(int argc, char** argv) {
                 CK(hipDeviceSynchronize());
                 CK(hipMemcpy(ref.data(), a.roi, nb, hipMemcpyDeviceToHost));
                 run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7>), dim3(grid3), dim3(256), 0, 0, a); }, "p64");
-                run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0>), dim3(grid3), dim3(256), 0, 0, a); }, "p68");
-                run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 1>), dim3(grid3), dim3(256), 0, 0, a); }, "p68 r03stg");
-                run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 0, true>), dim3(grid3), dim3(256), 0, 0, a); }, "p68 pft");
-                run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68, 0, 0, false, true>), dim3(grid3), dim3(256), 0, 0, a); }, "p68 sld");
+                run_cmp([&] { hipLaunchKernelGGL((k_roi_warp3<7, 68>), dim3(grid3), dim3(256), 0, 0, a); }, "p68");
                 run_cmp([&] { launch_roi_warp(a, 0); }, "product");
             }
 
@@ -352,115 +344,86 @@ int main(int argc, char** argv) {
     launch_roi_warp(a, 0);   // the product's ROIs (the warp variants above may have left other bytes)
     timeit([&] { launch_roi_corr(a, 0); }, "prod corr");
     if (TW > 512 && TW <= 768) {   // register-A form (12 k-steps, the Src7 layer-0 product) and its phase ablations
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc, true);
+        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
         const int grid = (int)std::min<long>(items, 768);
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA full");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false, 0>), dim3(grid), dim3(256), lds, 0, a); }, "corrA RS0 full");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false, 1, true>), dim3(grid), dim3(256), lds, 0, a); }, "corrA SE full");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false, 1, true, true>), dim3(grid), dim3(256), lds, 0, a); }, "corrA SE DMA 3w");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 1, false, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA DMA 4w");
-        // round 5: the product form's phases (MODE ablations of k_roi_corr<., true, 4, 12, false, 1, true, true>)
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no mfma+epi");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no stores");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no partials");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no rowsums");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA full");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 12, false, 1, true>), dim3(grid), dim3(256), lds, 0, a); }, "corrA SE full");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 12, false, 1, true, true>), dim3(grid), dim3(256), lds, 0, a); }, "corrA SE DMA 3w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 1, false, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA DMA 4w");
+        // round 5: the product form's phases (MODE ablations of k_roi_corr<., 4, 12, false, 1, true, true>)
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no mfma+epi");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no stores");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no partials");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no rowsums");
         // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3 (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4 (again)");
-        {
-            const size_t lds_db = lds + 16 + (size_t)38 * a.roi_pitch;
-            hipFuncSetAttribute((const void*)k_roi_corr<0, true, 2, 12, false, 1, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_db);
-            hipFuncSetAttribute((const void*)k_roi_corr<0, true, 3, 12, false, 1, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_db);
-            printf("corr DB lds %zu\n", lds_db);
-            timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 2, 12, false, 1, true, true, true>), dim3((int)std::min<long>(items, 512)), dim3(256), lds_db, 0, a); }, "corrA SE DMA DB 2w");
-            timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false, 1, true, true, true>), dim3((int)std::min<long>(items, 512)), dim3(256), lds_db, 0, a); }, "corrA SE DMA DB 3wr");
-        }
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no mfma+epi");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<4, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no edges");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no stores");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no partials");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no rowsums");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no mfma+epi");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no stores");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no partials");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no rowsums");
         if (envi("MB_CORR_ONLY", 0)) { launch_roi_corr(a, 0); }
     }
     if (TW > 256 && TW <= 512) {   // 8 k-steps (the Src7 layer-1 product): 3 vs 4 waves per SIMD
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc, true);
+        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 8, false>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 3 waves");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 8, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 SE 3 waves");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE 4 waves");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w no rowsums");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 8, false>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 3 waves");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 8, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 SE 3 waves");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE 4 waves");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w no rowsums");
         // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3 (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4 (again)");
-        {
-            const size_t lds_db = lds + 16 + (size_t)38 * a.roi_pitch;
-            hipFuncSetAttribute((const void*)k_roi_corr<0, true, 4, 8, false, 1, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_db);
-            printf("corr8 DB lds %zu\n", lds_db);
-            timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds_db, 0, a); }, "corrA8 SE DMA DB 4w");
-        }
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3, 8, false, 0>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 RS0 3 waves");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4 (again)");
     }
     if (TW <= 256) {   // 4 k-steps (the Src7 layer-2 product): register staging, 4 waves per SIMD
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc, true);
+        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w no rowsums");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w no rowsums");
         // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3 (again)");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 3, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS3 (again)");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 4, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w RS4 (again)");
     }
     timeit([&] { launch_roi_eval(a, 0); }, "prod eval");
     {
-        const size_t lds0 = roi_corr_lds(a.roi_pitch, a.tw, a.rc, false), lds1 = roi_corr_lds(a.roi_pitch, a.tw, a.rc, true);
+        const size_t lds1 = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
         const int grid = std::min(C * n3 * ((TH + 31) / 32), 16384);
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, false, 1>), dim3(grid), dim3(256), lds0, 0, a); }, "corr ldsA free");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, false, 4>), dim3(grid), dim3(256), lds0, 0, a); }, "corr ldsA w4");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 1>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA free");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, true, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, true, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4 no mfma");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<3, true, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4 no stage");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<3, true, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3 no stage");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, true, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3 no mfma");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 1>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA free");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4 no mfma");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<3, 4>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w4 no stage");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<3, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3 no stage");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3 no mfma");
         launch_roi_corr(a, 0);
         if (envi("MB_DMA_CHECK", 0)) {   // the host check below then checks the LDS-DMA staged form
             hipMemset(a.rowsum, 0xff, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4);
             const long items = (long)a.slot_cap * ((TH + 31) / 32);
             if (TW > 512 && TW <= 768)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
             else if (TW > 256 && TW <= 512)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
             printf("host check of the DMA form\n");
-        }
-        if (envi("MB_DB_CHECK", 0)) {   // the host check below then checks the double-buffered LDS-DMA form
-            hipMemset(a.rowsum, 0xff, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4);
-            const long items = (long)a.slot_cap * ((TH + 31) / 32);
-            const size_t lds_db = lds1 + 16 + (size_t)38 * a.roi_pitch;
-            if (TW > 512 && TW <= 768)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 2, 12, false, 1, true, true, true>), dim3((int)std::min<long>(items, 512)), dim3(256), lds_db, 0, a);
-            else if (TW > 256 && TW <= 512)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds_db, 0, a);
-            printf("host check of the DB form\n");
         }
         if (envi("MB_SE_CHECK", 0)) {   // the host check below then checks the LDS-staged epilogue form
             hipMemset(a.rowsum, 0xff, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4);
             const long items = (long)a.slot_cap * ((TH + 31) / 32);
             if (TW > 512 && TW <= 768)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 3, 12, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, 3, 12, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds1, 0, a);
             else if (TW > 256 && TW <= 512)
-                hipLaunchKernelGGL((k_roi_corr<0, true, 4, 8, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
+                hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds1, 0, a);
             printf("host check of the SE form\n");
         }
     }

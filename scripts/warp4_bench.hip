@@ -334,7 +334,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&a.wsum, (size_t)C * n3 * a.nchunk * 49 * 4));
     CK(hipMalloc(&a.wsq, (size_t)C * n3 * a.nchunk * 49 * 8));
     CK(hipMalloc(&a.rec, sizeof(RoiRecord) * C * n3));
-        printf("rois %d rc %d chunks %d corr lds %zu / %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc, false), roi_corr_lds(roi_pitch_for(TW), TW, a.rc, true));
+        printf("rois %d rc %d chunks %d corr lds %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc));
     // ---- product kernels (tables -> warp -> corr -> eval) --------------------------------------------------
     a.tabw = roi_pitch_for(TW); a.tabh = roi_tab_rows(TH);
     a.roi_pitch = roi_pitch_for(TW); a.roi_stride = roi_tiles_bytes(TW, TH);
@@ -359,7 +359,7 @@ int main(int argc, char** argv) {
     const size_t nb = (size_t)a.slot_cap * a.roi_stride;
     std::vector<uint8_t> ref(nb), got(nb);
     CK(hipMemset(a.roi, 0x5a, nb));
-    hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch, 0>), dim3(grid3), dim3(256), 0, 0, a);
+    hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch>), dim3(grid3), dim3(256), 0, 0, a);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(ref.data(), a.roi, nb, hipMemcpyDeviceToHost));
     auto check = [&](auto launch, const char* name) {
@@ -375,7 +375,7 @@ int main(int argc, char** argv) {
         auto l = [&] { hipLaunchKernelGGL((k_roi_warp4<WPE, PF>), dim3(grid3), dim3(256), 0, 0, a); }; \
         check(l, "warp4 w" #WPE " pf" #PF); timeit(l, "warp4 w" #WPE " pf" #PF); } while (0)
     for (int rep = 0; rep < 2; ++rep) {
-        timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch, 0>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 product");
+        timeit([&] { hipLaunchKernelGGL((k_roi_warp3<7, kFtPitch>), dim3(grid3), dim3(256), 0, 0, a); }, "warp3 product");
         W4(7, 0); W4(7, 1); W4(7, 2); W4(7, 3); W4(6, 3); W4(6, 7); W4(5, 7); W4(7, 7);
     }
     return 0;

@@ -74,7 +74,7 @@ def _kernel_symbols():
 
 def test_product_library_holds_no_measurement_kernels():
     """The product library carries only result-path kernels: no fused K6+K7 experiment and no 16-row-item
-    correlation (FPM_EXPERIMENTAL builds only, scripts/fused_bench.hip / corr16_bench.hip), and every ablation template parameter of k_roi_corr / k_roi_small (MODE) and
+    correlation (scripts/roi_fused.hip / roi_corr16.hip, built only into fused_bench / corr16_bench), and every ablation template parameter of k_roi_corr / k_roi_small (MODE) and
     k_roi_warp (ABL) at its product value 0 -- the profiling instantiations exist only in scripts/*.hip."""
     ks = _kernel_symbols()
     assert any(k.startswith("fpm::k_roi_warp3") for k in ks) and any(k.startswith("fpm::k_roi_corr<") for k in ks)
@@ -87,9 +87,21 @@ def test_product_library_holds_no_measurement_kernels():
         if k.startswith("fpm::k_roi_warp<"):
             assert args[1] == "0", k
         if k.startswith("fpm::k_roi_warp3<"):
-            assert args[3] == "0" and args[4:] == ["false", "false"], k   # no ablation, no measurement-only form
+            assert args[2] == "0" and len(args) == 3, k   # <WPE, PITCH, ABL>: no ablation, no measurement-only form
         if k.startswith("fpm::k_roi_corr<"):
-            assert args[-1] == "false", k                                  # no double-buffered measurement form
+            assert len(args) == 7, k   # <MODE, WPE, NK, PFR, RS, SE, DMA>: no double-buffered measurement form
+
+
+def test_product_sources_hold_no_measurement_kernels():
+    """No file under csrc/ mentions the measurement-only kernels or the define that once guarded them: they live in
+    scripts/roi_fused.hip and scripts/roi_corr16.hip."""
+    csrc = os.path.join(REPO, "fastest_image_pattern_matching_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)))
+    assert any(f.endswith(".hip") for f in files)
+    for f in files:
+        text = open(os.path.join(csrc, f), errors="replace").read()
+        for word in ("FPM_EXPERIMENTAL", "k_roi_fused", "k_roi_corr16"):
+            assert word not in text, (f, word)
 
 
 def test_product_switches_are_result_neutral():

@@ -23,21 +23,23 @@ FPM_E_CAPACITY = -5
 FPM_E_INTERNAL = -6
 
 (K_PYR, K_TOP_WARP, K_TOP_NCC, K_TOP_NMS, K_CAND_INIT, K_ROI_TABLES, K_ROI_WARP, K_ROI_CORR, K_ROI_EVAL, K_ROI_SMALL,
- K_CAND_STEP, K_TOP_MAP) = range(12)
+ K_CAND_STEP, K_TOP_MAP, K_NOT) = range(13)
 # profiling index -> kernel (include/fpm.h FPM_K_*); top_ncc is k_top_mma (matrix-core top layer) where it applies, else
 # k_ncc_tile for templates up to 128 x 64; top_map = k_top_map, the matrix-core form's fallback (full maps for the jobs
-# its lists left)
+# its lists left); bitwise_not = k_bitwise_not, 255 - source over the staged level 0 (Params.bitwise_not)
 KERNEL_NAMES = ["pyr_down", "top_warp", "top_ncc", "top_nms", "cand_init", "roi_tables", "roi_warp", "roi_corr",
-                "roi_eval", "roi_small", "cand_step", "top_map"]
+                "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not"]
 KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_warp"],
                   "top_ncc": ["k_top_mma", "k_ncc_tile", "k_ncc_map"],
                   "top_nms": ["k_nms_greedy", "k_nms"], "cand_init": ["k_cand_init"], "roi_tables": ["k_roi_tables"],
                   "roi_warp": ["k_roi_warp3", "k_roi_warp"], "roi_corr": ["k_roi_corr"], "roi_eval": ["k_roi_eval"],
-                  "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"]}
+                  "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"],
+                  "bitwise_not": ["k_bitwise_not"]}
 
 
 class Params(C.Structure):
-    """fpm_params — the 7 TemplateMatcher setters + hidden range members (TemplateMatcher.h:22-28, 88-89)."""
+    """fpm_params — the 7 TemplateMatcher setters + hidden range members (TemplateMatcher.h:22-28, 88-89), then the
+    MFC tool's fast mode and bitwise-not switches (MatchToolDlg.cpp:936, :788)."""
 
     _fields_ = [
         ("max_pos", C.c_int32),
@@ -51,6 +53,8 @@ class Params(C.Structure):
         ("semantics", C.c_int32),
         ("tolerance", C.c_double * 4),
         ("top_angle_step", C.c_double),
+        ("stop_layer", C.c_int32),
+        ("bitwise_not", C.c_int32),
     ]
 
 
@@ -99,6 +103,7 @@ SIGNATURES = {
     "fpm_op_pyr_down": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, _U8P, C.c_size_t]),
     "fpm_op_pyr_down2": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, _U8P, C.c_size_t, _U8P, C.c_size_t,
                                    C.c_int32, C.c_int32]),
+    "fpm_op_bitwise_not": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, _U8P, C.c_size_t]),
     "fpm_op_warp_affine": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_double), _U8P,
                                      C.c_int32, C.c_int32, C.c_size_t, C.c_int32]),
     "fpm_op_ncc_map": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32,

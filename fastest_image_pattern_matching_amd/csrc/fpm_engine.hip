@@ -85,6 +85,7 @@ struct SrcLevel {
 struct Plan {
     bool valid = false;
     int sw = 0, sh = 0, S = 0, L = 0;
+    int stop = 0;                              // the last refined layer: min(1, L) with fpm_params.stop_layer, else 0
     fpm_params prm{};
     int nang = 0, cap = 0, n3 = 1, C = 0;      // C = S * nang * cap candidate slots
     int a0 = 0, nang_all = 0;                  // this plan's angles = [a0, a0 + nang) of the full top-layer list
@@ -185,6 +186,7 @@ struct fpm_ctx {
     std::chrono::steady_clock::time_point t_call0;
     bool pending = false;    // a staged search is in flight (fpm_match_staged_launch)
     bool staged = false;     // the source slab holds an fpm_stage_sources batch (fpm_match re-lays it out for one source)
+    bool src_inverted = false;   // level 0 of the slab holds 255 - source (fpm_params.bitwise_not; apply_polarity)
     fpm_params run_prm{};    // parameters of the search in flight (snapshot at launch; the host tail reads these)
     // per-source candidate records of the last search (collect_candidates; fpm_match_*candidates)
     std::vector<std::vector<fpm_candidate>> cands;
@@ -364,7 +366,8 @@ bool same_search_params(const fpm_params& a, const fpm_params& b) {
     return a.max_pos == b.max_pos && a.min_reduce_area == b.min_reduce_area && a.max_overlap == b.max_overlap &&
            a.score == b.score && a.tolerance_angle == b.tolerance_angle && a.use_simd == b.use_simd &&
            a.tolerance_range == b.tolerance_range && a.semantics == b.semantics &&
-           a.top_angle_step == b.top_angle_step && std::equal(a.tolerance, a.tolerance + 4, b.tolerance);
+           a.top_angle_step == b.top_angle_step && std::equal(a.tolerance, a.tolerance + 4, b.tolerance) &&
+           (a.stop_layer != 0) == (b.stop_layer != 0);
 }
 
 // Input guard of the angle list (TemplateMatcher.cpp:130-144 accumulates `a += step` until the tolerance): a non-finite
@@ -510,6 +513,9 @@ int build_plan(fpm_ctx* ctx) {
     P.sw = ctx->sw; P.sh = ctx->sh; P.S = ctx->S; P.L = L; P.prm = ctx->prm;
     P.shard = ctx->shard; P.shards = ctx->shards;
     const fpm_params& prm = ctx->prm;
+    // fast mode (MatchToolDlg.cpp:936): with a top layer of 0 the reference reads vecPyramid[1] out of bounds; here
+    // that case is the normal search
+    P.stop = std::min(prm.stop_layer ? 1 : 0, L);
     const TmplLevel& tt = ctx->tmpl[L];
     // angle list (TemplateMatcher.cpp:130-144); the step override is an extension (fpm_params.top_angle_step)
     const double step = prm.top_angle_step > 0 ? prm.top_angle_step : std::atan(2.0 / std::max(tt.w, tt.h)) * kR2D;
@@ -799,6 +805,7 @@ constexpr int64_t kPyr2MaxBytes = 16ll << 20;     // two-level pyramid launches 
 int enqueue_search(fpm_ctx* ctx) {
     Plan& P = ctx->plan;
     const int L = P.L, S = P.S, J = S * P.nang;
+    const int stop = P.stop;   // the last refined layer (the plan's copy: nothing here reads the context's parameters for it)
     hipStream_t st = ctx->stream;
     uint8_t* dsrc = ctx->d_src.as<uint8_t>();
     const SrcLevel& top = ctx->src[L];
@@ -837,7 +844,7 @@ int enqueue_search(fpm_ctx* ctx) {
     ca.live_count = livecnt + 0;
     ca.nang = P.nang; ca.cap = P.cap; ca.total = P.C;
     ca.center = P.center;
-    ca.refine = L > 0 ? (L == 1 ? 2 : 1) : 0;
+    ca.refine = L > stop ? (L - 1 == stop ? 2 : 1) : 0;   // (no refinement at all when L == stop: MatchToolDlg.cpp:949-953)
     bool cand_fused = false;
     // the fused top layer also initialises the candidates (cand_init_job) when the peaks fit its LDS list; its
     // live-list atomics then need the counters zeroed by an earlier launch: the first pyramid level's
@@ -845,6 +852,7 @@ int enqueue_search(fpm_ctx* ctx) {
     // L >= 1: the first pyrDown launch zeroes the counters before the top kernel's live-list atomics.  L == 0: no
     // pyramid launch precedes it, so its block 0 zeroes them -- safe only because the candidate init then runs in
     // mode 1 (refine == 0: states and live list written directly, no live-count atomics); launch_top_fused checks it
+    // (L == stop == 1 also runs mode 1, behind the pyramid launch's zeroing)
     const bool pyr_zero = (top_init && L >= 1) || use_mma;   // (use_mma implies L >= 1: plan_top_mma)
     // K1: source pyramid (all staged sources per launch).  Two levels per launch (k_pyr_down2) where the pair's input
     // is small (<= kPyr2MaxBytes over the batch: launch-bound levels, e.g. every pair of a single Src7 search: 14.8 ->
@@ -971,7 +979,7 @@ int enqueue_search(fpm_ctx* ctx) {
         ProfScope ps(ctx, FPM_K_CAND_INIT, 0);
         launch_cand_init(ca, st);
     }
-    // the prologue-stepped run: layers L-1 .. run_end, the leading small layers above layer 0 (none of them a
+    // the prologue-stepped run: layers L-1 .. run_end, the leading small layers above the stop layer (none of them a
     // matResult = 1 layer).  From its second layer on, a layer's k_roi_small steps the previous layer's candidates in
     // its prologue over the unchanged live list (k_cand_step launches saved: run length - 1); one k_cand_step after
     // the run's last layer steps and compacts.  FPM_STEP_PROLOGUE=0 keeps one k_cand_step per layer (result-neutral).
@@ -983,7 +991,7 @@ int enqueue_search(fpm_ctx* ctx) {
     const bool step_prologue = prol_env ? atoi(prol_env) != 0 : S <= kPrologueMaxSources;
     int run_end = L;
     if (step_prologue)
-        for (int l = L - 1; l >= 1; --l) {
+        for (int l = L - 1; l > stop; --l) {
             if (!roi_small_fits(ctx->tmpl[l].w, ctx->tmpl[l].h) || ctx->tmpl[l].equal1) break;
             run_end = l;
         }
@@ -999,7 +1007,7 @@ int enqueue_search(fpm_ctx* ctx) {
     const char* stab_env = getenv("FPM_STEP_TABLES");
     const bool step_tables = (stab_env ? atoi(stab_env) != 0 : true) && (size_t)P.C * P.n3 <= (size_t)P.slot_cap;
     bool tables_done = false;   // this layer's tables were written by the previous layer's step
-    for (int l = L - 1; l >= 0; --l) {
+    for (int l = L - 1; l >= stop; --l) {
         const int d = L - 1 - l;
         const SrcLevel& lv = ctx->src[l];
         const TmplLevel& tl = ctx->tmpl[l];
@@ -1029,8 +1037,8 @@ int enqueue_search(fpm_ctx* ctx) {
         ra.wsum = P.d_wsum.as<uint32_t>();
         ra.wsq = P.d_wsq.as<uint64_t>();
         ra.rec = P.d_rec.as<RoiRecord>();
-        ra.step = l > 0 ? 1 : 0;   // candidate step fused into k_roi_eval (layer 0 is decided on the host)
-        ra.mark_reached0 = l - 1 == 0 ? 1 : 0;
+        ra.step = l > stop ? 1 : 0;   // candidate step fused into k_roi_eval (the stop layer is decided on the host)
+        ra.mark_reached0 = l - 1 == stop ? 1 : 0;
         ra.live_out = live[cur_list ^ 1];
         ra.live_out_count = livecnt + d + 1;
         ra.thr = P.layer_score[l];
@@ -1049,7 +1057,7 @@ int enqueue_search(fpm_ctx* ctx) {
                 ra.live_out_count = livecnt + d;   // the survivors entering this layer (counted, not listed)
             }
         }
-        if (step_tables && l >= 1 && ra.step && !roi_small_fits(ctx->tmpl[l - 1].w, ctx->tmpl[l - 1].h) &&
+        if (step_tables && l - 1 >= stop && ra.step && !roi_small_fits(ctx->tmpl[l - 1].w, ctx->tmpl[l - 1].h) &&
             !ctx->tmpl[l - 1].equal1) {
             const TmplLevel& nt = ctx->tmpl[l - 1];
             ra.nt_tab = P.d_tab.as<int32_t>();
@@ -1108,7 +1116,7 @@ int enqueue_search(fpm_ctx* ctx) {
         }
     }
     HIP_TRY(hipGetLastError());
-    // results into pinned host memory (one kernel; only the layer-0 candidates' states and records)
+    // results into pinned host memory (one kernel; only the stop-layer candidates' states and records)
     {
         PackArgs pa;
         pa.counts = P.d_counts.as<int32_t>(); pa.J = J;
@@ -1116,8 +1124,8 @@ int enqueue_search(fpm_ctx* ctx) {
         pa.cap = P.cap;
         if ((size_t)J * P.cap != (size_t)P.C) { ctx->err = "plan layout: C != J * cap"; return FPM_E_INTERNAL; }
         pa.livecnt = livecnt; pa.nlive = L + 2;
-        pa.live0 = L > 0 ? live[cur_list] : nullptr;   // the layer-0 list
-        pa.live0_count = livecnt + (L > 0 ? L - 1 : 0);
+        pa.live0 = L > stop ? live[cur_list] : nullptr;   // the stop layer's list
+        pa.live0_count = livecnt + (L > stop ? L - 1 - stop : 0);
         pa.state = P.d_state.as<CandState>();
         pa.rec = P.d_rec.as<RoiRecord>();
         pa.n3 = P.n3;
@@ -1139,10 +1147,12 @@ int enqueue_search(fpm_ctx* ctx) {
 //     vecAllResult in sorted order, filterWithScore, filterWithRotatedRect, the final sort and the
 //     s_SingleTargetMatch conversion (:373-432).  It needs the complete push-order sequence, i.e. the shards'
 //     records concatenated in shard order.
-// pos[id] = index of candidate id in the layer-0 live list (k_pack's compact states / records), -1 if absent.
+// pos[id] = index of candidate id in the stop layer's live list (k_pack's compact states / records), -1 if absent.
+// The stop layer is layer 0, or layer 1 in fast mode (fpm_params.stop_layer, MatchToolDlg.cpp:936-1037): the same
+// decision from that layer's records, no sub-pixel fit (:1013), the back-mapped ptLT doubled in float (:1035).
 void collect_candidates(fpm_ctx* ctx, int s, const std::vector<int>& pos, std::vector<fpm_candidate>& out) {
     Plan& P = ctx->plan;
-    const int L = P.L;
+    const int L = P.L, stop = P.stop;
     out.clear();
     if (P.nang == 0) return;
     const char* h = P.h_out.as<char>();
@@ -1152,7 +1162,7 @@ void collect_candidates(fpm_ctx* ctx, int s, const std::vector<int>& pos, std::v
     const RoiRecord* rec = (const RoiRecord*)(h + P.h_rec);
     const TmplLevel& t0 = ctx->tmpl[0];
     const double astep = std::atan(2.0 / std::max(t0.w, t0.h)) * kR2D;   // layer 0's angle step (:283)
-    const SrcLevel& lv = ctx->src[0];
+    const SrcLevel& lv = ctx->src[stop];
     const F2 sc = f2((lv.w - 1) / 2.0f, (lv.h - 1) / 2.0f);
     // each angle's candidates go to their place in push order (angle-major): the angles run on the host pool when
     // there are many candidates
@@ -1171,19 +1181,20 @@ void collect_candidates(fpm_ctx* ctx, int s, const std::vector<int>& pos, std::v
             c.angle_index = P.a0 + a;
             c.peak_rank = r;
             c.source = s;
-            if (L == 0) {   // iTopLayer <= iStopLayer (:272-276)
+            if (L <= stop) {   // iTopLayer <= iStopLayer (:272-276; MatchToolDlg.cpp:949-953: ptLT * 2 when L == 1)
                 const F2 pt = f2((float)pk.x - P.top[a].tx, (float)pk.y - P.top[a].ty);
                 const double rad = -P.angles[a] * kD2R;
                 const F2 lt = rotate_pt(f2(pt.x, pt.y), P.center, std::cos(rad), std::sin(rad));
-                c.x = lt.x; c.y = lt.y; c.score = pk.score; c.angle = P.angles[a]; c.kept = 1;
+                const F2 up_lt = L == 0 ? lt : f2(lt.x * 2, lt.y * 2);
+                c.x = up_lt.x; c.y = up_lt.y; c.score = pk.score; c.angle = P.angles[a]; c.kept = 1;
                 out[o++] = c;
                 continue;
             }
             const int li = pos[id];
             if (li < 0) { out[o++] = c; continue; }   // broke out at a layer > 0 (:331-332)
             const CandState& cs = state[li];
-            // layer 0 (:282-358) from the device's ROI records
-            const int d = L - 1;
+            // the stop layer (:282-358) from the device's ROI records
+            const int d = L - 1 - stop;
             int imax = 0;
             double big = -1;
             for (int j = 0; j < P.n3; ++j) {
@@ -1198,8 +1209,8 @@ void collect_candidates(fpm_ctx* ctx, int s, const std::vector<int>& pos, std::v
                 nm[j] = m;
                 if (nm[j].score > big) { imax = j; big = nm[j].score; }
             }
-            if (nm[imax].score < P.layer_score[0]) { out[o++] = c; continue; }
-            if (ctx->run_prm.subpixel && !nm[imax].on_border && imax != 0 && imax != 2) {
+            if (nm[imax].score < P.layer_score[stop]) { out[o++] = c; continue; }
+            if (ctx->run_prm.subpixel && stop == 0 && !nm[imax].on_border && imax != 0 && imax != 2) {
                 double nx = 0, ny = 0, na = 0;
                 subpix_estimation(nm, &nx, &ny, &na, astep, imax);
                 nm[imax].ptx = nx; nm[imax].pty = ny;
@@ -1212,6 +1223,7 @@ void collect_candidates(fpm_ctx* ctx, int s, const std::vector<int>& pos, std::v
             F2 p = f2((float)(nm[imax].ptx + pad.x), (float)(nm[imax].pty + pad.y));
             const double nrad = -nang * kD2R;
             p = rotate_pt(p, sc, std::cos(nrad), std::sin(nrad));
+            if (stop) p = f2(p.x * 2, p.y * 2);   // to layer 0's coordinates, in float before it widens (MatchToolDlg.cpp:1035)
             c.x = p.x; c.y = p.y; c.score = nm[imax].score; c.angle = nang; c.kept = 1;
             out[o++] = c;
         }
@@ -1361,8 +1373,9 @@ static bool overlap_filter_device(fpm_ctx* ctx, std::vector<HostMatch>& v, doubl
 }
 
 // Returns false when `cand` is not in push order (angle_index ascending, peak_rank 0, 1, ... within an angle).
+// stop: the search's stop layer (the plan's), or -1 to derive it from prm (fpm_merge_candidates has no plan).
 bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candidate* cand, int n,
-                      std::vector<fpm_result>& out, fpm_ctx* dev_ctx) {
+                      std::vector<fpm_result>& out, fpm_ctx* dev_ctx, int stop = -1) {
     out.clear();
     for (int i = 0; i < n; ++i) {
         const bool first = i == 0 || cand[i].angle_index != cand[i - 1].angle_index;
@@ -1376,6 +1389,11 @@ bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candida
     const clk::time_point t0 = clk::now();
     clk::time_point t1 = t0;
     std::vector<HostMatch> all;
+    // the overlap filter's rectangle: the stop layer's template size scaled to layer 0 (MatchToolDlg.cpp:1053-1054) --
+    // with fast mode and a top layer >= 1 the layer-1 size times two, which exceeds an odd level-0 size by one.
+    // Without a plan the top layer comes from the level-0 size and MinReduceArea by the search's own rule.
+    if (stop < 0) stop = std::min(prm.stop_layer ? 1 : 0, top_layer(t0w, t0h, (int)std::sqrt((double)prm.min_reduce_area)));
+    const int rw = stop ? (t0w + 1) / 2 * 2 : t0w, rh = stop ? (t0h + 1) / 2 * 2 : t0h;
     // vecAllResult entry from a candidate record, with its rotated rectangle (:380-390)
     auto fill = [&](HostMatch& m, const fpm_candidate& c) {
         m = HostMatch{};
@@ -1383,8 +1401,8 @@ bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candida
         const double rad = -m.angle * kD2R;
         const float cs = (float)std::cos(rad), sn = (float)std::sin(rad);
         const F2 lt = f2((float)m.ptx, (float)m.pty);
-        const F2 rt = f2(lt.x + t0w * cs, lt.y - t0w * sn);
-        const F2 rb = f2(rt.x + t0h * sn, rt.y + t0h * cs);
+        const F2 rt = f2(lt.x + rw * cs, lt.y - rw * sn);
+        const F2 rb = f2(rt.x + rh * sn, rt.y + rh * cs);
         m.rect = rrect_from3(lt, rt, rb);
         m.del = false;
     };
@@ -1490,6 +1508,24 @@ int launch_search(fpm_ctx* ctx) {
     return FPM_OK;
 }
 
+// fpm_params.bitwise_not (MatchToolDlg.cpp:788-796): bring level 0 of the source slab to the polarity the search
+// asks for, on the context's stream ahead of the search graph.  The inversion is an involution, so switching the
+// option off over a batch that is still staged restores the uploaded bytes; the upper levels are rebuilt from level
+// 0 by every pass.
+int apply_polarity(fpm_ctx* ctx) {
+    const bool want = ctx->prm.bitwise_not != 0;
+    if (want == ctx->src_inverted) return FPM_OK;
+    const SrcLevel& l0 = ctx->src[0];
+    ProfScope ps(ctx, FPM_K_NOT, 2 * (int64_t)ctx->S * l0.w * l0.h);
+    if (!launch_bitwise_not(ctx->d_src.as<uint8_t>() + l0.off, l0.w, l0.h, l0.pitch, l0.img_bytes, ctx->S, ctx->stream)) {
+        ctx->err = "source slab layout: level-0 rows not 16-byte aligned";
+        return FPM_E_INTERNAL;
+    }
+    HIP_TRY(hipGetLastError());
+    ctx->src_inverted = want;
+    return FPM_OK;
+}
+
 // First half of a staged search: plan, then the whole device pass enqueued on the context's stream (no wait).
 int start_staged(fpm_ctx* ctx) {
     ctx->t_call0 = std::chrono::steady_clock::now();
@@ -1502,6 +1538,8 @@ int start_staged(fpm_ctx* ctx) {
         HIP_TRY(hipEventCreate(&ctx->t_ev[1]));
     }
     HIP_TRY(hipEventRecord(ctx->t_ev[0], ctx->stream));
+    rc = apply_polarity(ctx);   // (inside the timed pass, as the reference inverts inside its timer, :783-791)
+    if (rc != FPM_OK) return rc;
     if (ctx->plan.nang > 0) {   // an angle shard with no angles has no device work (and no candidates)
         rc = launch_search(ctx);
         if (rc != FPM_OK) return rc;
@@ -1533,9 +1571,9 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
     Plan& P = ctx->plan;
     results.assign(P.S, {});
     std::vector<int> pos;
-    if (P.L > 0 && P.nang > 0) {
+    if (P.L > P.stop && P.nang > 0) {   // the stop layer's live list
         const char* hb = P.h_out.as<char>();
-        const int n0 = ((const int32_t*)(hb + P.h_live))[P.L - 1];
+        const int n0 = ((const int32_t*)(hb + P.h_live))[P.L - 1 - P.stop];
         const int32_t* ids = (const int32_t*)(hb + P.h_live0);
         pos.assign(P.C, -1);
         for (int li = 0; li < n0; ++li) pos[ids[li]] = li;
@@ -1545,9 +1583,9 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
         collect_candidates(ctx, s, pos, ctx->cands[s]);
         if (merge)
             merge_candidates(ctx->run_prm, ctx->tmpl[0].w, ctx->tmpl[0].h, ctx->cands[s].data(), (int)ctx->cands[s].size(),
-                             results[s], ctx);
+                             results[s], ctx, P.stop);
     }
-    // stats: [angles, top candidates, live entering layer L-1 .. 0] (totals over the batch)
+    // stats: [angles, top candidates, live entering layer L-1 .. stop] (totals over the batch)
     const char* h = P.h_out.as<char>();
     const int32_t* counts = (const int32_t*)(h + P.h_counts);
     int64_t topc = 0;
@@ -1555,18 +1593,20 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
     ctx->stats.assign({(int64_t)P.nang, topc});
     static const int32_t zeros[64] = {};
     const int32_t* lc = P.nang > 0 ? (const int32_t*)(h + P.h_live) : zeros;
-    for (int d = 0; d < P.L; ++d) ctx->stats.push_back(lc[d]);
+    const int nref = P.L - P.stop;   // refinement layers that ran
+    for (int d = 0; d < nref; ++d) ctx->stats.push_back(lc[d]);
     // SURVEY.md §8(d) algorithmic bytes (compulsory input + output of each stage, u8 = 1 B, f32 = 4 B; scratch
     // between the stages of this design is not counted), summed over the batch:
     //   B_pyr = sum_{l<L} (W_l H_l + W_{l+1} H_{l+1});  B_top = sum_angles (W_L H_L + 4 |R_a|);
-    //   B_ref = sum_{l<L} sum_{live ROIs at l} ((w_l + 6)(h_l + 6) + w_l h_l + 49 * 4)
+    //   B_ref = sum_{stop<=l<L} sum_{live ROIs at l} ((w_l + 6)(h_l + 6) + w_l h_l + 49 * 4)
+    // (the pyramid is built down from level 0 whatever the stop layer; the layers below it add nothing to B_ref)
     {
         int64_t bp = 0, bt = 0, br = 0;
         for (int l = 0; l < P.L; ++l)
             bp += (int64_t)ctx->src[l].w * ctx->src[l].h + (int64_t)ctx->src[l + 1].w * ctx->src[l + 1].h;
         for (int a = 0; a < P.nang; ++a)
             bt += (int64_t)ctx->src[P.L].w * ctx->src[P.L].h + 4LL * P.map_w[a] * P.map_h[a];
-        for (int d = 0; d < P.L && P.nang > 0; ++d) {
+        for (int d = 0; d < nref && P.nang > 0; ++d) {
             const TmplLevel& t = ctx->tmpl[P.L - 1 - d];
             br += (int64_t)lc[d] * P.n3 * ((int64_t)(t.w + 6) * (t.h + 6) + (int64_t)t.w * t.h + 49 * 4);
         }
@@ -1579,7 +1619,7 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
         // lists) is charged the map term of B_top, 4 |R_a| per source and angle
         if (P.top_lists)
             for (int a = 0; a < P.nang; ++a) ctx->kp[FPM_K_TOP_NMS].bytes += 4LL * P.map_w[a] * P.map_h[a] * P.S;
-        for (int d = 0; d < P.L; ++d) {
+        for (int d = 0; d < nref; ++d) {
             const int l = P.L - 1 - d;
             const TmplLevel& t = ctx->tmpl[l];
             const int64_t rois = (int64_t)lc[d] * P.n3;
@@ -1613,6 +1653,7 @@ int run_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results) {
 int upload_sources(fpm_ctx* ctx, const uint8_t* const* grays, int count, int w, int h, size_t stride) {
     int rc = layout_sources(ctx, count, w, h);
     if (rc != FPM_OK) return rc;
+    ctx->src_inverted = false;   // the slab holds the sources as given
     const SrcLevel& l0 = ctx->src[0];
     for (int s = 0; s < count; ++s)
         HIP_TRY(hipMemcpy2DAsync(ctx->d_src.as<uint8_t>() + l0.off + l0.img_bytes * s, l0.pitch, grays[s], stride, w, h,
@@ -1640,6 +1681,8 @@ void fpm_params_default(fpm_params* p) {
     p->tolerance_range = 0;     // :38
     p->semantics = FPM_SEMANTICS_QT;
     p->top_angle_step = 0.0;    // extension: the reference's derived step
+    p->stop_layer = 0;          // m_bStopLayer1 off (MatchToolDlg.cpp:936)
+    p->bitwise_not = 0;         // m_ckBitwiseNot off (MatchToolDlg.cpp:788)
 }
 
 int fpm_abi_version(void) { return FPM_ABI_VERSION; }
@@ -2005,6 +2048,28 @@ int fpm_op_pyr_down(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2DAsync(dst, ds, ctx->d_op_b.p, dp, dw, dh, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FPM_OK;
+}
+
+int fpm_op_bitwise_not(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t ss, uint8_t* dst, size_t ds) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!src || !dst || w <= 0 || h <= 0 || ss < (size_t)w) { ctx->err = "bad image"; return FPM_E_INVALID_ARG; }
+    if (ds < (size_t)w) { ctx->err = "bad dst stride"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const SrcLevel lv = level_layout(w, h);   // the search's level-0 layout
+    HIP_TRY(ctx->d_op_a.ensure(lv.img_bytes));
+    HIP_TRY(hipMemcpy2DAsync(ctx->d_op_a.p, lv.pitch, src, ss, w, h, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, FPM_K_NOT, 2 * (int64_t)w * h);
+        if (!launch_bitwise_not(ctx->d_op_a.as<uint8_t>(), w, h, lv.pitch, lv.img_bytes, 1, ctx->stream)) {
+            ctx->err = "level layout: rows not 16-byte aligned";
+            return FPM_E_INTERNAL;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(dst, ds, ctx->d_op_a.p, lv.pitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
     return FPM_OK;
 }
 

@@ -185,6 +185,10 @@ void launch_pyr_down(const uint8_t* src, int sw, int sh, int sp, size_t s_img, u
 void launch_pyr_down2(const uint8_t* src, int sw, int sh, int sp, size_t s_img, uint8_t* bdst, int bw, int bh, int bp,
                       size_t b_img, uint8_t* cdst, int cw, int ch, int cp, size_t c_img, int nimg, hipStream_t st,
                       int seg_chunks = 0, int32_t* zero = nullptr, int nzero = 0, int chunk_rows = 0);
+// k_bitwise_not: 255 - x in place over the w x h pixels of nimg images (row pitch `pitch`, image stride `img_bytes`; the
+// bytes between w and the pitch are left alone).  Needs 16-byte aligned rows (img, pitch and img_bytes multiples of 16,
+// as level_layout gives them); returns false, launching nothing, otherwise
+bool launch_bitwise_not(uint8_t* img, int w, int h, int pitch, size_t img_bytes, int nimg, hipStream_t st);
 // zero / nzero: counters the search zeroes before its later kernels use them (block (0, 0) clears them), so the
 // graph carries no memset nodes
 void launch_warp(const WarpJob* jobs, int njobs, int max_pixels, hipStream_t st, int32_t* zero = nullptr,

@@ -662,6 +662,47 @@ void launch_pyr_down2(const uint8_t* src, int sw, int sh, int sp, size_t s_img, 
                            bp, b_img, cdst, cw, ch, cp, c_img, nimg, zero, nzero);
 }
 
+// ============================================================================================== bitwise not
+// x -> 255 - x (= ~x on a byte) in place over the w x h pixels of nimg level images (fpm_params.bitwise_not: the MFC
+// tool's `255 - m_matSrc`, MatchToolDlg.cpp:790).  One wave per row (wave-strided over the nimg * h rows), one lane
+// per 16 bytes of it: a uint4 load, ~ on its four packed dwords, a uint4 store.  Rows start 16-byte aligned
+// (launch_bitwise_not checks the base, the pitch and the image stride), so every access is an aligned 16-byte one; the
+// ragged end of a row (w % 16 bytes) goes as aligned dwords and then single bytes, so the bytes between w and the pitch
+// keep their values.  1 B read + 1 B written per pixel.
+__global__ __launch_bounds__(256) void k_bitwise_not(uint8_t* __restrict__ img0, int w, int h, int pitch, size_t img_bytes,
+                                                     int nrows) {
+    const int lane = threadIdx.x & 63;
+    const int nwaves = gridDim.x * 4;
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < nrows; row += nwaves) {
+        const int im = row / h, y = row - im * h;
+        uint8_t* r = img0 + (size_t)im * img_bytes + (size_t)y * pitch;
+        for (int x = lane << 4; x < w; x += 64 << 4) {
+            uint8_t* p = r + x;
+            if (x + 16 <= w) {
+                uint4 v = *(const uint4*)p;
+                v.x = ~v.x; v.y = ~v.y; v.z = ~v.z; v.w = ~v.w;
+                *(uint4*)p = v;
+            } else {
+                const int rem = w - x;   // 1 .. 15
+                int k = 0;
+                for (; k + 4 <= rem; k += 4) *(uint32_t*)(p + k) = ~*(const uint32_t*)(p + k);
+                for (; k < rem; ++k) p[k] = (uint8_t)~p[k];
+            }
+        }
+    }
+}
+
+// false: the layout does not give 16-byte aligned rows (nothing launched)
+bool launch_bitwise_not(uint8_t* img, int w, int h, int pitch, size_t img_bytes, int nimg, hipStream_t st) {
+    if (w <= 0 || h <= 0 || nimg <= 0) return true;
+    const int64_t nrows = (int64_t)nimg * h;
+    if (((uintptr_t)img & 15) || (pitch & 15) || (img_bytes & 15) || pitch < w || nrows > (1 << 30)) return false;
+    // memory-bound: at most 8 workgroups per CU's worth of blocks (4 rows each per turn), the rest by the wave stride
+    const int64_t g = std::min((nrows + 3) / 4, (int64_t)2048);
+    hipLaunchKernelGGL(k_bitwise_not, dim3((unsigned)g), dim3(256), 0, st, img, w, h, pitch, img_bytes, (int)nrows);
+    return true;
+}
+
 // ============================================================================================== K2
 __global__ __launch_bounds__(256) void k_warp(const WarpJob* __restrict__ jobs, int32_t* zero, int nzero) {
     if (blockIdx.x == 0 && blockIdx.y == 0)

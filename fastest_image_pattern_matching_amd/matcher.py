@@ -299,6 +299,20 @@ class TemplateMatcher:
     def getSubPixelEstimation(self) -> bool: return bool(self._params.subpixel)
     def getLastExecutionTime(self) -> float: return self._last_time
 
+    # -- the MFC tool's two search switches (MatchToolDlg.cpp:936, :788-796), honoured under both semantics ---
+    def setStopLayer1(self, v: bool):
+        """Fast mode (m_bStopLayer1): stop the pyramid descent at layer 1.  Positions have layer-1 precision (the
+        layer-1 ptLT times 2, no sub-pixel fit); a template whose top layer is 0 is searched as usual."""
+        self._params.stop_layer = 1 if v else 0
+
+    def getStopLayer1(self) -> bool: return bool(self._params.stop_layer)
+
+    def setBitwiseNot(self, v: bool):
+        """m_ckBitwiseNot: search 255 - source with the template as learned (patterns of inverted polarity)."""
+        self._params.bitwise_not = 1 if v else 0
+
+    def getBitwiseNot(self) -> bool: return bool(self._params.bitwise_not)
+
     # -- user rectangle: stored only, unused by matching (TemplateMatcher.cpp:1224-1238) ---------------------
     def setUserDefinedRect(self, rect): self._user_rect = tuple(rect)
     def getUserDefinedRect(self): return self._user_rect if self._user_rect is not None else (0, 0, 0, 0)
@@ -311,6 +325,20 @@ class TemplateMatcher:
         out = np.zeros(((h + 1) // 2, (w + 1) // 2), np.uint8)
         rc = self._check(self._lib.fpm_op_pyr_down(self._ctx, L.u8ptr(g), w, h, g.strides[0], L.u8ptr(out),
                                                    out.strides[0]), "pyr_down")
+        if rc != L.FPM_OK:
+            raise ValueError(self.last_error())
+        return out
+
+    def bitwise_not(self, img) -> np.ndarray:
+        """255 - img by the kernel a bitwise-not search runs over its staged sources (fpm_op_bitwise_not)."""
+        a = np.asarray(img)
+        # a row-strided view (a column slice of a wider image) goes down as it is, with its row stride
+        strided = a.ndim == 2 and a.dtype == np.uint8 and a.shape[1] > 0 and a.strides[1] == 1 and a.strides[0] >= a.shape[1]
+        g = a if strided else _gray(a)
+        h, w = g.shape
+        out = np.zeros((h, w), np.uint8)
+        rc = self._check(self._lib.fpm_op_bitwise_not(self._ctx, L.u8ptr(g), w, h, g.strides[0], L.u8ptr(out),
+                                                      out.strides[0]), "bitwise_not")
         if rc != L.FPM_OK:
             raise ValueError(self.last_error())
         return out

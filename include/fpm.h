@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPM_ABI_VERSION 10
+#define FPM_ABI_VERSION 11
 
 /* status codes */
 #define FPM_OK 0
@@ -66,6 +66,17 @@ typedef struct fpm_params {
     double top_angle_step;    /* extension, no reference knob: the top-layer angle step in degrees replacing the
                                  derived atan(2 / max(w, h)) of TemplateMatcher.cpp:130 when > 0 (BASELINE
                                  configs[3] "1 degree step"); 0 = the reference's step (default)     */
+    int32_t stop_layer;       /* m_bStopLayer1, the MFC tool's fast mode (MatchToolDlg.cpp:936; default 0): nonzero stops
+                                 the pyramid descent at layer 1 instead of layer 0 (:949-956, :1033-1037).  The layer-1
+                                 ptLT is doubled in float (:951, :1035), no sub-pixel fit runs (:1013), the overlap
+                                 filter's rectangle is the layer-1 template size times two (:1053-1054) and the result
+                                 corners keep the level-0 size (:1080).  A coarse match: layer-1 precision for speed.
+                                 With a top layer of 0 the reference indexes vecPyramid[1] out of bounds; here that
+                                 case is the normal search (the stop layer is min(1, top layer))               */
+    int32_t bitwise_not;      /* m_ckBitwiseNot (MatchToolDlg.cpp:788-796; default 0): nonzero searches 255 - source,
+                                 the template as learned (patterns of inverted polarity).  The pyramid is built from
+                                 the inverted source (:790-791).  Both switches are honoured under both
+                                 semantics values, as tolerance_range is                                        */
 } fpm_params;
 
 /* One result; POD-identical to s_SingleTargetMatch (DataStructures.h:97-115): five cv::Point2d then two
@@ -141,7 +152,8 @@ int fpm_last_results(const fpm_ctx* ctx, fpm_result* out, int32_t cap_per_source
  * its refinement. */
 typedef struct fpm_candidate {
     double top_score;     /* dMatchScore at the top layer: the key of std::sort(compareScoreBig2Small) (:214) */
-    double x, y;          /* refined ptLT at layer 0 (the vecAllResult entry's pt, :346-356), when kept     */
+    double x, y;          /* refined ptLT at the stop layer, scaled to layer 0 (the vecAllResult entry's pt, :346-356;
+                             fpm_params.stop_layer: MatchToolDlg.cpp:951, :1035), when kept                  */
     double score;         /* refined dMatchScore (:312), when kept                                         */
     double angle;         /* refined dMatchAngle (sub-pixel estimate applied, :334-344), when kept          */
     int32_t angle_index;  /* index of the candidate's angle in the full top-layer angle list (:130-144)    */
@@ -160,7 +172,10 @@ int fpm_get_angle_shard(const fpm_ctx* ctx, int32_t* shard, int32_t* shards);
 int fpm_last_candidates(const fpm_ctx* ctx, int32_t source, fpm_candidate* out, int32_t cap, int32_t* n);
 /* The coupled tail of TemplateMatcher::match (:214, :262-432) over the candidate records of ONE source: `cand` is
  * the concatenation of every shard's records in shard order (push order; FPM_E_INVALID_ARG otherwise).  Host
- * only, no context or device needed; tmpl_w/tmpl_h = the learned template's level-0 size. */
+ * only, no context or device needed; tmpl_w/tmpl_h = the learned template's level-0 size.  With p->stop_layer set the
+ * overlap filter's rectangle is the layer-1 template size times two (MatchToolDlg.cpp:1053-1054) when the top layer is
+ * at least 1; having no context, the function derives the top layer from tmpl_w, tmpl_h and p->min_reduce_area by the
+ * rule the search uses (getTopLayer, TemplateMatcher.cpp:445-455), so p must carry the search's min_reduce_area. */
 int fpm_merge_candidates(const fpm_params* p, int32_t tmpl_w, int32_t tmpl_h, const fpm_candidate* cand, int32_t n,
                          fpm_result* out, int32_t cap, int32_t* n_results);
 
@@ -178,6 +193,10 @@ int fpm_op_pyr_down(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size
 int fpm_op_pyr_down2(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t src_stride,
                      uint8_t* dst1, size_t dst1_stride, uint8_t* dst2, size_t dst2_stride, int32_t seg_chunks,
                      int32_t chunk_rows);
+/* 255 - src (the MFC tool's `255 - m_matSrc`, MatchToolDlg.cpp:790) by the kernel a bitwise_not search runs over its
+ * staged sources (k_bitwise_not).  dst is w x h with row stride dst_stride. */
+int fpm_op_bitwise_not(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t src_stride,
+                       uint8_t* dst, size_t dst_stride);
 /* cv::warpAffine(INTER_LINEAR, BORDER_CONSTANT=border) with forward 2x3 matrix m (row-major), as called at
  * TemplateMatcher.cpp:175 (top layer) and :1089 (getRotatedROI, border 0). */
 int fpm_op_warp_affine(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t src_stride,
@@ -228,8 +247,8 @@ int fpm_template_level(const fpm_ctx* ctx, int32_t level, int32_t* w, int32_t* h
 
 /* --- instrumentation -------------------------------------------------------------------------------- */
 /* Per-search counters of the last fpm_match / fpm_match_staged call (source 0 for staged batches):
- *   [0] top-layer angles  [1] top-layer candidates  [2..2+L) live candidates entering layer L-1..0
- * Returns the number of entries written. */
+ *   [0] top-layer angles  [1] top-layer candidates  [2..2+L-stop) live candidates entering layer L-1..stop
+ * (stop = the stop layer: 0, or min(1, L) with fpm_params.stop_layer).  Returns the number of entries written. */
 int fpm_search_stats(const fpm_ctx* ctx, int64_t* stats, int32_t cap);
 /* SURVEY.md §8(d) algorithmic bytes of the last search, summed over its sources: B_pyr (pyramid in + out), B_top
  * (top-layer level read per angle + the f32 maps), B_ref (per live refinement ROI: the source footprint, the template
@@ -253,7 +272,8 @@ int fpm_search_bytes(const fpm_ctx* ctx, int64_t* b_pyr, int64_t* b_top, int64_t
 #define FPM_K_ROI_SMALL 9   /* k_roi_small    K6-K8 in one kernel for small templates             */
 #define FPM_K_CAND_STEP 10  /* k_cand_step    candidate step after k_roi_small                    */
 #define FPM_K_TOP_MAP 11    /* k_top_map: full maps of the jobs the list path left (fallback) */
-#define FPM_K_COUNT 12
+#define FPM_K_NOT 12        /* k_bitwise_not: 255 - source over the staged level 0 (fpm_params.bitwise_not) */
+#define FPM_K_COUNT 13
 int fpm_profile_enable(fpm_ctx* ctx, int32_t enable);
 int fpm_profile_reset(fpm_ctx* ctx);
 int fpm_profile_get(const fpm_ctx* ctx, int32_t kernel, double* total_ms, int64_t* launches,

@@ -22,6 +22,10 @@ FPM_E_DEVICE = -4
 FPM_E_CAPACITY = -5
 FPM_E_INTERNAL = -6
 
+# pixel formats of the device-memory entries (include/fpm.h FPM_FMT_*)
+(FMT_GRAY8, FMT_BGR8, FMT_RGB8, FMT_BGRA8, FMT_RGBA8, FMT_BGR8_PLANAR, FMT_RGB8_PLANAR) = range(7)
+FMT_COUNT = 7
+
 (K_PYR, K_TOP_WARP, K_TOP_NCC, K_TOP_NMS, K_CAND_INIT, K_ROI_TABLES, K_ROI_WARP, K_ROI_CORR, K_ROI_EVAL, K_ROI_SMALL,
  K_CAND_STEP, K_TOP_MAP, K_NOT) = range(13)
 # profiling index -> kernel (include/fpm.h FPM_K_*); top_ncc is k_top_mma (matrix-core top layer) where it applies, else
@@ -97,6 +101,10 @@ SIGNATURES = {
     "fpm_match": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(Result), C.c_int32,
                             C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "fpm_stage_sources": (C.c_int, [_P, C.POINTER(_U8P), C.c_int32, C.c_int32, C.c_int32, C.c_size_t]),
+    "fpm_stage_sources_device": (C.c_int, [_P, C.POINTER(_P), C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_size_t,
+                                           C.c_int32, _P]),
+    "fpm_match_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, C.c_int32, _P,
+                                   C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "fpm_match_staged": (C.c_int, [_P, C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_match_staged_launch": (C.c_int, [_P]),
     "fpm_match_staged_finish": (C.c_int, [_P, C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
@@ -104,6 +112,8 @@ SIGNATURES = {
     "fpm_op_pyr_down2": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, _U8P, C.c_size_t, _U8P, C.c_size_t,
                                    C.c_int32, C.c_int32]),
     "fpm_op_bitwise_not": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, _U8P, C.c_size_t]),
+    "fpm_op_to_gray": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, _U8P,
+                                 C.c_size_t]),
     "fpm_op_warp_affine": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_double), _U8P,
                                      C.c_int32, C.c_int32, C.c_size_t, C.c_int32]),
     "fpm_op_ncc_map": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32,
@@ -160,6 +170,24 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def hip_runtimes():
+    """Paths of the HIP runtime libraries (libamdhip64) mapped into this process.  Device pointers and stream handles
+    mean something only inside the runtime that made them, so the device-memory entries need the caller's framework and
+    libfpm_hip.so on ONE runtime.  A torch wheel bundles its own libamdhip64 under the system library's soname: imported
+    before libfpm_hip.so is loaded, the dynamic linker gives both the same copy; imported after it, the process ends up
+    with two runtimes and torch's tensors are foreign to the library."""
+    paths = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                path = line.split(None, 5)[-1].strip() if line.count("/") else ""
+                if os.path.basename(path).startswith("libamdhip64.so"):
+                    paths.add(os.path.realpath(path))
+    except OSError:
+        pass
+    return sorted(paths)
 
 
 def u8ptr(a):

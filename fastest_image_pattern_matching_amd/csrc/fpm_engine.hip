@@ -159,6 +159,11 @@ struct fpm_ctx {
     int shard = 0, shards = 1;
     std::vector<SrcLevel> src;
     DevBuf d_src;
+    // sources from device memory (stage_device_sources): the images' pointer table (pinned staging + device copy) and
+    // the event that orders the context's stream after the producer's (timing disabled, created on first use)
+    PinBuf h_imgtab;
+    DevBuf d_imgtab;
+    hipEvent_t in_ev = nullptr;
     // plan
     Plan plan;
     uint64_t plan_gen = ~0ull;
@@ -1661,6 +1666,98 @@ int upload_sources(fpm_ctx* ctx, const uint8_t* const* grays, int count, int w, 
     return FPM_OK;
 }
 
+// ---- sources already in device memory (fpm_stage_sources_device, fpm_match_device, fpm_op_to_gray) ----
+inline bool fmt_planar(int format) { return format == FPM_FMT_BGR8_PLANAR || format == FPM_FMT_RGB8_PLANAR; }
+
+// sizes, format and strides of a device-image description; no device call
+int check_image_desc(fpm_ctx* ctx, int count, int w, int h, size_t stride, size_t plane_stride, int format) {
+    if (count <= 0 || w <= 0 || h <= 0) { ctx->err = "bad sources: count, width and height must be positive"; return FPM_E_INVALID_ARG; }
+    const int bpp = stage_gray_bpp(format);
+    if (!bpp) { ctx->err = "unknown pixel format " + std::to_string(format); return FPM_E_INVALID_ARG; }
+    if (stride < (size_t)w * bpp) { ctx->err = "stride below width x bytes per pixel"; return FPM_E_INVALID_ARG; }
+    if (fmt_planar(format) && plane_stride < stride * (size_t)h) {
+        ctx->err = "plane stride below stride x height";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// bytes from an image's base to one past its last pixel
+size_t image_extent(int w, int h, size_t stride, size_t plane_stride, int format) {
+    const size_t plane = (size_t)(h - 1) * stride + (size_t)w * stage_gray_bpp(format);
+    return fmt_planar(format) ? 2 * plane_stride + plane : plane;
+}
+
+// Every image must be memory the context's device can read: device memory of that device, managed memory or
+// registered (pinned) host memory.  An unregistered host pointer makes hipPointerGetAttributes fail or report
+// hipMemoryTypeUnregistered, depending on the runtime; either way it is rejected and the sticky error cleared.  The
+// extent check against the allocation is best effort (a caching allocator's blocks are larger than its tensors), and
+// skipped where the runtime cannot name the allocation.
+int check_device_images(fpm_ctx* ctx, const void* const* imgs, int count, size_t extent) {
+    for (int i = 0; i < count; ++i) {
+        const std::string who = "source " + std::to_string(i);
+        if (!imgs[i]) { ctx->err = who + ": null pointer"; return FPM_E_INVALID_ARG; }
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, imgs[i]);
+        (void)hipGetLastError();
+        const bool ok = e == hipSuccess && ((at.type == hipMemoryTypeDevice && at.device == ctx->device) ||
+                                            at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost);
+        if (!ok) {
+            ctx->err = who + ": not memory the context's device can access (device " + std::to_string(ctx->device) +
+                       " memory, managed or registered host memory expected)";
+            return FPM_E_INVALID_ARG;
+        }
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)imgs[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        const size_t at_off = (size_t)((const char*)imgs[i] - (const char*)base);
+        if (at_off > size || extent > size - at_off) {
+            ctx->err = who + ": the image's byte extent leaves its allocation";
+            return FPM_E_INVALID_ARG;
+        }
+    }
+    return FPM_OK;
+}
+
+// upload_sources for images in device memory: checks, slab layout, ordering after the producer, pointer table, one
+// k_stage_gray launch on the context's stream (no wait).  Everything is checked before anything is enqueued or the
+// slab is re-laid out.  With fpm_params.bitwise_not set the kernel writes 255 - gray and the slab counts as inverted,
+// so apply_polarity has nothing to do for a search under the same setting.
+int stage_device_sources(fpm_ctx* ctx, const void* const* imgs, int count, int w, int h, size_t stride,
+                         size_t plane_stride, int format, hipStream_t producer) {
+    int rc = check_image_desc(ctx, count, w, h, stride, plane_stride, format);
+    if (rc != FPM_OK) return rc;
+    rc = check_device_images(ctx, imgs, count, image_extent(w, h, stride, plane_stride, format));
+    if (rc != FPM_OK) return rc;
+    rc = layout_sources(ctx, count, w, h);
+    if (rc != FPM_OK) return rc;
+    const bool invert = ctx->prm.bitwise_not != 0;
+    ctx->src_inverted = invert;
+    if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctx->in_ev, producer));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->in_ev, 0));
+    const size_t tab = sizeof(void*) * (size_t)count;
+    HIP_TRY(ctx->h_imgtab.ensure(tab));
+    HIP_TRY(ctx->d_imgtab.ensure(tab));
+    bool aligned = (stride & 15) == 0 && (!fmt_planar(format) || (plane_stride & 15) == 0);
+    for (int i = 0; i < count; ++i) {
+        ctx->h_imgtab.as<const void*>()[i] = imgs[i];
+        aligned = aligned && ((uintptr_t)imgs[i] & 15) == 0;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_imgtab.p, ctx->h_imgtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
+    const SrcLevel& l0 = ctx->src[0];
+    if (!launch_stage_gray(ctx->d_imgtab.as<const uint8_t*>(), count, w, h, stride, plane_stride, format, aligned,
+                           ctx->d_src.as<uint8_t>() + l0.off, l0.pitch, l0.img_bytes, invert, ctx->stream)) {
+        ctx->err = "source slab layout: level-0 rows not 16-byte aligned";
+        return FPM_E_INTERNAL;
+    }
+    HIP_TRY(hipGetLastError());
+    return FPM_OK;
+}
+
 }  // namespace
 
 // =========================================================================================================
@@ -1720,6 +1817,8 @@ int fpm_destroy(fpm_ctx* ctx) {
     for (DevBuf* b : {&ctx->d_rf_tab, &ctx->d_rf_tdesc, &ctx->d_rf_roi, &ctx->d_rf_rowsum, &ctx->d_rf_wsum, &ctx->d_rf_wsq})
         b->release();
     ctx->d_ov.release(); ctx->h_ov_in.release(); ctx->h_ov_out.release();
+    ctx->d_imgtab.release(); ctx->h_imgtab.release();
+    if (ctx->in_ev) (void)hipEventDestroy(ctx->in_ev);
     for (auto& k : ctx->kp)
         for (auto& e : k.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     (void)hipStreamDestroy(ctx->stream);
@@ -1921,6 +2020,67 @@ int fpm_match(fpm_ctx* ctx, const uint8_t* gray, int32_t w, int32_t h, size_t st
     return (int)r.size() > cap ? FPM_E_CAPACITY : FPM_OK;
 }
 
+// fpm_stage_sources for images already in device memory (no reference equivalent: match() takes a host cv::Mat,
+// TemplateMatcher.cpp:97-104)
+int fpm_stage_sources_device(fpm_ctx* ctx, const void* const* d_images, int32_t count, int32_t w, int32_t h,
+                             size_t stride, size_t plane_stride, int32_t format, void* producer_stream) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!d_images) { ctx->err = "bad sources: null image table"; return FPM_E_INVALID_ARG; }
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    int rc = check_image_desc(ctx, count, w, h, stride, plane_stride, format);
+    if (rc != FPM_OK) return rc;
+    rc = check_sizes(ctx, w, h);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool was_staged = ctx->staged;
+    ctx->staged = false;
+    rc = stage_device_sources(ctx, d_images, count, w, h, stride, plane_stride, format, (hipStream_t)producer_stream);
+    if (rc != FPM_OK) {
+        if (rc == FPM_E_INVALID_ARG) ctx->staged = was_staged;   // rejected before the slab was touched
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->staged = true;
+    return FPM_OK;
+}
+
+// fpm_match on an image already in device memory
+int fpm_match_device(fpm_ctx* ctx, const void* d_image, int32_t w, int32_t h, size_t stride, size_t plane_stride,
+                     int32_t format, void* producer_stream, fpm_result* out, int32_t cap, int32_t* n_results,
+                     double* seconds) {
+    if (!ctx || !n_results) return FPM_E_INVALID_ARG;
+    *n_results = 0;
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    ctx->cands.clear();   // as fpm_match: a failed call leaves no stale records behind
+    ctx->stats.clear();
+    ctx->results.clear();
+    if (!d_image) { ctx->err = "empty source"; return FPM_E_INVALID_ARG; }
+    int rc = check_image_desc(ctx, 1, w, h, stride, plane_stride, format);
+    if (rc != FPM_OK) return rc;
+    rc = check_sizes(ctx, w, h);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool was_staged = ctx->staged;
+    ctx->staged = false;   // the slab is re-laid out for this one source
+    // the staging is the reference's deep copy of the source (TemplateMatcher.cpp:104), made before its clock starts
+    // (:117), as fpm_match's upload is
+    rc = stage_device_sources(ctx, &d_image, 1, w, h, stride, plane_stride, format, (hipStream_t)producer_stream);
+    if (rc != FPM_OK) {
+        if (rc == FPM_E_INVALID_ARG) ctx->staged = was_staged;
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    rc = run_staged(ctx, ctx->results);
+    if (rc != FPM_OK) return rc;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    const std::vector<fpm_result>& r = ctx->results[0];
+    *n_results = (int32_t)r.size();
+    if (!r.empty() && seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
+    for (int i = 0; i < (int)r.size() && i < cap && out; ++i) out[i] = r[i];
+    return (int)r.size() > cap ? FPM_E_CAPACITY : FPM_OK;
+}
+
 int fpm_last_results(const fpm_ctx* ctx, fpm_result* out, int32_t cap, int32_t* n_results) {
     if (!ctx || !n_results) return FPM_E_INVALID_ARG;
     if (ctx->pending) return FPM_E_INVALID_ARG;
@@ -2070,6 +2230,44 @@ int fpm_op_bitwise_not(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, s
     HIP_TRY(hipMemcpy2DAsync(dst, ds, ctx->d_op_a.p, lv.pitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     prof_collect(ctx);
+    return FPM_OK;
+}
+
+// k_stage_gray over one image, host in / host out.  The source goes to the device byte for byte at its own address
+// modulo 16 and with its own strides, so the kernel form and the byte alignment are those of a device image laid out
+// like it.  The destination rows travel to the device and back over min(dst_stride, pitch) bytes (w for the last row,
+// which need not have more), so a byte the kernel wrote past w would show in the caller's buffer.
+int fpm_op_to_gray(fpm_ctx* ctx, const void* src, int32_t w, int32_t h, size_t ss, size_t plane_stride, int32_t format,
+                   int32_t invert, uint8_t* dst, size_t ds) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!src || !dst) { ctx->err = "bad image"; return FPM_E_INVALID_ARG; }
+    const int rc = check_image_desc(ctx, 1, w, h, ss, plane_stride, format);
+    if (rc != FPM_OK) return rc;
+    if (ds < (size_t)w) { ctx->err = "bad dst stride"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t extent = image_extent(w, h, ss, plane_stride, format);
+    const size_t mis = (uintptr_t)src & 15;
+    const SrcLevel lv = level_layout(w, h);   // the search's level-0 layout
+    HIP_TRY(ctx->d_op_a.ensure(mis + extent + 16));
+    HIP_TRY(ctx->d_op_b.ensure(lv.img_bytes));
+    HIP_TRY(ctx->d_op_job.ensure(sizeof(void*)));
+    const uint8_t* d_img = ctx->d_op_a.as<uint8_t>(mis);
+    uint8_t* d_dst = ctx->d_op_b.as<uint8_t>();
+    const size_t back = std::min(ds, (size_t)lv.pitch);
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_a.as<uint8_t>(mis), src, extent, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_job.p, &d_img, sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    if (h > 1) HIP_TRY(hipMemcpy2DAsync(d_dst, lv.pitch, dst, ds, back, h - 1, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_dst + (size_t)(h - 1) * lv.pitch, dst + (size_t)(h - 1) * ds, w, hipMemcpyHostToDevice, ctx->stream));
+    const bool aligned = mis == 0 && (ss & 15) == 0 && (!fmt_planar(format) || (plane_stride & 15) == 0);
+    if (!launch_stage_gray(ctx->d_op_job.as<const uint8_t*>(), 1, w, h, ss, plane_stride, format, aligned, d_dst, lv.pitch,
+                           lv.img_bytes, invert != 0, ctx->stream)) {
+        ctx->err = "level layout: rows not 16-byte aligned";
+        return FPM_E_INTERNAL;
+    }
+    HIP_TRY(hipGetLastError());
+    if (h > 1) HIP_TRY(hipMemcpy2DAsync(dst, ds, d_dst, lv.pitch, back, h - 1, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst + (size_t)(h - 1) * ds, d_dst + (size_t)(h - 1) * lv.pitch, w, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FPM_OK;
 }
 

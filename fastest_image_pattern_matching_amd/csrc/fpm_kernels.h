@@ -189,6 +189,18 @@ void launch_pyr_down2(const uint8_t* src, int sw, int sh, int sp, size_t s_img, 
 // bytes between w and the pitch are left alone).  Needs 16-byte aligned rows (img, pitch and img_bytes multiples of 16,
 // as level_layout gives them); returns false, launching nothing, otherwise
 bool launch_bitwise_not(uint8_t* img, int w, int h, int pitch, size_t img_bytes, int nimg, hipStream_t st);
+// k_stage_gray<FMT, ALIGNED>: the 8-bit gray plane of nimg caller-owned device images (d_imgs: device-side table of
+// their base pointers; w x h pixels of `format`, an FPM_FMT_* of include/fpm.h; `stride` bytes between rows,
+// `plane_stride` between the planes of a planar format) written to dst + image * img_bytes with row pitch `pitch`:
+// exactly the w bytes of each row, the bytes between w and the pitch are left alone.  invert: 255 - gray.
+// aligned: every image base, the stride and (planar) the plane stride are multiples of 16, so whole 16-pixel groups
+// load as 16-byte words; otherwise the general form runs (aligned dwords + byte alignment, any base and stride).
+// Needs 16-byte aligned destination rows, as launch_bitwise_not; returns false, launching nothing, otherwise or on an
+// unknown format
+bool launch_stage_gray(const uint8_t* const* d_imgs, int nimg, int w, int h, size_t stride, size_t plane_stride,
+                       int format, bool aligned, uint8_t* dst, int pitch, size_t img_bytes, bool invert,
+                       hipStream_t st);
+int stage_gray_bpp(int format);   // bytes per pixel within a row (1 for the planar formats); 0 = unknown format
 // zero / nzero: counters the search zeroes before its later kernels use them (block (0, 0) clears them), so the
 // graph carries no memset nodes
 void launch_warp(const WarpJob* jobs, int njobs, int max_pixels, hipStream_t st, int32_t* zero = nullptr,

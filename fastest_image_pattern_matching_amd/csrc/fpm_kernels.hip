@@ -2,6 +2,7 @@
 //
 //   K1  k_pyr_down_s  cv::pyrDown, one level per launch    (TemplateMatcher.cpp:55, :124)
 //       k_pyr_down2   two levels per launch (small inputs)
+//       k_stage_gray  device-memory sources (gray / BGR / RGB(A) / planar) -> level 0, imread's gray conversion
 //   K2  k_warp        cv::warpAffine INTER_LINEAR          (TemplateMatcher.cpp:175, :1089)
 //   K3+K4 k_ncc_map   matchTemplate(TM_CCORR) + CCOEFF_Denominator   (:177 -> :514, :523, :527-598)
 //   K5  k_nms         minMaxLoc + getNextMaxLoc / s_BlockMax (:179-210, :1196-1221, DataStructures.h:118-246)
@@ -27,6 +28,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "../../include/fpm.h"   // FPM_FMT_* (k_stage_gray)
 #include "fpm_kernels.h"
 #include "fpm_rrect.h"
 
@@ -701,6 +703,169 @@ bool launch_bitwise_not(uint8_t* img, int w, int h, int pitch, size_t img_bytes,
     const int64_t g = std::min((nrows + 3) / 4, (int64_t)2048);
     hipLaunchKernelGGL(k_bitwise_not, dim3((unsigned)g), dim3(256), 0, st, img, w, h, pitch, img_bytes, (int)nrows);
     return true;
+}
+
+// ============================================================================================== stage gray
+// The gray plane of caller-owned device images, written into level 0 of the source slab (fpm_stage_sources_device): the
+// device-side stand-in for upload_sources' hipMemcpy2DAsync, with the colour conversion of the reference's load path
+// folded in.  gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 in exact integers: cv::imread(IMREAD_GRAYSCALE)'s
+// conversion (images.bgr_to_gray; src/MatchToolDialog.cpp:314, 341), deliberately NOT
+// cv::cvtColor's 15-bit formula; the largest intermediate is 255 * 16384 + 8192, inside u32.
+// One wave per row (wave-strided over the nimg * h rows, as k_bitwise_not), one lane per 16 output pixels and turn: 16,
+// 48 or 64 source bytes (three 16-byte spans for the planar formats) in, one 16-byte store out.  Destination rows are
+// 16-byte aligned (launch_stage_gray checks); the ragged end of a row goes as dwords and then bytes, so the bytes between
+// w and the pitch keep their values.  Plain stores: the first pyramid launch reads the slab next.
+// Source side, two forms.  ALIGNED (bases, stride and plane stride multiples of 16): whole groups load as 16-byte words.
+// General (any base, any stride: a view into a wider tensor): each span is fetched as the aligned dwords that hold it
+// (16-byte loads at dword alignment for a whole group, plus one dword when the span is not dword aligned) and shifted
+// into place with v_alignbyte_b32; a dword is loaded only if it holds a byte of the image, so nothing outside the dwords
+// the image touches is read.  Both forms use the general fetch, dword by dword, for a row's last, partial group.
+constexpr int kBpp[FPM_FMT_COUNT] = {1, 3, 3, 4, 4, 1, 1};
+constexpr bool stage_planar(int f) { return f == FPM_FMT_BGR8_PLANAR || f == FPM_FMT_RGB8_PLANAR; }
+constexpr bool stage_red_first(int f) { return f == FPM_FMT_RGB8 || f == FPM_FMT_RGBA8 || f == FPM_FMT_RGB8_PLANAR; }
+int stage_gray_bpp(int format) { return format >= 0 && format < FPM_FMT_COUNT ? kBpp[format] : 0; }
+
+// d[0 .. NB/4) = the NB bytes at p, of which the first `valid` (1 .. NB) belong to the image (the rest: unspecified)
+template <int NB, bool ALIGNED>
+__device__ __forceinline__ void load_span(const uint8_t* p, int valid, uint32_t (&d)[NB / 4]) {
+    // the images' pointers come out of a table in memory: tell the compiler they are global addresses (device, managed
+    // or registered host memory all are), so the loads are global_load, not flat_load
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if (ALIGNED && valid >= NB) {
+#pragma unroll
+        for (int k = 0; k < NB / 16; ++k) {
+            const u32x4 v = ((const __attribute__((address_space(1))) u32x4*)p)[k];
+            d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+        }
+        return;
+    }
+    const uint32_t m = (uint32_t)(uintptr_t)p & 3u;
+    const __attribute__((address_space(1))) uint32_t* a = (const __attribute__((address_space(1))) uint32_t*)(p - m);
+    const int last = (int)m + valid;   // aligned dword k holds a byte of the span iff 4 k < last
+    uint32_t w[NB / 4 + 1];
+    if (valid >= NB) {
+        // a whole group: dwords 0 .. NB/4 - 1 all hold image bytes and go as 16-byte loads at dword alignment (legal
+        // for global memory), dword NB/4 is needed iff the span is not dword aligned
+        typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
+#pragma unroll
+        for (int k = 0; k < NB / 16; ++k) {
+            const u32x4 v = ((const __attribute__((address_space(1))) u32x4_a4*)a)[k];
+            w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+        }
+        w[NB / 4] = m ? a[NB / 4] : 0u;
+    } else {
+#pragma unroll
+        for (int k = 0; k <= NB / 4; ++k) w[k] = 4 * k < last ? a[k] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < NB / 4; ++k) d[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], m);   // bytes m .. m + 3 of hi:lo
+}
+
+__device__ __forceinline__ uint32_t span_byte(const uint32_t* d, int i) { return (d[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
+__device__ __forceinline__ uint32_t bgr_gray(uint32_t b, uint32_t g, uint32_t r) {
+    return (1868u * b + 9617u * g + 4899u * r + 8192u) >> 14;
+}
+
+template <int FMT, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_stage_gray(const uint8_t* const* __restrict__ imgs, int w, int h, size_t stride,
+                                                    size_t plane_stride, uint8_t* __restrict__ dst0, int pitch,
+                                                    size_t img_bytes, int nrows, uint32_t inv) {
+    constexpr int BPP = kBpp[FMT];
+    const int lane = threadIdx.x & 63;
+    const int nwaves = gridDim.x * 4;
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < nrows; row += nwaves) {
+        const int im = row / h, y = row - im * h;
+        const uint8_t* s = imgs[im] + (size_t)y * stride;
+        uint8_t* r = dst0 + (size_t)im * img_bytes + (size_t)y * pitch;
+        for (int x = lane << 4; x < w; x += 64 << 4) {
+            const int n = min(16, w - x);   // pixels of this group inside the row
+            uint32_t o[4];
+            if (stage_planar(FMT)) {
+                uint32_t c0[4], c1[4], c2[4];
+                load_span<16, ALIGNED>(s + x, n, c0);
+                load_span<16, ALIGNED>(s + plane_stride + x, n, c1);
+                load_span<16, ALIGNED>(s + 2 * plane_stride + x, n, c2);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const uint32_t a = span_byte(c0, 4 * k + i), g = span_byte(c1, 4 * k + i), c = span_byte(c2, 4 * k + i);
+                        v |= (stage_red_first(FMT) ? bgr_gray(c, g, a) : bgr_gray(a, g, c)) << (8 * i);
+                    }
+                    o[k] = v;
+                }
+            } else if (BPP == 1) {
+                load_span<16, ALIGNED>(s + x, n, o);
+            } else {
+                uint32_t d[4 * BPP];
+                load_span<16 * BPP, ALIGNED>(s + (size_t)x * BPP, n * BPP, d);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int b0 = (4 * k + i) * BPP;
+                        const uint32_t a = span_byte(d, b0), g = span_byte(d, b0 + 1), c = span_byte(d, b0 + 2);
+                        v |= (stage_red_first(FMT) ? bgr_gray(c, g, a) : bgr_gray(a, g, c)) << (8 * i);
+                    }
+                    o[k] = v;
+                }
+            }
+            uint8_t* p = r + x;
+            if (n == 16) {
+                *(uint4*)p = make_uint4(o[0] ^ inv, o[1] ^ inv, o[2] ^ inv, o[3] ^ inv);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t v = o[k] ^ inv;
+                    if (4 * k + 4 <= n) {
+                        *(uint32_t*)(p + 4 * k) = v;
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i)
+                            if (4 * k + i < n) p[4 * k + i] = (uint8_t)(v >> (8 * i));
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int FMT>
+static void launch_stage_gray_fmt(bool aligned, unsigned g, hipStream_t st, const uint8_t* const* d_imgs, int w, int h,
+                                  size_t stride, size_t plane_stride, uint8_t* dst, int pitch, size_t img_bytes,
+                                  int nrows, uint32_t inv) {
+    if (aligned)
+        hipLaunchKernelGGL((k_stage_gray<FMT, true>), dim3(g), dim3(256), 0, st, d_imgs, w, h, stride, plane_stride, dst,
+                           pitch, img_bytes, nrows, inv);
+    else
+        hipLaunchKernelGGL((k_stage_gray<FMT, false>), dim3(g), dim3(256), 0, st, d_imgs, w, h, stride, plane_stride, dst,
+                           pitch, img_bytes, nrows, inv);
+}
+
+bool launch_stage_gray(const uint8_t* const* d_imgs, int nimg, int w, int h, size_t stride, size_t plane_stride,
+                       int format, bool aligned, uint8_t* dst, int pitch, size_t img_bytes, bool invert,
+                       hipStream_t st) {
+    if (w <= 0 || h <= 0 || nimg <= 0) return true;
+    const int64_t nrows = (int64_t)nimg * h;
+    if (((uintptr_t)dst & 15) || (pitch & 15) || (img_bytes & 15) || pitch < w || nrows > (1 << 30)) return false;
+    // memory-bound: at most 8 workgroups per CU's worth of blocks (4 rows each per turn), the rest by the wave stride
+    const unsigned g = (unsigned)std::min((nrows + 3) / 4, (int64_t)2048);
+    const uint32_t inv = invert ? 0xffffffffu : 0u;
+#define FPM_STAGE_CASE(F) \
+    case F: launch_stage_gray_fmt<F>(aligned, g, st, d_imgs, w, h, stride, plane_stride, dst, pitch, img_bytes, (int)nrows, inv); return true
+    switch (format) {
+        FPM_STAGE_CASE(FPM_FMT_GRAY8);
+        FPM_STAGE_CASE(FPM_FMT_BGR8);
+        FPM_STAGE_CASE(FPM_FMT_RGB8);
+        FPM_STAGE_CASE(FPM_FMT_BGRA8);
+        FPM_STAGE_CASE(FPM_FMT_RGBA8);
+        FPM_STAGE_CASE(FPM_FMT_BGR8_PLANAR);
+        FPM_STAGE_CASE(FPM_FMT_RGB8_PLANAR);
+    }
+#undef FPM_STAGE_CASE
+    return false;
 }
 
 // ============================================================================================== K2

@@ -84,6 +84,109 @@ def _gray(img) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+_one_runtime = False   # torch and libfpm_hip.so were seen to share one HIP runtime (_lib.hip_runtimes, checked once)
+
+
+def device_layout(shape, strides, layout=None):
+    """How a uint8 image with this ``shape`` and these ``strides`` (in elements = bytes) lies in memory, for the
+    device-memory entries (fpm_match_device, fpm_stage_sources_device, fpm_op_to_gray).  Pure: works on the two tuples,
+    needs neither torch nor a device.  Returns ``(kind, height, width, channels, row_stride, plane_stride)`` with kind
+    "gray", "hwc" (interleaved) or "chw" (planar; plane_stride is 0 otherwise).
+
+    * 2-D (H, W) is gray: unit pixel stride.
+    * 3-D (H, W, C) with C in (3, 4), unit channel stride and pixel stride C is interleaved.
+    * 3-D (3, H, W) with unit pixel stride is planar: strides[1] is the row stride, strides[0] the plane stride.
+    * A shape both rules fit, (3, H, 3) or (3, H, 4), needs ``layout="hwc"`` or ``"chw"``.
+
+    Row strides wider than a row, plane strides wider than a plane and any base offset are fine (views into larger
+    tensors).  Everything else raises ValueError: a non-unit pixel or channel stride (a channel slice of a wider pixel,
+    a column step), negative strides, rows or planes that overlap.  The stride of a dimension of size 1 is not looked
+    at."""
+    shape = tuple(int(v) for v in shape)
+    strides = tuple(int(v) for v in strides)
+    if layout not in (None, "hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc', 'chw' or None, not {layout!r}")
+    if len(shape) != len(strides) or len(shape) not in (2, 3):
+        raise ValueError(f"expected a 2-D (H, W) or 3-D (H, W, C) / (3, H, W) image, got shape {shape}")
+    if any(n <= 0 for n in shape):
+        raise ValueError(f"empty image: shape {shape}")
+    if any(st < 0 for n, st in zip(shape, strides) if n > 1):
+        raise ValueError(f"negative strides {strides} are not supported")
+
+    def unit(d):
+        return shape[d] == 1 or strides[d] == 1
+
+    def at_least(d, least):   # a stride that must clear the extent below it; free when the dimension has one entry
+        return least if shape[d] == 1 else (strides[d] if strides[d] >= least else None)
+
+    if len(shape) == 2:
+        if layout is not None:
+            raise ValueError("layout applies to 3-D images only")
+        h, w = shape
+        if not unit(1):
+            raise ValueError(f"pixel stride {strides[1]} of a gray image must be 1 (no column steps or channel slices)")
+        row = at_least(0, w)
+        if row is None:
+            raise ValueError(f"row stride {strides[0]} below the width {w}")
+        return "gray", h, w, 1, row, 0
+
+    def hwc():
+        h, w, c = shape
+        if c not in (3, 4):
+            return f"{c} channels (3 or 4 expected)"
+        if not unit(2):
+            return f"channel stride {strides[2]} must be 1"
+        if w > 1 and strides[1] != c:
+            return f"pixel stride {strides[1]} must equal the channel count {c} (no channel slices of wider pixels)"
+        row = at_least(0, w * c)
+        if row is None:
+            return f"row stride {strides[0]} below width x channels = {w * c}"
+        return "hwc", h, w, c, row, 0
+
+    def chw():
+        c, h, w = shape
+        if c != 3:
+            return f"{c} planes (3 expected)"
+        if not unit(2):
+            return f"pixel stride {strides[2]} must be 1"
+        row = at_least(1, w)
+        if row is None:
+            return f"row stride {strides[1]} below the width {w}"
+        plane = at_least(0, row * h)
+        if plane is None:
+            return f"plane stride {strides[0]} below row stride x height = {row * h}"
+        return "chw", h, w, 3, row, plane
+
+    fits_hwc, fits_chw = shape[2] in (3, 4), shape[0] == 3
+    if layout is None and fits_hwc and fits_chw:
+        raise ValueError(f"shape {shape} reads as interleaved (H, W, C) and as planar (3, H, W): pass layout='hwc' or "
+                         f"layout='chw'")
+    if layout is None and not (fits_hwc or fits_chw):
+        raise ValueError(f"shape {shape} is neither (H, W, 3 or 4) nor (3, H, W)")
+    got = hwc() if (layout == "hwc" or (layout is None and fits_hwc)) else chw()
+    if isinstance(got, str):
+        raise ValueError(f"shape {shape}, strides {strides}: {got}")
+    return got
+
+
+def device_format(kind: str, channels: int, channel_order: str = "bgr") -> int:
+    """The FPM_FMT_* of a device_layout kind and a channel order ("bgr" or "rgb"; "bgra" / "rgba" say the same for four
+    channels).  The order does not matter for gray."""
+    order = str(channel_order).lower()
+    if order not in ("bgr", "rgb", "bgra", "rgba"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', not {channel_order!r}")
+    if kind == "gray":
+        return L.FMT_GRAY8
+    rgb = order.startswith("rgb")
+    if len(order) == 4 and (kind != "hwc" or channels != 4):
+        raise ValueError(f"channel_order {channel_order!r} needs a four-channel interleaved image")
+    if kind == "chw":
+        return L.FMT_RGB8_PLANAR if rgb else L.FMT_BGR8_PLANAR
+    if channels == 4:
+        return L.FMT_RGBA8 if rgb else L.FMT_BGRA8
+    return L.FMT_RGB8 if rgb else L.FMT_BGR8
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -93,6 +196,7 @@ class TemplateMatcher:
         rc = self._lib.fpm_create(device, C.byref(self._ctx))
         if rc != L.FPM_OK:
             raise RuntimeError(f"fpm_create(device={device}) failed with {rc}: no gfx950 device / HIP runtime")
+        self._device = int(device)
         self._params = L.Params()
         self._lib.fpm_params_default(C.byref(self._params))
         self._last_time = 0.0
@@ -177,6 +281,86 @@ class TemplateMatcher:
         if rc != L.FPM_OK:
             raise ValueError(f"fpm_stage_sources failed with {rc}: {self.last_error()}")
         self._staged = len(gs)
+
+    # -- sources already in device memory (fpm_match_device / fpm_stage_sources_device) ----------------------------
+    def _device_image(self, img, channel_order, layout):
+        """(data pointer, height, width, row stride, plane stride, FPM_FMT_*) of a uint8 torch tensor on this
+        context's device, as it lies in memory: no copy is made, a layout the kernel cannot read raises instead."""
+        import torch   # only the device-memory entries need torch
+
+        if not isinstance(img, torch.Tensor):
+            raise TypeError(f"expected a torch.Tensor on cuda:{self._device}, got {type(img).__name__}")
+        if img.dtype != torch.uint8:
+            raise TypeError(f"expected a uint8 tensor, got {img.dtype}")
+        if img.device.type != "cuda":
+            raise ValueError(f"expected a tensor on cuda:{self._device}, got one on {img.device} (match() takes host images)")
+        if img.device.index != self._device:
+            raise ValueError(f"tensor on {img.device}, context on cuda:{self._device}")
+        global _one_runtime
+        if not _one_runtime:
+            rts = L.hip_runtimes()
+            if len(rts) > 1:
+                raise RuntimeError("torch and libfpm_hip.so run on separate HIP runtimes (" + ", ".join(rts) + "), so "
+                                   "the tensor's pointer and stream are foreign to the library: import torch before "
+                                   "the first TemplateMatcher is created (before libfpm_hip.so is loaded)")
+            _one_runtime = True
+        kind, h, w, ch, row, plane = device_layout(tuple(img.shape), tuple(img.stride()), layout)
+        return img.data_ptr(), h, w, row, plane, device_format(kind, ch, channel_order)
+
+    def _producer_stream(self, stream):
+        import torch
+
+        if stream is None:
+            return torch.cuda.current_stream(torch.device("cuda", self._device)).cuda_stream
+        return int(getattr(stream, "cuda_stream", stream))
+
+    def match_device(self, img, channel_order: str = "bgr", layout=None, stream=None) -> List[SingleTargetMatch]:
+        """match() on a frame already in device memory: a uint8 torch tensor on this context's device, gray (H, W),
+        interleaved (H, W, 3 or 4) or planar (3, H, W), contiguous or a view (device_layout has the rules; nothing is
+        copied or made contiguous).  Colour is converted as the reference's load path converts it
+        (cv::imread(IMREAD_GRAYSCALE), images.bgr_to_gray); channel_order names the order of the channels in memory.
+        stream is the stream the frame was written on (a torch stream or a raw handle; None = torch's current stream
+        of the device): the search is ordered after it, no host synchronisation is needed."""
+        ptr, h, w, row, plane, fmt = self._device_image(img, channel_order, layout)
+        prod = self._producer_stream(stream)
+        self._staged = 0
+        if not self.isPatternLearned():
+            # as match(): an argument-less fpm_match fails its checks and drops the previous search's records
+            self._lib.fpm_match(self._ctx, None, 0, 0, 0, None, 0, C.byref(C.c_int32()), None)
+            return []
+        self._push()
+        out = (L.Result * self._cap)()
+        n = C.c_int32()
+        sec = C.c_double(self._last_time)
+        rc = self._check(self._lib.fpm_match_device(self._ctx, ptr, w, h, row, plane, fmt, prod, out, self._cap,
+                                                    C.byref(n), C.byref(sec)), "match_device")
+        if rc == L.FPM_E_CAPACITY:   # fetch the results already computed into a larger buffer (no second search)
+            self._cap = max(self._cap * 2, n.value)
+            out = (L.Result * self._cap)()
+            rc = self._check(self._lib.fpm_last_results(self._ctx, out, self._cap, C.byref(n)), "last_results")
+        if rc != L.FPM_OK:
+            return []
+        self._last_time = sec.value
+        return [SingleTargetMatch.from_c(out[i]) for i in range(n.value)]
+
+    def stage_device(self, imgs, channel_order: str = "bgr", layout=None, stream=None):
+        """stage() for frames already in device memory (fpm_stage_sources_device): tensors as match_device takes them,
+        all of one size, format and strides (separate allocations and views are fine).  match_staged* then work as
+        after stage()."""
+        descs = [self._device_image(t, channel_order, layout) for t in imgs]
+        if not descs:
+            raise ValueError("no sources")
+        if any(d[1:] != descs[0][1:] for d in descs):
+            raise ValueError("all staged sources must have the same size, format and strides")
+        _, h, w, row, plane, fmt = descs[0]
+        prod = self._producer_stream(stream)
+        self._push()
+        ptrs = (C.c_void_p * len(descs))(*[d[0] for d in descs])
+        rc = self._check(self._lib.fpm_stage_sources_device(self._ctx, ptrs, len(descs), w, h, row, plane, fmt, prod),
+                         "stage_device")
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_stage_sources_device failed with {rc}: {self.last_error()}")
+        self._staged = len(descs)
 
     def match_staged(self) -> List[List[SingleTargetMatch]]:
         counts, res = self.match_staged_array()
@@ -339,6 +523,27 @@ class TemplateMatcher:
         out = np.zeros((h, w), np.uint8)
         rc = self._check(self._lib.fpm_op_bitwise_not(self._ctx, L.u8ptr(g), w, h, g.strides[0], L.u8ptr(out),
                                                       out.strides[0]), "bitwise_not")
+        if rc != L.FPM_OK:
+            raise ValueError(self.last_error())
+        return out
+
+    def to_gray(self, img, channel_order: str = "bgr", layout=None, invert: bool = False, dst=None) -> np.ndarray:
+        """The gray plane match_device / stage_device search, for a host array (fpm_op_to_gray): the staging kernel over
+        one image.  img is a uint8 numpy array laid out as device_layout accepts (views go down as they are, with their
+        strides and their base address modulo 16, so the kernel takes the path it would take on the device); invert
+        gives 255 - gray.  dst (optional): a 2-D uint8 array with unit pixel stride to write into; its bytes between
+        the width and its row stride keep their values."""
+        a = np.asarray(img)
+        if a.dtype != np.uint8:
+            raise TypeError(f"expected a uint8 array, got {a.dtype}")
+        kind, h, w, ch, row, plane = device_layout(a.shape, a.strides, layout)
+        fmt = device_format(kind, ch, channel_order)
+        out = np.zeros((h, w), np.uint8) if dst is None else dst
+        if out.dtype != np.uint8 or out.shape != (h, w) or (w > 1 and out.strides[1] != 1) or (h > 1 and out.strides[0] < w):
+            raise ValueError(f"dst must be a ({h}, {w}) uint8 array with unit pixel stride")
+        rc = self._check(self._lib.fpm_op_to_gray(self._ctx, a.ctypes.data, w, h, row, plane, fmt, 1 if invert else 0,
+                                                  L.u8ptr(out), out.strides[0] if h > 1 else max(out.strides[0], w)),
+                         "to_gray")
         if rc != L.FPM_OK:
             raise ValueError(self.last_error())
         return out

@@ -9,6 +9,7 @@
  *   - Images are 8-bit single-channel (CV_8UC1) row-major with an explicit row stride in bytes, exactly
  *     what `cv::imread(..., IMREAD_GRAYSCALE)` yields (src/MatchToolDialog.cpp:314, 341).
  *   - Host image pointers are copied to device memory inside the call; the library never retains them.
+ *     (fpm_stage_sources_device / fpm_match_device take images that already lie in device memory, gray or colour.)
  *   - Every function returns an `int` status: FPM_OK (0) or a negative FPM_E_* code.  "No match" is
  *     FPM_OK with *n_results == 0, mirroring the reference's empty vector (TemplateMatcher.cpp:99-114, 398).
  *   - One context per host thread; a context is bound to one HIP device and owns one HIP stream.
@@ -140,6 +141,50 @@ int fpm_match_staged_finish(fpm_ctx* ctx, fpm_result* out, int32_t cap_per_sourc
  * the results already computed instead of searching again. */
 int fpm_last_results(const fpm_ctx* ctx, fpm_result* out, int32_t cap_per_source, int32_t* n_results);
 
+/* --- sources already in device memory (no reference equivalent: match() takes a host cv::Mat,
+ * TemplateMatcher.cpp:97-104) -------------------------------------------------------------------------------
+ * Frames a GPU decoder, a torch pipeline or a camera SDK left in HBM go straight into the context's source slab: one
+ * kernel (k_stage_gray) reads the caller's device images and writes the 8-bit gray plane the search runs on; nothing
+ * crosses the host.  Added without a change of FPM_ABI_VERSION: the entries are additive, no existing entry or struct
+ * changes, so callers built against the earlier header are unaffected.
+ *
+ * Pixel formats.  Colour is converted as cv::imread(IMREAD_GRAYSCALE) converts a decoded colour file (the way the
+ * reference loads its images, src/MatchToolDialog.cpp:314, 341): gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 in
+ * exact integers.  This is deliberately NOT cv::cvtColor's 15-bit formula
+ * ((3735 B + 19235 G + 9798 R + 16384) >> 15), whose rounding differs on some pixels: a colour frame staged
+ * from device memory gives the gray plane of the same frame saved as a BMP and loaded by the reference. */
+#define FPM_FMT_GRAY8 0         /* 1 B per pixel                                                        */
+#define FPM_FMT_BGR8 1          /* 3 B per pixel, interleaved B G R (cv::Mat CV_8UC3 order)             */
+#define FPM_FMT_RGB8 2          /* 3 B per pixel, interleaved R G B                                     */
+#define FPM_FMT_BGRA8 3         /* 4 B per pixel, interleaved B G R A, alpha ignored                    */
+#define FPM_FMT_RGBA8 4         /* 4 B per pixel, interleaved R G B A, alpha ignored                    */
+#define FPM_FMT_BGR8_PLANAR 5   /* three w x h planes, B then G then R, plane_stride bytes apart        */
+#define FPM_FMT_RGB8_PLANAR 6   /* three w x h planes, R then G then B, plane_stride bytes apart        */
+#define FPM_FMT_COUNT 7
+/* fpm_stage_sources for `count` images in device memory.  d_images is a HOST array of `count` device pointers; every
+ * image is width x height pixels of `format` with `stride` bytes between rows (>= width x bytes per pixel; any value,
+ * any base alignment: views into larger buffers are fine) and, for the planar formats, plane_stride bytes between
+ * planes (>= stride x height; ignored otherwise).  With fpm_params.bitwise_not set at the time of the call the kernel
+ * writes 255 - gray and the search launches no k_bitwise_not; the polarity is tracked as for fpm_stage_sources, so
+ * the parameter may be flipped between searches of the staged batch.
+ * producer_stream is the hipStream_t on which the images were, or are being, written (NULL = the null stream).  The
+ * context's own stream is non-blocking, so it is ordered neither after the caller's stream nor after the null stream
+ * by itself: the call records a context-owned event on producer_stream and makes its stream wait for it.  The caller
+ * needs no host synchronisation before the call; the call returns once the images have been read, so the caller may
+ * overwrite them afterwards.
+ * Every pointer must be device memory of the context's device, or memory that device can access (managed or
+ * registered host memory): FPM_E_INVALID_ARG otherwise, as for a bad size, stride or format.  The image's byte extent
+ * is also checked against its allocation -- a best-effort guard, not a guarantee: a caching allocator's blocks are
+ * larger than the tensors carved from them. */
+int fpm_stage_sources_device(fpm_ctx* ctx, const void* const* d_images, int32_t count, int32_t width, int32_t height,
+                             size_t stride, size_t plane_stride, int32_t format, void* producer_stream);
+/* fpm_match on one image in device memory: arguments as fpm_stage_sources_device (d_image is the device pointer
+ * itself), results, capacity handling and *seconds as fpm_match.  The staging is the reference's deep copy of the
+ * source (TemplateMatcher.cpp:104), so the clock of *seconds starts once it has landed (:117). */
+int fpm_match_device(fpm_ctx* ctx, const void* d_image, int32_t width, int32_t height, size_t stride,
+                     size_t plane_stride, int32_t format, void* producer_stream, fpm_result* out, int32_t cap,
+                     int32_t* n_results, double* seconds);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent
@@ -197,6 +242,15 @@ int fpm_op_pyr_down2(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, siz
  * staged sources (k_bitwise_not).  dst is w x h with row stride dst_stride. */
 int fpm_op_bitwise_not(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t src_stride,
                        uint8_t* dst, size_t dst_stride);
+/* The gray plane fpm_stage_sources_device writes for one image, host in / host out like the other operators (no
+ * reference equivalent: match() takes a host cv::Mat, TemplateMatcher.cpp:97-104; the conversion is that of
+ * cv::imread(IMREAD_GRAYSCALE), src/MatchToolDialog.cpp:314, 341).  src is copied to device memory byte for byte,
+ * keeping its row stride and its address modulo 16, so the kernel (k_stage_gray) takes the path it would take for a
+ * device image at that alignment; format, src_stride and plane_stride as fpm_stage_sources_device; invert != 0 gives
+ * 255 - gray.  dst is w x h with row stride dst_stride; the bytes between w and dst_stride come back as the kernel
+ * left them (untouched). */
+int fpm_op_to_gray(fpm_ctx* ctx, const void* src, int32_t w, int32_t h, size_t src_stride, size_t plane_stride,
+                   int32_t format, int32_t invert, uint8_t* dst, size_t dst_stride);
 /* cv::warpAffine(INTER_LINEAR, BORDER_CONSTANT=border) with forward 2x3 matrix m (row-major), as called at
  * TemplateMatcher.cpp:175 (top layer) and :1089 (getRotatedROI, border 0). */
 int fpm_op_warp_affine(fpm_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, size_t src_stride,

@@ -27,18 +27,21 @@ FPM_E_INTERNAL = -6
 FMT_COUNT = 7
 
 (K_PYR, K_TOP_WARP, K_TOP_NCC, K_TOP_NMS, K_CAND_INIT, K_ROI_TABLES, K_ROI_WARP, K_ROI_CORR, K_ROI_EVAL, K_ROI_SMALL,
- K_CAND_STEP, K_TOP_MAP, K_NOT) = range(13)
+ K_CAND_STEP, K_TOP_MAP, K_NOT, K_PATCH) = range(14)
 # profiling index -> kernel (include/fpm.h FPM_K_*); top_ncc is k_top_mma (matrix-core top layer) where it applies, else
 # k_ncc_tile for templates up to 128 x 64; top_map = k_top_map, the matrix-core form's fallback (full maps for the jobs
-# its lists left); bitwise_not = k_bitwise_not, 255 - source over the staged level 0 (Params.bitwise_not)
+# its lists left); bitwise_not = k_bitwise_not, 255 - source over the staged level 0 (Params.bitwise_not); patch_warp =
+# the match patches' launch (k_patch_warp, or k_warp under FPM_PATCH_FORM_WARP), never part of a search
 KERNEL_NAMES = ["pyr_down", "top_warp", "top_ncc", "top_nms", "cand_init", "roi_tables", "roi_warp", "roi_corr",
-                "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not"]
+                "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not", "patch_warp"]
+# fpm_set_patch_form
+PATCH_FORM_TILED, PATCH_FORM_WARP = 0, 1
 KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_warp"],
                   "top_ncc": ["k_top_mma", "k_ncc_tile", "k_ncc_map"],
                   "top_nms": ["k_nms_greedy", "k_nms"], "cand_init": ["k_cand_init"], "roi_tables": ["k_roi_tables"],
                   "roi_warp": ["k_roi_warp3", "k_roi_warp"], "roi_corr": ["k_roi_corr"], "roi_eval": ["k_roi_eval"],
                   "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"],
-                  "bitwise_not": ["k_bitwise_not"]}
+                  "bitwise_not": ["k_bitwise_not"], "patch_warp": ["k_patch_warp"]}
 
 
 class Params(C.Structure):
@@ -75,6 +78,12 @@ class Candidate(C.Structure):
     _fields_ = [("top_score", C.c_double), ("x", C.c_double), ("y", C.c_double), ("score", C.c_double),
                 ("angle", C.c_double), ("angle_index", C.c_int32), ("peak_rank", C.c_int32), ("source", C.c_int32),
                 ("kept", C.c_int32)]
+
+
+class PatchRect(C.Structure):
+    """fpm_patch_rect — a patch's rectangle in template coordinates."""
+
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
 class RoiRecord(C.Structure):
@@ -131,6 +140,16 @@ SIGNATURES = {
     "fpm_get_angle_shard": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "fpm_last_candidates": (C.c_int, [_P, C.c_int32, C.POINTER(Candidate), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_last_results": (C.c_int, [_P, C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_patch_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_double)]),
+    "fpm_last_patches": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, _U8P, C.c_size_t, C.c_size_t, C.c_int32,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "fpm_last_patches_device": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, _P, C.c_size_t, C.c_size_t, C.c_int32,
+                                          C.POINTER(C.c_int32), _P]),
+    "fpm_patches_at": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_double), C.c_int32, _U8P, C.c_size_t, C.c_size_t,
+                                 C.POINTER(C.c_double)]),
+    "fpm_set_patch_form": (C.c_int, [_P, C.c_int32]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

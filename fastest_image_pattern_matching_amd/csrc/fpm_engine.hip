@@ -133,6 +133,13 @@ struct Plan {
     }
 };
 
+// The pose a result was built from (its vecAllResult entry: the f32 point, dMatchAngle), kept next to the results for
+// fpm_last_patches: the converted fpm_result fields do not give it back under FPM_SEMANTICS_MFC.
+struct RawPose {
+    float x, y;
+    double angle;
+};
+
 struct KProf {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     size_t used = 0;
@@ -196,6 +203,14 @@ struct fpm_ctx {
     // per-source candidate records of the last search (collect_candidates; fpm_match_*candidates)
     std::vector<std::vector<fpm_candidate>> cands;
     std::vector<std::vector<fpm_result>> results;   // of the last search, per source (fpm_last_results)
+    std::vector<std::vector<RawPose>> poses;        // the results' raw poses, same shape (fpm_last_patches)
+    // match patches (fpm_last_patches* / fpm_patches_at)
+    bool src_valid = false;   // level 0 of the slab holds staged sources (not so after a new template or a failed staging)
+    bool searched = false;    // a search has finished on them since they were staged
+    int patch_form = FPM_PATCH_FORM_TILED;
+    PinBuf h_patchtab;        // job table: pinned staging + device copy; tab_ev = the last staging copy has left h_patchtab
+    DevBuf d_patchtab, d_patch;   // d_patch: the patches of the host variants, before they are copied out
+    hipEvent_t tab_ev = nullptr, out_ev = nullptr;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -778,6 +793,8 @@ int layout_sources(fpm_ctx* ctx, int count, int w, int h) {
         return FPM_E_INVALID_ARG;
     }
     ctx->S = count; ctx->sw = w; ctx->sh = h; ctx->src_L = L;
+    ctx->src_valid = false;   // until the pixels are on their way (upload_sources, stage_device_sources)
+    ctx->searched = false;
     ctx->src.assign(L + 1, {});
     size_t off = 0;
     int lw = w, lh = h;
@@ -1379,9 +1396,12 @@ static bool overlap_filter_device(fpm_ctx* ctx, std::vector<HostMatch>& v, doubl
 
 // Returns false when `cand` is not in push order (angle_index ascending, peak_rank 0, 1, ... within an angle).
 // stop: the search's stop layer (the plan's), or -1 to derive it from prm (fpm_merge_candidates has no plan).
+// poses (optional): the raw pose of every result, in result order.
 bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candidate* cand, int n,
-                      std::vector<fpm_result>& out, fpm_ctx* dev_ctx, int stop = -1) {
+                      std::vector<fpm_result>& out, fpm_ctx* dev_ctx, int stop = -1,
+                      std::vector<RawPose>* poses = nullptr) {
     out.clear();
+    if (poses) poses->clear();
     for (int i = 0; i < n; ++i) {
         const bool first = i == 0 || cand[i].angle_index != cand[i - 1].angle_index;
         if (first ? (cand[i].peak_rank != 0 || (i > 0 && cand[i].angle_index < cand[i - 1].angle_index))
@@ -1470,6 +1490,7 @@ bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candida
             if (o.angle > 180) o.angle -= 360;
             o.score = m.score;
             out.push_back(o);
+            if (poses) poses->push_back({(float)m.ptx, (float)m.pty, m.angle});
             if ((int)out.size() == prm.max_pos) break;   // at most MaxPos rows (:1115-1116)
         }
         return true;
@@ -1487,6 +1508,7 @@ bool merge_candidates(const fpm_params& prm, int t0w, int t0h, const fpm_candida
         o.rb_x = rb.x; o.rb_y = rb.y; o.lb_x = lb.x; o.lb_y = lb.y;
         o.cx = c.x; o.cy = c.y; o.angle = m.angle; o.score = m.score;
         out.push_back(o);
+        if (poses) poses->push_back({lt.x, lt.y, m.angle});
     }
     return true;
 }
@@ -1584,11 +1606,13 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
         for (int li = 0; li < n0; ++li) pos[ids[li]] = li;
     }
     ctx->cands.assign(P.S, {});
+    ctx->poses.assign(P.S, {});
+    ctx->searched = true;
     for (int s = 0; s < P.S; ++s) {
         collect_candidates(ctx, s, pos, ctx->cands[s]);
         if (merge)
             merge_candidates(ctx->run_prm, ctx->tmpl[0].w, ctx->tmpl[0].h, ctx->cands[s].data(), (int)ctx->cands[s].size(),
-                             results[s], ctx, P.stop);
+                             results[s], ctx, P.stop, &ctx->poses[s]);
     }
     // stats: [angles, top candidates, live entering layer L-1 .. stop] (totals over the batch)
     const char* h = P.h_out.as<char>();
@@ -1663,6 +1687,7 @@ int upload_sources(fpm_ctx* ctx, const uint8_t* const* grays, int count, int w, 
     for (int s = 0; s < count; ++s)
         HIP_TRY(hipMemcpy2DAsync(ctx->d_src.as<uint8_t>() + l0.off + l0.img_bytes * s, l0.pitch, grays[s], stride, w, h,
                                  hipMemcpyHostToDevice, ctx->stream));
+    ctx->src_valid = true;
     return FPM_OK;
 }
 
@@ -1693,9 +1718,9 @@ size_t image_extent(int w, int h, size_t stride, size_t plane_stride, int format
 // hipMemoryTypeUnregistered, depending on the runtime; either way it is rejected and the sticky error cleared.  The
 // extent check against the allocation is best effort (a caching allocator's blocks are larger than its tensors), and
 // skipped where the runtime cannot name the allocation.
-int check_device_images(fpm_ctx* ctx, const void* const* imgs, int count, size_t extent) {
+int check_device_images(fpm_ctx* ctx, const void* const* imgs, int count, size_t extent, const char* what = "source") {
     for (int i = 0; i < count; ++i) {
-        const std::string who = "source " + std::to_string(i);
+        const std::string who = std::string(what) + " " + std::to_string(i);
         if (!imgs[i]) { ctx->err = who + ": null pointer"; return FPM_E_INVALID_ARG; }
         hipPointerAttribute_t at{};
         const hipError_t e = hipPointerGetAttributes(&at, imgs[i]);
@@ -1755,6 +1780,159 @@ int stage_device_sources(fpm_ctx* ctx, const void* const* imgs, int count, int w
         return FPM_E_INTERNAL;
     }
     HIP_TRY(hipGetLastError());
+    ctx->src_valid = true;
+    return FPM_OK;
+}
+
+// ---- match patches (fpm_last_patches*, fpm_patches_at) ----
+struct PatchPose {
+    int32_t src;
+    RawPose pose;
+};
+
+// the forward matrix of one patch: glibc trig of angle * D2R on the host, as for every other matrix of the search
+void patch_forward(int sw, int sh, const RawPose& p, int rx, int ry, double M[6]) {
+    const double rad = p.angle * kD2R;
+    patch_matrix(sw, sh, f2(p.x, p.y), std::cos(rad), std::sin(rad), rx, ry, M);
+}
+
+int patch_state(fpm_ctx* ctx, bool need_search) {
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (!ctx->learned) { ctx->err = "template not learned"; return FPM_E_NOT_LEARNED; }
+    if (!ctx->src_valid || ctx->S <= 0 || ctx->src.empty() || !ctx->d_src.p) {
+        ctx->err = "no staged sources to take patches from";
+        return FPM_E_INVALID_ARG;
+    }
+    if (need_search && !ctx->searched) {
+        ctx->err = "no search has run since the sources were staged";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+int patch_rect(fpm_ctx* ctx, const fpm_patch_rect* rect, fpm_patch_rect* r) {
+    *r = rect ? *rect : fpm_patch_rect{0, 0, ctx->tmpl[0].w, ctx->tmpl[0].h};
+    constexpr int kMaxOrigin = 1 << 20;
+    if (r->w < 1 || r->h < 1 || r->w > 8192 || r->h > 8192 || r->x < -kMaxOrigin || r->x > kMaxOrigin ||
+        r->y < -kMaxOrigin || r->y > kMaxOrigin) {
+        ctx->err = "bad patch rectangle: width and height must be 1 .. 8192, |x| and |y| at most 2^20";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// the poses of the last search's results: of one source, or of all in source order
+int last_poses(fpm_ctx* ctx, int source, std::vector<PatchPose>& poses) {
+    if (source < -1 || source >= ctx->S) { ctx->err = "bad source index"; return FPM_E_INVALID_ARG; }
+    for (int s = 0; s < (int)ctx->poses.size() && s < ctx->S; ++s)
+        if (source < 0 || s == source)
+            for (const RawPose& p : ctx->poses[s]) poses.push_back({s, p});
+    return FPM_OK;
+}
+
+int check_patch_out(fpm_ctx* ctx, const void* out, const fpm_patch_rect& r, size_t row_stride, size_t patch_stride) {
+    if (!out) { ctx->err = "null patch buffer"; return FPM_E_INVALID_ARG; }
+    if (row_stride < (size_t)r.w || row_stride > (size_t)INT32_MAX || patch_stride / (size_t)r.h < row_stride) {
+        ctx->err = "bad patch strides: row_stride >= width and patch_stride >= row_stride x height expected";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// Job table and the one launch for `poses` on the context's stream (no wait): patch i goes to d_out + i * patch_stride.
+// matrices (optional): the forward matrices, [n][6].
+int enqueue_patches(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* d_out,
+                    size_t row_stride, size_t patch_stride, double* matrices) {
+    const int n = (int)poses.size();
+    const SrcLevel& l0 = ctx->src[0];
+    const bool tiled = ctx->patch_form == FPM_PATCH_FORM_TILED;
+    const size_t tab = std::max(sizeof(PatchJob), sizeof(WarpJob)) * (size_t)n;
+    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table (long done as a rule)
+    HIP_TRY(ctx->h_patchtab.ensure(tab));
+    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    const uint8_t* level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    for (int i = 0; i < n; ++i) {
+        const PatchPose& p = poses[i];
+        if (p.src < 0 || p.src >= ctx->S) { ctx->err = "pose " + std::to_string(i) + ": bad source index"; return FPM_E_INVALID_ARG; }
+        if (!std::isfinite(p.pose.x) || !std::isfinite(p.pose.y) || !std::isfinite(p.pose.angle)) {
+            ctx->err = "pose " + std::to_string(i) + ": not finite";
+            return FPM_E_INVALID_ARG;
+        }
+        double M[6];
+        patch_forward(ctx->sw, ctx->sh, p.pose, r.x, r.y, M);
+        if (matrices) std::copy(M, M + 6, matrices + 6 * (size_t)i);
+        invert_affine(M);
+        // the samplers' coordinates are AB_BITS fixed point in 32 bits: the patch's corners bound every pixel's
+        for (int k = 0; k < 4; ++k) {
+            const double x = (k & 1) ? r.w - 1 : 0, y = (k & 2) ? r.h - 1 : 0;
+            const double sx = M[0] * x + M[1] * y + M[2], sy = M[3] * x + M[4] * y + M[5];
+            if (!(std::fabs(sx) < 1048576.0 && std::fabs(sy) < 1048576.0)) {
+                ctx->err = "pose " + std::to_string(i) + ": farther than 2^20 pixels from the source";
+                return FPM_E_INVALID_ARG;
+            }
+        }
+        const size_t off = (size_t)i * patch_stride;
+        if (tiled) {
+            PatchJob& j = ctx->h_patchtab.as<PatchJob>()[i];
+            std::copy(M, M + 6, j.M);
+            j.out_off = (int64_t)off;
+            j.src = p.src;
+            j.pad = 0;
+        } else {
+            WarpJob& j = ctx->h_patchtab.as<WarpJob>()[i];
+            j.src = level0 + l0.img_bytes * (size_t)p.src;
+            j.dst = d_out + off;
+            j.sw = l0.w; j.sh = l0.h; j.sp = l0.pitch;
+            j.dw = r.w; j.dh = r.h; j.dp = (int32_t)row_stride;
+            j.border = 0;
+            j.pad = 0;
+            std::copy(M, M + 6, j.M);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    // bytes: the patch pixels written + as many source pixels read (the footprint of a scale-1 warp)
+    ProfScope ps(ctx, FPM_K_PATCH, 2 * (int64_t)n * r.w * r.h);
+    if (tiled) {
+        PatchArgs a{};
+        a.jobs = ctx->d_patchtab.as<PatchJob>();
+        a.njobs = n;
+        a.level0 = level0;
+        a.img_stride = l0.img_bytes;
+        a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+        a.out = d_out;
+        a.row_stride = row_stride;
+        a.pw = r.w; a.ph = r.h;
+        a.dword = (((uintptr_t)d_out | row_stride | patch_stride) & 3) == 0;
+        if (!launch_patch_warp(a, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
+    } else {
+        constexpr int kMaxJobs = 65535;   // k_warp takes its job from blockIdx.y
+        for (int i0 = 0; i0 < n; i0 += kMaxJobs)
+            launch_warp(ctx->d_patchtab.as<WarpJob>() + i0, std::min(kMaxJobs, n - i0), r.w * r.h, ctx->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return FPM_OK;
+}
+
+// The host variants: the patches into the context's own buffer (row pitch a multiple of 64), then out to the caller's.
+int patches_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* out,
+                    size_t row_stride, size_t patch_stride, double* matrices) {
+    const size_t n = poses.size();
+    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
+    HIP_TRY(ctx->d_patch.ensure(pbytes * n));
+    uint8_t* d = ctx->d_patch.as<uint8_t>();
+    const int rc = enqueue_patches(ctx, r, poses, d, pitch, pbytes, matrices);
+    if (rc != FPM_OK) return rc;
+    if (patch_stride == row_stride * (size_t)r.h) {   // the caller's patches are one run of rows
+        HIP_TRY(hipMemcpy2DAsync(out, row_stride, d, pitch, r.w, (size_t)r.h * n, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        for (size_t i = 0; i < n; ++i)
+            HIP_TRY(hipMemcpy2DAsync(out + i * patch_stride, row_stride, d + i * pbytes, pitch, r.w, r.h,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
     return FPM_OK;
 }
 
@@ -1819,6 +1997,9 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_ov.release(); ctx->h_ov_in.release(); ctx->h_ov_out.release();
     ctx->d_imgtab.release(); ctx->h_imgtab.release();
     if (ctx->in_ev) (void)hipEventDestroy(ctx->in_ev);
+    ctx->d_patchtab.release(); ctx->h_patchtab.release(); ctx->d_patch.release();
+    for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
+        if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
         for (auto& e : k.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     (void)hipStreamDestroy(ctx->stream);
@@ -1849,6 +2030,7 @@ int fpm_learn(fpm_ctx* ctx, const uint8_t* gray, int32_t w, int32_t h, size_t st
     HIP_TRY(hipSetDevice(ctx->device));
     ctx->learned = false;
     ctx->staged = false;
+    ctx->src_valid = false;   // the slab's layout follows the template's pyramid depth
     ctx->tmpl.clear();
     const int L = top_layer(w, h, (int)std::sqrt((double)ctx->prm.min_reduce_area));
     std::vector<TmplLevel> lv(L + 1);
@@ -1927,6 +2109,7 @@ int fpm_clear_pattern(fpm_ctx* ctx) {
     if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
     ctx->learned = false;
     ctx->staged = false;
+    ctx->src_valid = false;
     ctx->tmpl.clear();
     ctx->tmpl_gen++;
     return FPM_OK;
@@ -1977,6 +2160,7 @@ int fpm_match_staged_finish(fpm_ctx* ctx, fpm_result* out, int32_t cap, int32_t*
     if (!ctx || !n_results) return FPM_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     ctx->results.clear();
+    ctx->poses.clear();
     const int rc = complete_staged(ctx, ctx->results, out != nullptr);
     if (rc != FPM_OK) return rc;
     return copy_results(ctx->results, out, cap, n_results);
@@ -1999,6 +2183,7 @@ int fpm_match(fpm_ctx* ctx, const uint8_t* gray, int32_t w, int32_t h, size_t st
     ctx->cands.clear();
     ctx->stats.clear();
     ctx->results.clear();
+    ctx->poses.clear();
     if (!gray || w <= 0 || h <= 0 || stride < (size_t)w) { ctx->err = "empty source"; return FPM_E_INVALID_ARG; }
     int rc = check_sizes(ctx, w, h);
     if (rc != FPM_OK) return rc;
@@ -2054,6 +2239,7 @@ int fpm_match_device(fpm_ctx* ctx, const void* d_image, int32_t w, int32_t h, si
     ctx->cands.clear();   // as fpm_match: a failed call leaves no stale records behind
     ctx->stats.clear();
     ctx->results.clear();
+    ctx->poses.clear();
     if (!d_image) { ctx->err = "empty source"; return FPM_E_INVALID_ARG; }
     int rc = check_image_desc(ctx, 1, w, h, stride, plane_stride, format);
     if (rc != FPM_OK) return rc;
@@ -2085,6 +2271,95 @@ int fpm_last_results(const fpm_ctx* ctx, fpm_result* out, int32_t cap, int32_t* 
     if (!ctx || !n_results) return FPM_E_INVALID_ARG;
     if (ctx->pending) return FPM_E_INVALID_ARG;
     return copy_results(ctx->results, out, cap, n_results);
+}
+
+// --- match patches --------------------------------------------------------------------
+int fpm_patch_matrix(int32_t src_w, int32_t src_h, float lt_x, float lt_y, double angle, int32_t rect_x, int32_t rect_y,
+                     double m[6]) {
+    if (!m || src_w <= 0 || src_h <= 0) return FPM_E_INVALID_ARG;
+    const double rad = angle * kD2R;
+    patch_matrix(src_w, src_h, f2(lt_x, lt_y), std::cos(rad), std::sin(rad), rect_x, rect_y, m);
+    return FPM_OK;
+}
+
+int fpm_set_patch_form(fpm_ctx* ctx, int32_t form) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (form != FPM_PATCH_FORM_TILED && form != FPM_PATCH_FORM_WARP) { ctx->err = "unknown patch form"; return FPM_E_INVALID_ARG; }
+    ctx->patch_form = form;
+    return FPM_OK;
+}
+
+// state, rectangle, poses and capacity of a fpm_last_patches* call; FPM_OK with poses empty = nothing to do
+static int last_patches_begin(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t cap, int32_t* n_patches,
+                              fpm_patch_rect* r, std::vector<PatchPose>& poses) {
+    *n_patches = 0;
+    int rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = patch_rect(ctx, rect, r);
+    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
+    if (rc != FPM_OK) return rc;
+    *n_patches = (int32_t)poses.size();
+    if ((int)poses.size() > cap) {
+        ctx->err = "patch buffer too small";
+        return FPM_E_CAPACITY;
+    }
+    return FPM_OK;
+}
+
+int fpm_last_patches(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, uint8_t* out, size_t row_stride,
+                     size_t patch_stride, int32_t cap, int32_t* n_patches, double* matrices) {
+    if (!ctx || !n_patches) return FPM_E_INVALID_ARG;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    int rc = last_patches_begin(ctx, rect, source, cap, n_patches, &r, poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    rc = check_patch_out(ctx, out, r, row_stride, patch_stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return patches_to_host(ctx, r, poses, out, row_stride, patch_stride, matrices);
+}
+
+int fpm_last_patches_device(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, void* d_out, size_t row_stride,
+                            size_t patch_stride, int32_t cap, int32_t* n_patches, void* consumer_stream) {
+    if (!ctx || !n_patches) return FPM_E_INVALID_ARG;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    int rc = last_patches_begin(ctx, rect, source, cap, n_patches, &r, poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    rc = check_patch_out(ctx, d_out, r, row_stride, patch_stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t extent = (poses.size() - 1) * patch_stride + (size_t)(r.h - 1) * row_stride + (size_t)r.w;
+    const void* outs[1] = {d_out};
+    rc = check_device_images(ctx, outs, 1, extent, "patch output");
+    if (rc != FPM_OK) return rc;
+    hipStream_t consumer = (hipStream_t)consumer_stream;
+    // after what the consumer's stream already holds for the buffer, then the launch, then the consumer after the launch
+    if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
+    if (!ctx->out_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->out_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctx->in_ev, consumer));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->in_ev, 0));
+    rc = enqueue_patches(ctx, r, poses, (uint8_t*)d_out, row_stride, patch_stride, nullptr);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->out_ev, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(consumer, ctx->out_ev, 0));
+    return FPM_OK;
+}
+
+int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                   const double* angles, int32_t n, uint8_t* out, size_t row_stride, size_t patch_stride,
+                   double* matrices) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n < 0 || (n > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    int rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = patch_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n == 0) return rc;
+    rc = check_patch_out(ctx, out, r, row_stride, patch_stride);
+    if (rc != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n);
+    for (int i = 0; i < n; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return patches_to_host(ctx, r, poses, out, row_stride, patch_stride, matrices);
 }
 
 // --- angle sharding of one search ---------------------------------------------------------

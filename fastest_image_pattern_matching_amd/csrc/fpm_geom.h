@@ -63,6 +63,17 @@ FPM_HD void roi_matrix(int src_w, int src_h, F2 lt, double c, double s, double M
     invert_affine(M);
 }
 
+// A match patch (fpm_patch_matrix): getRotatedROI's FORWARD matrix with the rectangle's origin
+// (rx, ry) in template coordinates in place of the fixed 3-pixel margin.  The sum is formed in float, so (-3, -3) gives
+// roi_matrix's forward matrix bit for bit: ltr.x + (-3.f) == ltr.x - 3.
+FPM_HD void patch_matrix(int src_w, int src_h, F2 lt, double c, double s, int rx, int ry, double M[6]) {
+    F2 ctr = f2((src_w - 1) / 2.0f, (src_h - 1) / 2.0f);
+    F2 ltr = rotate_pt(lt, ctr, c, s);
+    rotation_matrix(ctr, c, s, M);
+    M[2] -= ltr.x + (float)rx;
+    M[5] -= ltr.y + (float)ry;
+}
+
 // Fixed-point sampling constants of cv::warpAffine INTER_LINEAR.
 constexpr int kAbBits = 10, kAbScale = 1 << kAbBits, kInterBits = 5, kInterTab = 1 << kInterBits;
 constexpr int kRoundDelta = kAbScale / kInterTab / 2;

@@ -205,6 +205,30 @@ int stage_gray_bpp(int format);   // bytes per pixel within a row (1 for the pla
 // graph carries no memset nodes
 void launch_warp(const WarpJob* jobs, int njobs, int max_pixels, hipStream_t st, int32_t* zero = nullptr,
                  int nzero = 0);
+// ---- match patches (fpm_last_patches / fpm_patches_at): upright crops of level 0 of the staged
+// sources, all of one size, one launch for all of them.  One descriptor per patch, built on the host.
+struct PatchJob {
+    double M[6];             // INVERTED matrix (patch -> source)
+    int64_t out_off;         // byte offset of the patch's first pixel from PatchArgs::out
+    int32_t src;             // source index in the slab
+    int32_t pad;
+};
+struct PatchArgs {
+    const PatchJob* jobs;
+    int32_t njobs;
+    const uint8_t* level0;   // level 0 of source 0; + src * img_stride
+    size_t img_stride;
+    int32_t sw, sh, sp;      // source size and row pitch (>= sw + 4: aligned dword reads of a footprint stay in the row)
+    uint8_t* out;
+    size_t row_stride;       // bytes between the rows of a patch
+    int32_t pw, ph;          // patch size
+    int32_t dword;           // out, row_stride and every out_off are multiples of 4: whole groups of 4 pixels are stored
+                             // as dwords (bytes otherwise)
+    int32_t tiles_x, tiles_y;   // 64 x 16 output tiles per patch (set by launch_patch_warp)
+};
+// k_patch_warp: one workgroup per 64 x 16 output tile.  Returns false, launching nothing, when the grid would exceed
+// 2^31 - 1 workgroups.
+bool launch_patch_warp(PatchArgs a, hipStream_t st);
 void launch_ncc_map(const NccJob* jobs, int njobs, int max_out, int tmpl_bytes, hipStream_t st);
 bool ncc_tile_fits(int tw, int th);   // LDS-tiled variant applies (templates up to 128 x 64)
 void launch_ncc_tile(const NccJob* jobs, int njobs, int max_ow, int max_oh, int tw, int th, hipStream_t st);

@@ -2609,6 +2609,113 @@ __device__ __forceinline__ void stage_block4(uint8_t* dst, int dp, const uint8_t
     }
 }
 
+// ============================================================================================== match patches
+// k_patch_warp (fpm_last_patches / fpm_patches_at): cv::warpAffine(INTER_LINEAR, BORDER_CONSTANT
+// 0) of level 0 of a staged source into an upright patch, for every patch of the job table in one launch.  k_warp
+// computes the same bytes; this kernel spends less per pixel:
+//  * a 256-lane workgroup takes one 64 x 16 output tile and forms warpAffine's fixed-point terms once per tile (64
+//    column terms adelta / bdelta, 16 row terms X0 / Y0, in f64 as k_warp forms them per pixel) into LDS;
+//  * the tile's source footprint -- the box of the four corner pixels' taps, one pixel wider on every side (the
+//    fixed-point map is two roundings of a linear map, so every pixel's tap lies within the corners' range +-1), plus
+//    the taps' own second column and row -- is staged into LDS with aligned dword loads and sampled there, without
+//    border tests, when it lies inside the image and fits the buffer.  A scale-1 rotation of a 64 x 16 tile spans at
+//    most sqrt(63^2 + 15^2) < 65 pixels on either axis, so every interior tile of a patch fits (72 columns after the
+//    alignment, 69 rows); the test is made all the same, once per workgroup and explicitly, and a tile that fails it --
+//    one that touches the image border, or a matrix that is no such rotation -- samples global memory through
+//    warp_tap, whose border rules are cv::remap's;
+//  * a lane produces 4 adjacent pixels and stores them as one dword (bytes on a ragged right edge, or where the
+//    caller's output is not 4-byte aligned); the bytes of a row past the patch width are never written.
+constexpr int kPatchTw = 64, kPatchTh = 16;
+constexpr int kPatchFtPitch = 76;   // footprint row pitch in LDS: 19 dwords (odd: row-strided byte gathers spread over the banks)
+constexpr int kPatchFtRows = 72;
+
+__global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[2 * kPatchTw + 2 * kPatchTh];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtPitch * kPatchFtRows + 16];
+    int32_t* const ad = tab;
+    int32_t* const bd = tab + kPatchTw;
+    int32_t* const X0 = tab + 2 * kPatchTw;
+    int32_t* const Y0 = X0 + kPatchTh;
+    const int tid = threadIdx.x;
+    // neighbouring tiles share footprint lines and output lines: keep them on one XCD's L2 (speed only)
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int p = b / tiles, t = b - p * tiles;
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const int x0 = tx * kPatchTw, y0 = ty * kPatchTh;
+    const PatchJob& j = a.jobs[p];
+    if (tid < kPatchTw) {
+        const int x = x0 + tid;
+        ad[tid] = rint_i(j.M[0] * x * kAbScale);
+        bd[tid] = rint_i(j.M[3] * x * kAbScale);
+    } else if (tid < kPatchTw + kPatchTh) {
+        const int y = y0 + tid - kPatchTw;
+        X0[tid - kPatchTw] = rint_i((j.M[1] * y + j.M[2]) * kAbScale) + kRoundDelta;
+        Y0[tid - kPatchTw] = rint_i((j.M[4] * y + j.M[5]) * kAbScale) + kRoundDelta;
+    }
+    __syncthreads();
+    // the footprint box from the taps of the tile's four corner pixels (the corners inside the patch)
+    const int cx = (a.pw - x0 < kPatchTw ? a.pw - x0 : kPatchTw) - 1, cy = (a.ph - y0 < kPatchTh ? a.ph - y0 : kPatchTh) - 1;
+    int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = (k & 1) ? cx : 0, r = (k & 2) ? cy : 0;
+        const int sx = (X0[r] + ad[c]) >> kAbBits, sy = (Y0[r] + bd[c]) >> kAbBits;
+        bx0 = sx < bx0 ? sx : bx0; bx1 = sx > bx1 ? sx : bx1;
+        by0 = sy < by0 ? sy : by0; by1 = sy > by1 ? sy : by1;
+    }
+    bx0 -= 1; by0 -= 1; bx1 += 2; by1 += 2;
+    const int bxa = bx0 & ~3;                       // dword-aligned first column (rows of the slab are 64-byte aligned)
+    const int wpr = ((bx1 - bxa) >> 2) + 1;         // dwords per footprint row
+    const int fth = by1 - by0 + 1;
+    // in LDS: inside the image (so no tap needs a border test, and coordinates stay below remap's 16-bit saturation),
+    // and within the buffer.  The same value in every lane (it comes from LDS words all lanes read); taken from the
+    // first lane so that the branch, and the barrier inside it, are uniform by construction.
+    const bool fits = bx0 >= 0 && by0 >= 0 && bx1 < a.sw && by1 < a.sh && a.sw <= 32768 && a.sh <= 32768 &&
+                      wpr <= kPatchFtPitch / 4 && fth <= kPatchFtRows;
+    const bool in_lds = __builtin_amdgcn_readfirstlane((int)fits) != 0;
+    const uint8_t* img = a.level0 + (size_t)j.src * a.img_stride;
+    if (in_lds) {
+        stage_block4(FT, kPatchFtPitch, img + (size_t)by0 * a.sp + bxa, (size_t)a.sp, fth, wpr, bxa, a.sp, tid, 256);
+        __syncthreads();
+    }
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = x0 + gx, y = y0 + r;
+    if (x >= a.pw || y >= a.ph) return;
+    const int nu = a.pw - x < 4 ? a.pw - x : 4;
+    const int Xr = X0[r], Yr = Y0[r];
+    const int4 A = *(const int4*)(ad + gx), B = *(const int4*)(bd + gx);
+    const int av[4] = {A.x, A.y, A.z, A.w}, bv[4] = {B.x, B.y, B.z, B.w};
+    uint32_t word = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (u >= nu) break;
+        const int X = (Xr + av[u]) >> (kAbBits - kInterBits), Y = (Yr + bv[u]) >> (kAbBits - kInterBits);
+        int v;
+        if (in_lds)
+            v = ft_tap_bytes(FT, ((Y >> kInterBits) - by0) * kPatchFtPitch + (X >> kInterBits) - bxa, kPatchFtPitch, X, Y);
+        else
+            v = warp_tap(img, a.sw, a.sh, a.sp, X, Y, 0);
+        word |= (uint32_t)v << (8 * u);
+    }
+    uint8_t* d = a.out + j.out_off + (size_t)y * a.row_stride + x;
+    if (a.dword && nu == 4) {
+        *(uint32_t*)d = word;
+    } else {
+        for (int u = 0; u < nu; ++u) d[u] = (uint8_t)(word >> (8 * u));
+    }
+}
+
+bool launch_patch_warp(PatchArgs a, hipStream_t st) {
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX) return false;
+    hipLaunchKernelGGL(k_patch_warp, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return true;
+}
+
 // ---- K6a: per-ROI fixed-point warp tables (getRotatedROI -> warpAffine's adelta/bdelta/X0/Y0) and, from them,
 // one descriptor per 32x32 ROI tile: the tile's source footprint box (corner samples +-1 px: the fixed-point map
 // is two roundings of a linear map, so every pixel's tap lies within the corners' range +-1) and flags

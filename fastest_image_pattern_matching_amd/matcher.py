@@ -8,6 +8,7 @@ nothing (:398-404).  All pixel work runs in libfpm_hip.so on a gfx950 device.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import List, Sequence, Tuple
 
@@ -187,6 +188,82 @@ def device_format(kind: str, channels: int, channel_order: str = "bgr") -> int:
     return L.FMT_RGB8 if rgb else L.FMT_BGR8
 
 
+# -- match patches (fpm_last_patches* / fpm_patches_at): pure argument checks, no device needed ----------------------
+PATCH_MAX_SIDE = 8192
+
+
+def normalize_rect(rect) -> Tuple[int, int, int, int]:
+    """A patch rectangle (x, y, w, h) in template coordinates as four ints.  It may reach outside the template; width
+    and height must be 1 .. 8192 (include/fpm.h).  Raises ValueError otherwise."""
+    try:
+        x, y, w, h = (int(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError(f"expected a rectangle (x, y, w, h), got {rect!r}") from None
+    if any(float(v) != i for v, i in zip(rect, (x, y, w, h))):
+        raise ValueError(f"rectangle {tuple(rect)!r} must hold whole numbers")
+    if not (1 <= w <= PATCH_MAX_SIDE and 1 <= h <= PATCH_MAX_SIDE):
+        raise ValueError(f"rectangle {(x, y, w, h)}: width and height must be 1 .. {PATCH_MAX_SIDE}")
+    return x, y, w, h
+
+
+def patch_out_layout(shape, strides, n: int, ph: int, pw: int) -> Tuple[int, int]:
+    """(row_stride, patch_stride) in bytes of a uint8 output of ``shape`` and ``strides`` (in elements = bytes) that is to
+    receive ``n`` patches of ``ph`` x ``pw`` (last_patches_device's ``out``).  The shape must be (n, ph, pw); the pixel
+    stride must be 1, rows must not overlap, patches must not overlap (views into larger tensors are fine: a column
+    slice, a row slice, every k-th patch slot).  The stride of a dimension of size 1 is not looked at.  Raises
+    ValueError otherwise."""
+    shape = tuple(int(v) for v in shape)
+    strides = tuple(int(v) for v in strides)
+    if shape != (n, ph, pw) or len(strides) != 3:
+        raise ValueError(f"out must have shape {(n, ph, pw)}, got {shape}")
+    if pw > 1 and strides[2] != 1:
+        raise ValueError(f"pixel stride {strides[2]} of out must be 1")
+    row = strides[1] if ph > 1 else pw   # one row per patch: only the patch stride matters
+    if row < pw:
+        raise ValueError(f"row stride {row} of out below the patch width {pw}")
+    patch = strides[0] if n > 1 else row * ph
+    if patch < row * ph:
+        raise ValueError(f"patch stride {patch} of out below row stride x height = {row * ph}")
+    return row, patch
+
+
+def patch_poses(src_index, lts, angles):
+    """(src_index int32 [n], lt float32 [n, 2], angles float64 [n]) for patches_at, from array-likes of matching
+    lengths; a scalar src_index stands for every pose.  Raises ValueError on a mismatch or a non-finite value."""
+    lt = np.ascontiguousarray(lts, np.float32)
+    if lt.ndim == 1 and lt.size == 2:
+        lt = lt.reshape(1, 2)
+    if lt.ndim != 2 or lt.shape[1] != 2:
+        raise ValueError(f"lts must be (n, 2) points (x, y), got shape {lt.shape}")
+    n = lt.shape[0]
+    ang = np.ascontiguousarray(angles, np.float64).reshape(-1)
+    if ang.size != n:
+        raise ValueError(f"{n} points but {ang.size} angles")
+    idx = np.asarray(src_index)
+    if idx.ndim == 0:
+        idx = np.full(n, int(idx))
+    idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    if idx.size != n:
+        raise ValueError(f"{n} points but {idx.size} source indices")
+    if not (np.isfinite(lt).all() and np.isfinite(ang).all()):
+        raise ValueError("poses must be finite")
+    if n and idx.min() < 0:
+        raise ValueError("negative source index")
+    return idx, lt, ang
+
+
+def patch_matrix(src_w: int, src_h: int, lt, angle: float, rect_xy=(0, 0)) -> np.ndarray:
+    """fpm_patch_matrix: the forward 2x3 matrix of the patch of a pose (ptLT ``lt`` as f32, ``angle`` in degrees) on a
+    ``src_w`` x ``src_h`` source, for a rectangle whose origin is ``rect_xy`` in template coordinates.  Host only (no
+    device): cv::warpAffine(source, m, (w, h), INTER_LINEAR, BORDER_CONSTANT 0) is the patch."""
+    m = (C.c_double * 6)()
+    rc = L.load().fpm_patch_matrix(int(src_w), int(src_h), float(np.float32(lt[0])), float(np.float32(lt[1])),
+                                   float(angle), int(rect_xy[0]), int(rect_xy[1]), m)
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_patch_matrix failed with {rc}")
+    return np.array(m[:], np.float64).reshape(2, 3)
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -204,6 +281,11 @@ class TemplateMatcher:
         self._cap = 64                 # results per source; grown on FPM_E_CAPACITY
         self._staged = 0               # sources of the last stage() (0 after a plain match())
         self._bufs = None              # reusable ctypes result buffers for match_staged
+        # FPM_PATCH_TILED=0: the match patches through k_warp instead of k_patch_warp (same bytes; the comparison and
+        # the fallback).  Read once, here; setPatchForm changes it afterwards.
+        env = os.environ.get("FPM_PATCH_TILED")
+        if env is not None and env.strip() != "":
+            self.setPatchForm(L.PATCH_FORM_WARP if int(env) == 0 else L.PATCH_FORM_TILED)
 
     def __del__(self):
         ctx = getattr(self, "_ctx", None)
@@ -296,6 +378,12 @@ class TemplateMatcher:
             raise ValueError(f"expected a tensor on cuda:{self._device}, got one on {img.device} (match() takes host images)")
         if img.device.index != self._device:
             raise ValueError(f"tensor on {img.device}, context on cuda:{self._device}")
+        self._check_one_runtime()
+        kind, h, w, ch, row, plane = device_layout(tuple(img.shape), tuple(img.stride()), layout)
+        return img.data_ptr(), h, w, row, plane, device_format(kind, ch, channel_order)
+
+    @staticmethod
+    def _check_one_runtime():
         global _one_runtime
         if not _one_runtime:
             rts = L.hip_runtimes()
@@ -304,8 +392,6 @@ class TemplateMatcher:
                                    "the tensor's pointer and stream are foreign to the library: import torch before "
                                    "the first TemplateMatcher is created (before libfpm_hip.so is loaded)")
             _one_runtime = True
-        kind, h, w, ch, row, plane = device_layout(tuple(img.shape), tuple(img.stride()), layout)
-        return img.data_ptr(), h, w, row, plane, device_format(kind, ch, channel_order)
 
     def _producer_stream(self, stream):
         import torch
@@ -497,10 +583,142 @@ class TemplateMatcher:
 
     def getBitwiseNot(self) -> bool: return bool(self._params.bitwise_not)
 
-    # -- user rectangle: stored only, unused by matching (TemplateMatcher.cpp:1224-1238) ---------------------
+    # -- user rectangle (TemplateMatcher.cpp:1224-1238): unused by matching; the default rectangle of the match patches,
+    # which is what the reference's tool does with it (MatchToolDialog.cpp:1216-1328 carries it onto every match) ----
     def setUserDefinedRect(self, rect): self._user_rect = tuple(rect)
     def getUserDefinedRect(self): return self._user_rect if self._user_rect is not None else (0, 0, 0, 0)
     def hasUserDefinedRect(self) -> bool: return self._user_rect is not None
+
+    # -- match patches: upright crops of the results, sampled on the device (fpm_last_patches* / fpm_patches_at) -------
+    def setPatchForm(self, form: int):
+        """fpm_set_patch_form: L.PATCH_FORM_TILED (k_patch_warp, default) or L.PATCH_FORM_WARP (k_warp; same bytes)."""
+        rc = self._lib.fpm_set_patch_form(self._ctx, int(form))
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_set_patch_form({form}) failed with {rc}: {self.last_error()}")
+
+    def _patch_rect(self, rect):
+        """The fpm_patch_rect of ``rect``: None = the user-defined rectangle when one is set, else NULL (the whole
+        template)."""
+        r = rect if rect is not None else self._user_rect
+        return None if r is None else L.PatchRect(*normalize_rect(r))
+
+    def patch_size(self, rect=None) -> Tuple[int, int]:
+        """(pw, ph) of the patches for ``rect`` ((x, y, w, h) in template coordinates; None = the user-defined rectangle
+        when one is set, else the learned template's frame)."""
+        r = self._patch_rect(rect)
+        if r is not None:
+            return r.w, r.h
+        w, h, eq = C.c_int32(), C.c_int32(), C.c_int32()
+        d = C.c_double()
+        if self._lib.fpm_template_level(self._ctx, 0, C.byref(w), C.byref(h), C.byref(d), C.byref(d), C.byref(d),
+                                        C.byref(eq), None, 0) != L.FPM_OK:
+            raise ValueError("template not learned")
+        return w.value, h.value
+
+    def _patch_fail(self, rc, what):
+        self._check(rc, what)
+        raise ValueError(f"{what} failed with {rc}: {self.last_error()}")
+
+    def _patch_count(self, r, source):
+        n = C.c_int32()
+        rc = self._lib.fpm_last_patches(self._ctx, C.byref(r) if r is not None else None, int(source), None, 0, 0, 0,
+                                        C.byref(n), None)
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_patches")
+        return n.value
+
+    def _last_counts(self) -> np.ndarray:
+        n = (C.c_int32 * max(self._staged, 1))()
+        self._lib.fpm_last_results(self._ctx, None, 0, n)
+        return np.array(n[:], np.int32)
+
+    @staticmethod
+    def _host_patch_out(out, n, ph, pw):
+        """(array, row_stride, patch_stride) of a host output: a fresh dense one, or the caller's checked."""
+        if out is None:
+            return np.zeros((n, ph, pw), np.uint8), pw, pw * ph
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8:
+            raise TypeError("out must be a uint8 numpy array")
+        row, patch = patch_out_layout(out.shape, out.strides, n, ph, pw)
+        return out, row, patch
+
+    def last_patches(self, source: int = 0, rect=None, matrices: bool = False, out=None):
+        """The pixels behind the last search's results: for every result of ``source`` (result order) the matched region
+        of level 0 turned upright and cropped to ``rect`` -- (x, y, w, h) in template coordinates, None = the
+        user-defined rectangle when one is set, else the template's frame; (-3, -3, tw + 6, th + 6) is the reference's
+        getRotatedROI (TemplateMatcher.cpp:1074-1090) bit for bit.  Returns a uint8 array (n, ph, pw); with
+        ``matrices`` also the patches' forward 2x3 matrices (n, 2, 3).  ``source=-1``: the patches of all sources in
+        source order and the per-source counts, ``(patches, counts[, matrices])``.  The plane sampled is the one the
+        search ran on: 255 - source under setBitwiseNot.  ``out``: a uint8 array (n, ph, pw) to write instead of a new
+        one (unit pixel stride, any row and patch strides; the bytes between the rows keep their values).  One device
+        launch (fpm_last_patches)."""
+        r = self._patch_rect(rect)
+        pr = C.byref(r) if r is not None else None
+        n = self._patch_count(r, source)
+        pw, ph = self.patch_size(rect)
+        out, row, patch = self._host_patch_out(out, n, ph, pw)
+        mats = np.zeros((n, 2, 3), np.float64)
+        if n:
+            got = C.c_int32()
+            rc = self._lib.fpm_last_patches(self._ctx, pr, int(source), L.u8ptr(out), row, patch, n, C.byref(got),
+                                            mats.ctypes.data_as(C.POINTER(C.c_double)))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_patches")
+        res = (out,) if source >= 0 else (out, self._last_counts())
+        res = res + (mats,) if matrices else res
+        return res[0] if len(res) == 1 else res
+
+    def last_patches_device(self, source: int = 0, rect=None, out=None, stream=None):
+        """last_patches into device memory, for a consumer on the device: a uint8 cuda tensor (n, ph, pw), no pixel
+        crossing the host (fpm_last_patches_device).  ``out``: the tensor to write, shape (n, ph, pw), unit pixel stride,
+        any row and patch strides (a view into a larger tensor is written in place; its other bytes are untouched);
+        None allocates one.  The launch is ordered after the work already enqueued on ``stream`` (a torch stream or a
+        raw handle; None = torch's current stream of the device) and that stream's later work after the launch, without
+        a host synchronisation: use the tensor on that stream.  ``source=-1``: ``(patches, counts)``."""
+        import torch
+
+        r = self._patch_rect(rect)
+        n = self._patch_count(r, source)
+        pw, ph = self.patch_size(rect)
+        dev = torch.device("cuda", self._device)
+        if out is None:
+            ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else torch.cuda.device(dev)
+            with ctx:
+                out = torch.empty((n, ph, pw), dtype=torch.uint8, device=dev)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8:
+            raise TypeError("out must be a uint8 torch.Tensor")
+        if out.device != dev:
+            raise ValueError(f"out on {out.device}, context on {dev}")
+        self._check_one_runtime()
+        row, patch = patch_out_layout(tuple(out.shape), tuple(out.stride()), n, ph, pw)
+        if n:
+            got = C.c_int32()
+            rc = self._lib.fpm_last_patches_device(self._ctx, C.byref(r) if r is not None else None, int(source),
+                                                   out.data_ptr(), row, patch, n, C.byref(got),
+                                                   self._producer_stream(stream))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_patches_device")
+        return out if source >= 0 else (out, self._last_counts())
+
+    def patches_at(self, src_index, lts, angles, rect=None, matrices: bool = False, out=None):
+        """Patches at poses the caller supplies, on the staged sources (fpm_patches_at): ``lts`` (n, 2) ptLT as the
+        search reports it, ``angles`` (n) dMatchedAngle of the Qt semantics in degrees, ``src_index`` (n) or one index
+        for all.  For results that no context holds, such as the merged results of an angle-sharded search.  Needs
+        staged sources (stage / stage_device, or the source of the last match), not a search.  Returns uint8
+        (n, ph, pw), with ``matrices`` also (n, 2, 3); ``out`` as last_patches."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        r = self._patch_rect(rect)
+        pw, ph = self.patch_size(rect)
+        n = len(idx)
+        out, row, patch = self._host_patch_out(out, n, ph, pw)
+        mats = np.zeros((n, 2, 3), np.float64)
+        rc = self._lib.fpm_patches_at(self._ctx, C.byref(r) if r is not None else None,
+                                      idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
+                                      ang.ctypes.data_as(C.POINTER(C.c_double)), n, L.u8ptr(out), row, patch,
+                                      mats.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "patches_at")
+        return (out, mats) if matrices else out
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------
     def pyr_down(self, img) -> np.ndarray:

@@ -185,6 +185,67 @@ int fpm_match_device(fpm_ctx* ctx, const void* d_image, int32_t width, int32_t h
                      size_t plane_stride, int32_t format, void* producer_stream, fpm_result* out, int32_t cap,
                      int32_t* n_results, double* seconds);
 
+/* --- match patches: the pixels behind the results, upright and cropped, from the sources in device memory ------------
+ * The reference's tools show what a caller wants after a search: the MFC tool's "Output ROI" switch saves the matched
+ * region of every result (MatchToolDlg.cpp:1114, :1223-1236), the Qt tool carries a rectangle drawn on the template onto
+ * every match (MatchToolDialog.cpp:1216-1328).  A patch is getRotatedROI (TemplateMatcher.cpp:1074-1090) with a
+ * caller-chosen rectangle (x, y, w, h) in template coordinates in place of its fixed 3-pixel margin: for a pose (ptLT
+ * as f32, angle in degrees) on a source of src_w x src_h with centre c = ((src_w - 1) / 2.f, (src_h - 1) / 2.f),
+ *     ltr = ptRotatePt2f(ptLT, c, angle * D2R);  M = getRotationMatrix2D(c, angle, 1);
+ *     M[2] -= (float)(ltr.x + (float)x);  M[5] -= (float)(ltr.y + (float)y);
+ *     patch = cv::warpAffine(source, M, (w, h), INTER_LINEAR, BORDER_CONSTANT 0)
+ * so (-3, -3, tw + 6, th + 6) is getRotatedROI itself, bit for bit, and NULL = (0, 0, tw, th) is the template's frame.
+ * The rectangle may reach outside the template; pixels outside the source are 0.  w and h are 1 .. 8192.
+ *
+ * Pose.  fpm_last_patches* use the pose of the vecAllResult entry each result came from -- its f32 point and its
+ * dMatchAngle, as the search left them (sub-pixel estimate applied; with stop_layer the doubled layer-1 point and the
+ * layer-1 angle) -- not the converted fpm_result fields: under FPM_SEMANTICS_MFC the reported angle is negated and
+ * wrapped, and the trigonometry of a +- 360 differs in its last bits.
+ * Pixels.  The level-0 plane the last search ran on, as it lies in the context's source slab.  With
+ * fpm_params.bitwise_not in force for that search the plane is 255 - source, so the patch looks like the template,
+ * not like the caller's image.
+ * Additive entries: FPM_ABI_VERSION is unchanged, as for the device-memory entries above. */
+typedef struct fpm_patch_rect { int32_t x, y, w, h; } fpm_patch_rect;   /* template coordinates; NULL = whole template */
+
+/* host only, no context: the forward 2x3 matrix (row-major) of one patch, by the rule above */
+int fpm_patch_matrix(int32_t src_w, int32_t src_h, float lt_x, float lt_y, double angle,
+                     int32_t rect_x, int32_t rect_y, double m[6]);
+
+/* Patches of the last search's results, in result order (fpm_match, fpm_match_device, fpm_match_staged*); source = -1:
+ * the patches of all sources, concatenated in source order (the per-source counts are fpm_last_results').  One device
+ * launch for all of them.  Patch i is written at out + i * patch_stride, its rows row_stride apart (w <= row_stride
+ * < 2^31, patch_stride >= row_stride * h); the bytes of a row past w are left untouched.  *n_patches receives the number of
+ * patches; with cap below it the call returns FPM_E_CAPACITY and writes no pixel (cap = 0 with out = NULL asks for the
+ * count).  matrices (may be NULL) receives the forward matrix of every patch, [cap][6].
+ * FPM_E_INVALID_ARG while a search is in flight, when no search has run since the sources were staged, when nothing is
+ * staged, and for a bad rectangle; FPM_E_NOT_LEARNED without a template.  After fpm_match_staged_finish(out = NULL)
+ * there are no results: *n_patches = 0, FPM_OK.  Returns when the pixels have landed in `out`. */
+int fpm_last_patches(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, uint8_t* out, size_t row_stride,
+                     size_t patch_stride, int32_t cap, int32_t* n_patches, double* matrices);
+/* The same into device memory, for a consumer on the device (a torch model): nothing crosses the host.  d_out is
+ * checked as fpm_stage_sources_device checks its images (memory the context's device can access, byte extent inside
+ * its allocation); any alignment and any strides are fine (views into larger buffers).  consumer_stream is the
+ * hipStream_t that owns d_out (NULL = the null stream): the call makes the context's stream wait for the work already
+ * enqueued there (the buffer's allocation or clearing), enqueues the launch on the context's stream, records a
+ * context-owned event and makes consumer_stream wait for it, then returns -- without a host synchronisation.  Work
+ * enqueued on consumer_stream afterwards sees the patches; the host must not read d_out before synchronising with that
+ * stream. */
+int fpm_last_patches_device(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, void* d_out, size_t row_stride,
+                            size_t patch_stride, int32_t cap, int32_t* n_patches, void* consumer_stream);
+/* Patches at caller-supplied poses on the staged sources (results merged elsewhere: an angle-sharded search leaves no
+ * results in any context): lt [n][2] f32 ptLT, angles [n] degrees, src_index [n] source of each pose.  Needs staged
+ * sources (fpm_stage_sources*, or the source of the last fpm_match), not a search.  out, strides and matrices ([n][6])
+ * as fpm_last_patches. */
+int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                   const double* angles, int32_t n, uint8_t* out, size_t row_stride, size_t patch_stride,
+                   double* matrices);
+/* Which kernel samples the patches: k_patch_warp (LDS-tiled, 4 pixels per lane; default) or k_warp, the parity
+ * operator of fpm_op_warp_affine, over the same job list (the comparison, and the fallback).  Both give the same
+ * bytes.  Takes effect at the next patch call. */
+#define FPM_PATCH_FORM_TILED 0
+#define FPM_PATCH_FORM_WARP 1
+int fpm_set_patch_form(fpm_ctx* ctx, int32_t form);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent
@@ -327,7 +388,9 @@ int fpm_search_bytes(const fpm_ctx* ctx, int64_t* b_pyr, int64_t* b_top, int64_t
 #define FPM_K_CAND_STEP 10  /* k_cand_step    candidate step after k_roi_small                    */
 #define FPM_K_TOP_MAP 11    /* k_top_map: full maps of the jobs the list path left (fallback) */
 #define FPM_K_NOT 12        /* k_bitwise_not: 255 - source over the staged level 0 (fpm_params.bitwise_not) */
-#define FPM_K_COUNT 13
+#define FPM_K_PATCH 13      /* k_patch_warp (or k_warp, fpm_set_patch_form): the patches of fpm_last_patches* / fpm_patches_at;
+                               bytes = pixels written + as many source pixels read */
+#define FPM_K_COUNT 14
 int fpm_profile_enable(fpm_ctx* ctx, int32_t enable);
 int fpm_profile_reset(fpm_ctx* ctx);
 int fpm_profile_get(const fpm_ctx* ctx, int32_t kernel, double* total_ms, int64_t* launches,

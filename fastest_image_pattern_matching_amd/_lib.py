@@ -27,21 +27,25 @@ FPM_E_INTERNAL = -6
 FMT_COUNT = 7
 
 (K_PYR, K_TOP_WARP, K_TOP_NCC, K_TOP_NMS, K_CAND_INIT, K_ROI_TABLES, K_ROI_WARP, K_ROI_CORR, K_ROI_EVAL, K_ROI_SMALL,
- K_CAND_STEP, K_TOP_MAP, K_NOT, K_PATCH) = range(14)
+ K_CAND_STEP, K_TOP_MAP, K_NOT, K_PATCH, K_COMPARE) = range(15)
 # profiling index -> kernel (include/fpm.h FPM_K_*); top_ncc is k_top_mma (matrix-core top layer) where it applies, else
 # k_ncc_tile for templates up to 128 x 64; top_map = k_top_map, the matrix-core form's fallback (full maps for the jobs
 # its lists left); bitwise_not = k_bitwise_not, 255 - source over the staged level 0 (Params.bitwise_not); patch_warp =
-# the match patches' launch (k_patch_warp, or k_warp under FPM_PATCH_FORM_WARP), never part of a search
+# the match patches' launch (k_patch_warp, or k_warp under FPM_PATCH_FORM_WARP), never part of a search; patch_compare =
+# k_patch_compare, the launches of last_compare / compare_at (one, two when normalising), never part of a search either
 KERNEL_NAMES = ["pyr_down", "top_warp", "top_ncc", "top_nms", "cand_init", "roi_tables", "roi_warp", "roi_corr",
-                "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not", "patch_warp"]
+                "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not", "patch_warp", "patch_compare"]
 # fpm_set_patch_form
 PATCH_FORM_TILED, PATCH_FORM_WARP = 0, 1
+# fpm_last_compare / fpm_compare_at flags
+COMPARE_NORMALIZE = 1
 KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_warp"],
                   "top_ncc": ["k_top_mma", "k_ncc_tile", "k_ncc_map"],
                   "top_nms": ["k_nms_greedy", "k_nms"], "cand_init": ["k_cand_init"], "roi_tables": ["k_roi_tables"],
                   "roi_warp": ["k_roi_warp3", "k_roi_warp"], "roi_corr": ["k_roi_corr"], "roi_eval": ["k_roi_eval"],
                   "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"],
-                  "bitwise_not": ["k_bitwise_not"], "patch_warp": ["k_patch_warp"]}
+                  "bitwise_not": ["k_bitwise_not"], "patch_warp": ["k_patch_warp"],
+                  "patch_compare": ["k_patch_compare"]}
 
 
 class Params(C.Structure):
@@ -84,6 +88,16 @@ class PatchRect(C.Structure):
     """fpm_patch_rect — a patch's rectangle in template coordinates."""
 
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class CompareStats(C.Structure):
+    """fpm_compare_stats — one hit against the template (fpm_last_compare / fpm_compare_at)."""
+
+    _fields_ = [("n", C.c_int64), ("sum_i", C.c_int64), ("sum_ii", C.c_int64), ("sum_t", C.c_int64),
+                ("sum_tt", C.c_int64), ("sum_it", C.c_int64), ("sum_abs", C.c_int64),
+                ("n_over", C.c_int32), ("max_abs", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32),
+                ("zncc", C.c_double), ("gain", C.c_double), ("offset", C.c_double)]
 
 
 class RoiRecord(C.Structure):
@@ -150,6 +164,13 @@ SIGNATURES = {
                                  C.POINTER(C.c_double), C.c_int32, _U8P, C.c_size_t, C.c_size_t,
                                  C.POINTER(C.c_double)]),
     "fpm_set_patch_form": (C.c_int, [_P, C.c_int32]),
+    "fpm_last_compare": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_int32, C.c_int32, C.POINTER(CompareStats),
+                                   C.c_int32, C.POINTER(C.c_int32), _U8P, C.c_size_t, C.c_size_t]),
+    "fpm_compare_at": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(CompareStats), _U8P,
+                                 C.c_size_t, C.c_size_t]),
+    "fpm_compare_derive": (C.c_int, [C.c_int64] * 6 + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_double), _U8P]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

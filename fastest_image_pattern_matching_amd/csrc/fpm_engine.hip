@@ -211,6 +211,8 @@ struct fpm_ctx {
     PinBuf h_patchtab;        // job table: pinned staging + device copy; tab_ev = the last staging copy has left h_patchtab
     DevBuf d_patchtab, d_patch;   // d_patch: the patches of the host variants, before they are copied out
     hipEvent_t tab_ev = nullptr, out_ev = nullptr;
+    DevBuf d_cmpacc;          // the comparison's per-hit records (fpm_last_compare / fpm_compare_at) and their host copy
+    PinBuf h_cmpacc;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -1839,14 +1841,16 @@ int check_patch_out(fpm_ctx* ctx, const void* out, const fpm_patch_rect& r, size
     return FPM_OK;
 }
 
-// Job table and the one launch for `poses` on the context's stream (no wait): patch i goes to d_out + i * patch_stride.
-// matrices (optional): the forward matrices, [n][6].
-int enqueue_patches(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* d_out,
-                    size_t row_stride, size_t patch_stride, double* matrices) {
+size_t patch_tab_bytes(int n) { return round_up(std::max(sizeof(PatchJob), sizeof(WarpJob)) * (size_t)n, (size_t)256); }
+
+// The job table of `poses` (PatchJob when tiled, else WarpJob), built in h_patchtab and sent to d_patchtab on the
+// context's stream (no wait): patch i goes to d_out + i * patch_stride.  matrices (optional): the forward matrices,
+// [n][6].  extra: bytes kept free in both buffers behind the table, from patch_tab_bytes(n) on (the comparison's tables).
+int stage_patch_jobs(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* d_out,
+                     size_t row_stride, size_t patch_stride, double* matrices, bool tiled, size_t extra = 0) {
     const int n = (int)poses.size();
     const SrcLevel& l0 = ctx->src[0];
-    const bool tiled = ctx->patch_form == FPM_PATCH_FORM_TILED;
-    const size_t tab = std::max(sizeof(PatchJob), sizeof(WarpJob)) * (size_t)n;
+    const size_t tab = patch_tab_bytes(n) + extra;
     if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table (long done as a rule)
     HIP_TRY(ctx->h_patchtab.ensure(tab));
@@ -1890,21 +1894,38 @@ int enqueue_patches(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
             std::copy(M, M + 6, j.M);
         }
     }
-    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, patch_tab_bytes(n), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    return FPM_OK;
+}
+
+// the arguments of the tiled kernels (k_patch_warp, k_patch_compare) for a staged PatchJob table
+PatchArgs patch_args(fpm_ctx* ctx, const fpm_patch_rect& r, int n, uint8_t* d_out, size_t row_stride, size_t patch_stride) {
+    const SrcLevel& l0 = ctx->src[0];
+    PatchArgs a{};
+    a.jobs = ctx->d_patchtab.as<PatchJob>();
+    a.njobs = n;
+    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    a.img_stride = l0.img_bytes;
+    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    a.out = d_out;
+    a.row_stride = row_stride;
+    a.pw = r.w; a.ph = r.h;
+    a.dword = (((uintptr_t)d_out | row_stride | patch_stride) & 3) == 0;
+    return a;
+}
+
+// Job table and the one launch for `poses` on the context's stream (no wait).
+int enqueue_patches(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* d_out,
+                    size_t row_stride, size_t patch_stride, double* matrices) {
+    const int n = (int)poses.size();
+    const bool tiled = ctx->patch_form == FPM_PATCH_FORM_TILED;
+    const int rc = stage_patch_jobs(ctx, r, poses, d_out, row_stride, patch_stride, matrices, tiled);
+    if (rc != FPM_OK) return rc;
     // bytes: the patch pixels written + as many source pixels read (the footprint of a scale-1 warp)
     ProfScope ps(ctx, FPM_K_PATCH, 2 * (int64_t)n * r.w * r.h);
     if (tiled) {
-        PatchArgs a{};
-        a.jobs = ctx->d_patchtab.as<PatchJob>();
-        a.njobs = n;
-        a.level0 = level0;
-        a.img_stride = l0.img_bytes;
-        a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
-        a.out = d_out;
-        a.row_stride = row_stride;
-        a.pw = r.w; a.ph = r.h;
-        a.dword = (((uintptr_t)d_out | row_stride | patch_stride) & 3) == 0;
+        const PatchArgs a = patch_args(ctx, r, n, d_out, row_stride, patch_stride);
         if (!launch_patch_warp(a, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
     } else {
         constexpr int kMaxJobs = 65535;   // k_warp takes its job from blockIdx.y
@@ -1915,15 +1936,9 @@ int enqueue_patches(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     return FPM_OK;
 }
 
-// The host variants: the patches into the context's own buffer (row pitch a multiple of 64), then out to the caller's.
-int patches_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* out,
-                    size_t row_stride, size_t patch_stride, double* matrices) {
-    const size_t n = poses.size();
-    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
-    HIP_TRY(ctx->d_patch.ensure(pbytes * n));
-    uint8_t* d = ctx->d_patch.as<uint8_t>();
-    const int rc = enqueue_patches(ctx, r, poses, d, pitch, pbytes, matrices);
-    if (rc != FPM_OK) return rc;
+// n images of r.w x r.h from the context's pitched buffer d to the caller's host buffer, on the context's stream (no wait)
+int copy_patches_out(fpm_ctx* ctx, const fpm_patch_rect& r, size_t n, const uint8_t* d, size_t pitch, size_t pbytes,
+                     uint8_t* out, size_t row_stride, size_t patch_stride) {
     if (patch_stride == row_stride * (size_t)r.h) {   // the caller's patches are one run of rows
         HIP_TRY(hipMemcpy2DAsync(out, row_stride, d, pitch, r.w, (size_t)r.h * n, hipMemcpyDeviceToHost, ctx->stream));
     } else {
@@ -1931,8 +1946,138 @@ int patches_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
             HIP_TRY(hipMemcpy2DAsync(out + i * patch_stride, row_stride, d + i * pbytes, pitch, r.w, r.h,
                                      hipMemcpyDeviceToHost, ctx->stream));
     }
+    return FPM_OK;
+}
+
+// The host variants: the patches into the context's own buffer (row pitch a multiple of 64), then out to the caller's.
+int patches_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, uint8_t* out,
+                    size_t row_stride, size_t patch_stride, double* matrices) {
+    const size_t n = poses.size();
+    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
+    HIP_TRY(ctx->d_patch.ensure(pbytes * n));
+    uint8_t* d = ctx->d_patch.as<uint8_t>();
+    int rc = enqueue_patches(ctx, r, poses, d, pitch, pbytes, matrices);
+    if (rc == FPM_OK) rc = copy_patches_out(ctx, r, n, d, pitch, pbytes, out, row_stride, patch_stride);
+    if (rc != FPM_OK) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     prof_collect(ctx);
+    return FPM_OK;
+}
+
+// ---- patch comparison (fpm_last_compare, fpm_compare_at, fpm_compare_derive) ----
+constexpr int64_t kCompareMaxArea = (int64_t)1 << 22;   // n * sum_ii, sum_i^2 and n * sum_it stay below 2^62
+
+// Unlike a patch rectangle, a comparison rectangle lies inside the template: every patch pixel has one beneath it.
+int compare_rect(fpm_ctx* ctx, const fpm_patch_rect* rect, fpm_patch_rect* r) {
+    const int tw = ctx->tmpl[0].w, th = ctx->tmpl[0].h;
+    *r = rect ? *rect : fpm_patch_rect{0, 0, tw, th};
+    if (r->x < 0 || r->y < 0 || r->w < 1 || r->h < 1 || r->w > tw - r->x || r->h > th - r->y ||
+        (int64_t)r->w * r->h > kCompareMaxArea) {
+        ctx->err = "bad comparison rectangle: it must lie inside the template and hold 1 .. 2^22 pixels";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// What the sums give (include/fpm.h states the operation order; the file is built with -ffp-contract=off, so the
+// product and the sum of a table entry are two roundings).  lut may be null.
+void compare_derive(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt, int64_t sit, bool normalize,
+                    double* zncc, double* gain, double* offset, uint8_t* lut) {
+    const int64_t Di = n * sii - si * si, Dt = n * stt - st * st, N = n * sit - si * st;
+    const double sdi = std::sqrt((double)Di), sdt = std::sqrt((double)Dt);
+    *zncc = Di == 0 || Dt == 0 ? 0.0 : (double)N / (sdi * sdt);
+    double g = 1.0, o = 0.0;
+    if (normalize) {
+        g = Di == 0 ? 1.0 : sdt / sdi;
+        const double gi = g * (double)si;
+        o = ((double)st - gi) / (double)n;
+    }
+    *gain = g;
+    *offset = o;
+    if (!lut) return;
+    for (int v = 0; v < 256; ++v) {
+        const double gv = g * (double)v;
+        const double q = std::nearbyint(gv + o);   // the default rounding mode: ties to even
+        lut[v] = (uint8_t)std::min(255.0, std::max(0.0, q));
+    }
+}
+
+// The comparison of `poses` (n >= 1): one launch, or with FPM_COMPARE_NORMALIZE the sums, the tables built here from
+// them, and the deviations through the tables.  Returns when out (and diff) are filled.
+int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int threshold, int flags,
+                    fpm_compare_stats* out, uint8_t* diff, size_t row_stride, size_t patch_stride) {
+    const int n = (int)poses.size();
+    const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
+    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
+    uint8_t* d = nullptr;   // the difference images: the context's pitched buffer, as for the host patches
+    if (diff) {
+        HIP_TRY(ctx->d_patch.ensure(pbytes * (size_t)n));
+        d = ctx->d_patch.as<uint8_t>();
+    }
+    const size_t accb = sizeof(CompareAcc) * (size_t)n, lut_off = patch_tab_bytes(n);
+    int rc = stage_patch_jobs(ctx, r, poses, d, pitch, pbytes, nullptr, true, norm ? (size_t)256 * n : 0);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(ctx->d_cmpacc.ensure(accb));
+    HIP_TRY(ctx->h_cmpacc.ensure(accb));
+    HIP_TRY(hipMemsetAsync(ctx->d_cmpacc.p, 0, accb, ctx->stream));   // also "no pixel over the threshold" (CompareAcc)
+    const TmplLevel& t0 = ctx->tmpl[0];
+    CompareArgs c{};
+    c.p = patch_args(ctx, r, n, norm ? nullptr : d, pitch, pbytes);
+    c.tmpl = ctx->d_tmpl.as<uint8_t>() + t0.off;
+    c.tp = t0.pitch;
+    c.rx = r.x; c.ry = r.y;
+    c.threshold = threshold;
+    c.acc = ctx->d_cmpacc.as<CompareAcc>();
+    // bytes: source pixels read + template pixels read (+ difference pixels written), per launch
+    const int64_t px = (int64_t)n * r.w * r.h;
+    const char* too_many = "too many patch tiles for one launch";
+    {
+        ProfScope ps(ctx, FPM_K_COMPARE, (2 + (c.p.out ? 1 : 0)) * px);
+        if (!launch_patch_compare(c, norm ? kCompareSums : kCompareRaw, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
+    }
+    HIP_TRY(hipGetLastError());
+    CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
+    if (norm) {
+        // the sums to the host, a table per hit from them, the tables to the device beside the job table, then the
+        // second launch, which samples the footprints again
+        HIP_TRY(hipMemcpyAsync(h, ctx->d_cmpacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));   // also: the job table has left h_patchtab
+        const int64_t area = (int64_t)r.w * r.h;
+        uint8_t* luts = ctx->h_patchtab.as<uint8_t>(lut_off);
+        for (int i = 0; i < n; ++i) {
+            double z, g, o;
+            compare_derive(area, (int64_t)h[i].s[kCmpSumI], (int64_t)h[i].s[kCmpSumII], (int64_t)h[i].s[kCmpSumT],
+                           (int64_t)h[i].s[kCmpSumTT], (int64_t)h[i].s[kCmpSumIT], true, &z, &g, &o, luts + (size_t)256 * i);
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.as<uint8_t>(lut_off), luts, (size_t)256 * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+        c.p = patch_args(ctx, r, n, d, pitch, pbytes);
+        c.luts = ctx->d_patchtab.as<uint8_t>(lut_off);
+        {
+            ProfScope ps(ctx, FPM_K_COMPARE, (2 + (d ? 1 : 0)) * px);
+            if (!launch_patch_compare(c, kCompareDevLut, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_cmpacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
+    if (d) {
+        rc = copy_patches_out(ctx, r, (size_t)n, d, pitch, pbytes, diff, row_stride, patch_stride);
+        if (rc != FPM_OK) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    for (int i = 0; i < n; ++i) {
+        fpm_compare_stats& s = out[i];
+        s.n = (int64_t)r.w * r.h;
+        s.sum_i = (int64_t)h[i].s[kCmpSumI]; s.sum_ii = (int64_t)h[i].s[kCmpSumII];
+        s.sum_t = (int64_t)h[i].s[kCmpSumT]; s.sum_tt = (int64_t)h[i].s[kCmpSumTT];
+        s.sum_it = (int64_t)h[i].s[kCmpSumIT]; s.sum_abs = (int64_t)h[i].s[kCmpSumAbs];
+        const uint32_t* m = h[i].m;
+        s.n_over = (int32_t)m[kCmpNOver - kCmpNOver]; s.max_abs = (int32_t)m[kCmpMaxAbs - kCmpNOver];
+        s.x0 = r.w - (int32_t)m[kCmpX0 - kCmpNOver]; s.y0 = r.h - (int32_t)m[kCmpY0 - kCmpNOver];
+        s.x1 = (int32_t)m[kCmpX1 - kCmpNOver] - 1; s.y1 = (int32_t)m[kCmpY1 - kCmpNOver] - 1;
+        compare_derive(s.n, s.sum_i, s.sum_ii, s.sum_t, s.sum_tt, s.sum_it, norm, &s.zncc, &s.gain, &s.offset, nullptr);
+    }
     return FPM_OK;
 }
 
@@ -1998,6 +2143,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_imgtab.release(); ctx->h_imgtab.release();
     if (ctx->in_ev) (void)hipEventDestroy(ctx->in_ev);
     ctx->d_patchtab.release(); ctx->h_patchtab.release(); ctx->d_patch.release();
+    ctx->d_cmpacc.release(); ctx->h_cmpacc.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -2289,12 +2435,13 @@ int fpm_set_patch_form(fpm_ctx* ctx, int32_t form) {
     return FPM_OK;
 }
 
-// state, rectangle, poses and capacity of a fpm_last_patches* call; FPM_OK with poses empty = nothing to do
+// state, rectangle, poses and capacity of a fpm_last_patches* / fpm_last_compare call; FPM_OK with poses empty =
+// nothing to do.  inside: the rectangle is a comparison's (within the template).
 static int last_patches_begin(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t cap, int32_t* n_patches,
-                              fpm_patch_rect* r, std::vector<PatchPose>& poses) {
+                              fpm_patch_rect* r, std::vector<PatchPose>& poses, bool inside = false) {
     *n_patches = 0;
     int rc = patch_state(ctx, true);
-    if (rc == FPM_OK) rc = patch_rect(ctx, rect, r);
+    if (rc == FPM_OK) rc = inside ? compare_rect(ctx, rect, r) : patch_rect(ctx, rect, r);
     if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
     if (rc != FPM_OK) return rc;
     *n_patches = (int32_t)poses.size();
@@ -2360,6 +2507,61 @@ int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_
     for (int i = 0; i < n; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
     HIP_TRY(hipSetDevice(ctx->device));
     return patches_to_host(ctx, r, poses, out, row_stride, patch_stride, matrices);
+}
+
+// --- patch comparison -----------------------------------------------------------------
+int fpm_compare_derive(int64_t n, int64_t sum_i, int64_t sum_ii, int64_t sum_t, int64_t sum_tt, int64_t sum_it,
+                       int32_t normalize, double* zncc, double* gain, double* offset, uint8_t lut[256]) {
+    if (!zncc || !gain || !offset || n < 1 || n > kCompareMaxArea) return FPM_E_INVALID_ARG;
+    // sums of n bytes and of their products, so that the three determinants are exact in 64 bits
+    if (sum_i < 0 || sum_i > 255 * n || sum_t < 0 || sum_t > 255 * n || sum_ii < 0 || sum_ii > 65025 * n || sum_tt < 0 ||
+        sum_tt > 65025 * n || sum_it < 0 || sum_it > 65025 * n)
+        return FPM_E_INVALID_ARG;
+    if (n * sum_ii < sum_i * sum_i || n * sum_tt < sum_t * sum_t) return FPM_E_INVALID_ARG;   // of no pixels (Cauchy-Schwarz)
+    compare_derive(n, sum_i, sum_ii, sum_t, sum_tt, sum_it, normalize != 0, zncc, gain, offset, lut);
+    return FPM_OK;
+}
+
+static int compare_args(fpm_ctx* ctx, int32_t threshold, int32_t flags) {
+    if (threshold < 0 || threshold > 255) { ctx->err = "threshold must be 0 .. 255"; return FPM_E_INVALID_ARG; }
+    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown comparison flags"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+int fpm_last_compare(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t threshold, int32_t flags,
+                     fpm_compare_stats* out, int32_t cap, int32_t* n, uint8_t* diff, size_t row_stride,
+                     size_t patch_stride) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = compare_args(ctx, threshold, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    rc = last_patches_begin(ctx, rect, source, cap, n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
+    if (diff && (rc = check_patch_out(ctx, diff, r, row_stride, patch_stride)) != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return compare_to_host(ctx, r, poses, threshold, flags, out, diff, row_stride, patch_stride);
+}
+
+int fpm_compare_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                   const double* angles, int32_t n_poses, int32_t threshold, int32_t flags, fpm_compare_stats* out,
+                   uint8_t* diff, size_t row_stride, size_t patch_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = compare_args(ctx, threshold, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
+    if (diff && (rc = check_patch_out(ctx, diff, r, row_stride, patch_stride)) != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return compare_to_host(ctx, r, poses, threshold, flags, out, diff, row_stride, patch_stride);
 }
 
 // --- angle sharding of one search ---------------------------------------------------------

@@ -229,6 +229,31 @@ struct PatchArgs {
 // k_patch_warp: one workgroup per 64 x 16 output tile.  Returns false, launching nothing, when the grid would exceed
 // 2^31 - 1 workgroups.
 bool launch_patch_warp(PatchArgs a, hipStream_t st);
+// ---- patch comparison (fpm_last_compare / fpm_compare_at): the patches of a job table against
+// the template pixels beneath them, reduced to one record per patch; the patch itself is never written.
+// The fields a workgroup reduces, in the order of its LDS partials: sums first, then maxima.
+enum { kCmpSumI, kCmpSumII, kCmpSumT, kCmpSumTT, kCmpSumIT, kCmpSumAbs, kCmpNOver, kCmpMaxAbs, kCmpX0, kCmpY0, kCmpX1,
+       kCmpY1, kCompareFields };
+// One record per patch, zero-filled before the launch.  m = n_over, max_abs, then the box of the pixels over the
+// threshold as maxima: pw - x0, ph - y0, x1 + 1, y1 + 1 (all 0 = no such pixel).
+struct CompareAcc {
+    uint64_t s[6];           // kCmpSumI .. kCmpSumAbs
+    uint32_t m[6];           // kCmpNOver .. kCmpY1
+};
+struct CompareArgs {
+    PatchArgs p;             // jobs, sources and patch size as for k_patch_warp; out = the difference images or null
+    const uint8_t* tmpl;     // template level 0, row pitch tp (a multiple of 64)
+    int32_t tp;
+    int32_t rx, ry;          // the rectangle's origin in the template (the rectangle lies inside it)
+    int32_t threshold;       // a pixel counts as deviating when d > threshold
+    const uint8_t* luts;     // [njobs][256] (kCompareDevLut), 4-byte aligned
+    CompareAcc* acc;         // [njobs]
+};
+// the launches of a comparison: everything at once without a table; or the sums, then (the host having built the
+// tables from them) the deviations through the tables
+enum { kCompareRaw, kCompareSums, kCompareDevLut };
+// k_patch_compare, k_patch_warp's grid.  Returns false, launching nothing, for a grid past 2^31 - 1 or an unknown form.
+bool launch_patch_compare(CompareArgs c, int form, hipStream_t st);
 void launch_ncc_map(const NccJob* jobs, int njobs, int max_out, int tmpl_bytes, hipStream_t st);
 bool ncc_tile_fits(int tw, int th);   // LDS-tiled variant applies (templates up to 128 x 64)
 void launch_ncc_tile(const NccJob* jobs, int njobs, int max_ow, int max_oh, int tw, int th, hipStream_t st);

@@ -2629,14 +2629,25 @@ constexpr int kPatchTw = 64, kPatchTh = 16;
 constexpr int kPatchFtPitch = 76;   // footprint row pitch in LDS: 19 dwords (odd: row-strided byte gathers spread over the banks)
 constexpr int kPatchFtRows = 72;
 
-__global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
-    __shared__ __attribute__((aligned(16))) int32_t tab[2 * kPatchTw + 2 * kPatchTh];
-    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtPitch * kPatchFtRows + 16];
+constexpr int kPatchTabWords = 2 * kPatchTw + 2 * kPatchTh;          // ad, bd, X0, Y0
+constexpr int kPatchFtBytes = kPatchFtPitch * kPatchFtRows + 16;
+
+// What the lanes of a workgroup share about their tile once patch_tile_stage has run (k_patch_warp, k_patch_compare).
+struct PatchTile {
+    int job;                 // the patch (index into PatchArgs::jobs)
+    int x0, y0;              // the tile's first pixel in the patch
+    int bxa, by0;            // source column of the footprint's byte 0, and its first source row
+    bool in_lds;             // the footprint is staged in FT; else the taps go to global memory through warp_tap
+    const uint8_t* img;      // level 0 of the job's source
+};
+
+// The tile of this workgroup: the fixed-point terms into `tab`, the footprint into `FT` where it lies inside the
+// image and fits.  Holds barriers: every lane of the workgroup calls it.  On return tab and FT may be read.
+__device__ __forceinline__ PatchTile patch_tile_stage(const PatchArgs& a, int32_t* tab, uint8_t* FT, int tid) {
     int32_t* const ad = tab;
     int32_t* const bd = tab + kPatchTw;
     int32_t* const X0 = tab + 2 * kPatchTw;
     int32_t* const Y0 = X0 + kPatchTh;
-    const int tid = threadIdx.x;
     // neighbouring tiles share footprint lines and output lines: keep them on one XCD's L2 (speed only)
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tiles = a.tiles_x * a.tiles_y;
@@ -2679,12 +2690,15 @@ __global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
         stage_block4(FT, kPatchFtPitch, img + (size_t)by0 * a.sp + bxa, (size_t)a.sp, fth, wpr, bxa, a.sp, tid, 256);
         __syncthreads();
     }
-    const int r = tid >> 4, gx = (tid & 15) * 4;
-    const int x = x0 + gx, y = y0 + r;
-    if (x >= a.pw || y >= a.ph) return;
-    const int nu = a.pw - x < 4 ? a.pw - x : 4;
-    const int Xr = X0[r], Yr = Y0[r];
-    const int4 A = *(const int4*)(ad + gx), B = *(const int4*)(bd + gx);
+    return {p, x0, y0, bxa, by0, in_lds, img};
+}
+
+// The first `nu` (0 .. 4) of the 4 adjacent pixels of tile row r from tile column gx, packed low byte first; the
+// bytes from nu on are 0.
+__device__ __forceinline__ uint32_t patch_sample4(const PatchArgs& a, const PatchTile& T, const int32_t* tab,
+                                                  const uint8_t* FT, int r, int gx, int nu) {
+    const int Xr = tab[2 * kPatchTw + r], Yr = tab[2 * kPatchTw + kPatchTh + r];
+    const int4 A = *(const int4*)(tab + gx), B = *(const int4*)(tab + kPatchTw + gx);
     const int av[4] = {A.x, A.y, A.z, A.w}, bv[4] = {B.x, B.y, B.z, B.w};
     uint32_t word = 0;
 #pragma unroll
@@ -2692,18 +2706,206 @@ __global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
         if (u >= nu) break;
         const int X = (Xr + av[u]) >> (kAbBits - kInterBits), Y = (Yr + bv[u]) >> (kAbBits - kInterBits);
         int v;
-        if (in_lds)
-            v = ft_tap_bytes(FT, ((Y >> kInterBits) - by0) * kPatchFtPitch + (X >> kInterBits) - bxa, kPatchFtPitch, X, Y);
+        if (T.in_lds)
+            v = ft_tap_bytes(FT, ((Y >> kInterBits) - T.by0) * kPatchFtPitch + (X >> kInterBits) - T.bxa, kPatchFtPitch, X, Y);
         else
-            v = warp_tap(img, a.sw, a.sh, a.sp, X, Y, 0);
+            v = warp_tap(T.img, a.sw, a.sh, a.sp, X, Y, 0);
         word |= (uint32_t)v << (8 * u);
     }
-    uint8_t* d = a.out + j.out_off + (size_t)y * a.row_stride + x;
-    if (a.dword && nu == 4) {
+    return word;
+}
+
+// nu pixels of `word` to d: one dword where the output allows it, else bytes
+__device__ __forceinline__ void patch_store4(uint8_t* d, uint32_t word, int nu, bool dword) {
+    if (dword && nu == 4) {
         *(uint32_t*)d = word;
     } else {
         for (int u = 0; u < nu; ++u) d[u] = (uint8_t)(word >> (8 * u));
     }
+}
+
+__global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    const int tid = threadIdx.x;
+    const PatchTile T = patch_tile_stage(a, tab, FT, tid);
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = T.x0 + gx, y = T.y0 + r;
+    if (x >= a.pw || y >= a.ph) return;
+    const int nu = a.pw - x < 4 ? a.pw - x : 4;
+    const uint32_t word = patch_sample4(a, T, tab, FT, r, gx, nu);
+    patch_store4(a.out + a.jobs[T.job].out_off + (size_t)y * a.row_stride + x, word, nu, a.dword != 0);
+}
+
+// k_patch_compare (fpm_last_compare / fpm_compare_at): k_patch_warp's tile, sampled the same
+// way (patch_tile_stage / patch_sample4), but the patch is never written: each lane reads the 4 template pixels
+// beneath its 4 patch pixels and the workgroup reduces to a handful of integers, which it adds to the hit's record.
+//   SUMS: sum I, I^2, T, T^2, I*T (v_dot4_u32_u8 on the packed words; a tile's largest sum is 1024 * 65025 < 2^26)
+//   DEV:  d = |L[I] - T| per pixel: sum d, max d, the count of d > threshold and those pixels' bounding box
+//   LUT:  L = the job's 256-byte table, staged in LDS (else L = identity)
+//   IMG:  d is also stored as the difference image (PatchArgs::out, as k_patch_warp stores the patch)
+// Lanes past the patch's right or bottom edge take part in every barrier and in the reduction with nu = 0: they
+// sample nothing, read no template byte and add nothing.  The reduction is by DPP within a wave for the sums and the
+// maximum and by lane votes (__ballot, then scalar bit counts) for the count and the box, through LDS across the four
+// waves, then one integer atomic per field and workgroup (fields that are 0 are skipped: they would not change the
+// record), so the record does not depend on the order of the workgroups.  The box's minima are kept as
+// maxima of (pw - x) and (ph - y) and its maxima as (x + 1) and (y + 1): 0, the record's fill, then means "none".
+template <int CTRL, int ROWS, bool MAX>
+__device__ __forceinline__ uint32_t dpp_fold(uint32_t v) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
+    return MAX ? (o > v ? o : v) : v + o;
+}
+// wave sum or maximum of a u32 in every lane: wave_better_reduce's steps (0 is the identity of both)
+template <bool MAX>
+__device__ __forceinline__ uint32_t wave_fold(uint32_t v) {
+    v = dpp_fold<0xb1, 0xf, MAX>(v);    // quad_perm [1,0,3,2]
+    v = dpp_fold<0x4e, 0xf, MAX>(v);    // quad_perm [2,3,0,1]
+    v = dpp_fold<0x141, 0xf, MAX>(v);   // row_half_mirror
+    v = dpp_fold<0x140, 0xf, MAX>(v);   // row_mirror
+    v = dpp_fold<0x142, 0xa, MAX>(v);   // row_bcast15 into rows 1 and 3
+    v = dpp_fold<0x143, 0xc, MAX>(v);   // row_bcast31 into rows 2 and 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The votes of a wave's lanes on their pixel u (lane l: tile row l / 16 of the wave's four, tile column 4 (l % 16) + u)
+// into the count of the pixels voted for and the box of their tile columns and rows.  Scalar work: mk is wave-uniform.
+__device__ __forceinline__ void vote_box(unsigned long long mk, int u, int& cnt, int& cmin, int& cmax, int& rmin,
+                                         int& rmax) {
+    if (mk == 0) return;
+    cnt += __popcll(mk);
+    const uint32_t cols = (uint32_t)(mk | (mk >> 16) | (mk >> 32) | (mk >> 48)) & 0xffffu;
+    const int lo = 4 * (__ffs(cols) - 1) + u, hi = 4 * (31 - __clz(cols)) + u;
+    cmin = lo < cmin ? lo : cmin; cmax = hi > cmax ? hi : cmax;
+    const int rlo = (__ffsll(mk) - 1) >> 4, rhi = (63 - __clzll(mk)) >> 4;
+    rmin = rlo < rmin ? rlo : rmin; rmax = rhi > rmax ? rhi : rmax;
+}
+
+template <bool SUMS, bool DEV, bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
+    __shared__ uint32_t part[4][kCompareFields];
+    const PatchArgs& a = c.p;
+    const int tid = threadIdx.x;
+    if (LUT) {
+        // the job index as patch_tile_stage derives it; the helper's first barrier orders these writes before any read
+        const int job = xcd_remap(blockIdx.x, gridDim.x) / (a.tiles_x * a.tiles_y);
+        if (tid < 64) ((uint32_t*)lut)[tid] = ((const uint32_t*)(c.luts + (size_t)job * 256))[tid];
+    }
+    const PatchTile T = patch_tile_stage(a, tab, FT, tid);
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = T.x0 + gx, y = T.y0 + r;
+    const int left = a.pw - x;
+    const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
+    const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
+    // the template's 4 bytes beneath: an aligned dword pair funnel-shifted to the group's first byte (the row pitch is
+    // a multiple of 64 and the rectangle lies inside the template: the first dword is inside the row, the second is
+    // read only where it is too), cut to nu bytes
+    uint32_t tw = 0;
+    if (nu > 0) {
+        const int tx = c.rx + x;
+        const uint8_t* trow = c.tmpl + (size_t)(c.ry + y) * c.tp;
+        const int c0 = tx & ~3;
+        const uint32_t lo = *(const uint32_t*)(trow + c0);
+        const uint32_t hi = (tx & 3) && c0 + 4 < c.tp ? *(const uint32_t*)(trow + c0 + 4) : 0u;
+        tw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)tx);
+        if (nu < 4) tw &= (1u << (8 * nu)) - 1u;
+    }
+    // wave totals (the same value in every lane) of the fields this form emits
+    uint32_t wv[kCompareFields];
+#pragma unroll
+    for (int k = 0; k < kCompareFields; ++k) wv[k] = 0;
+    if (SUMS) {
+        // a wave's 256 pixels sum to at most 65280: sum I and sum T share one word, and one fold
+        const uint32_t it = wave_fold<false>(__builtin_amdgcn_udot4(iw, 0x01010101u, 0u, false) +
+                                             (__builtin_amdgcn_udot4(tw, 0x01010101u, 0u, false) << 16));
+        wv[kCmpSumI] = it & 0xffffu;
+        wv[kCmpSumT] = it >> 16;
+        wv[kCmpSumII] = wave_fold<false>(__builtin_amdgcn_udot4(iw, iw, 0u, false));
+        wv[kCmpSumTT] = wave_fold<false>(__builtin_amdgcn_udot4(tw, tw, 0u, false));
+        wv[kCmpSumIT] = wave_fold<false>(__builtin_amdgcn_udot4(iw, tw, 0u, false));
+    }
+    if (DEV) {
+        uint32_t dw = 0, dmax = 0, over = 0;   // over: bit u = pixel u deviates by more than the threshold
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = (iw >> (8 * u)) & 255, t = (tw >> (8 * u)) & 255;
+            const int l = LUT ? (int)lut[i] : i;
+            const uint32_t d = u < nu ? (uint32_t)(l > t ? l - t : t - l) : 0u;   // past the edge: nothing (L[0] may not be 0)
+            dw |= d << (8 * u);
+            dmax = d > dmax ? d : dmax;
+            over |= (uint32_t)((int)d > c.threshold) << u;
+        }
+        if (IMG && nu > 0)
+            patch_store4(a.out + a.jobs[T.job].out_off + (size_t)y * a.row_stride + x, dw, nu, a.dword != 0);
+        wv[kCmpSumAbs] = wave_fold<false>(__builtin_amdgcn_udot4(dw, 0x01010101u, 0u, false));
+        wv[kCmpMaxAbs] = wave_fold<true>(dmax);
+        // the count and the box from the lanes' votes, in scalar registers
+        int cnt = 0, cmin = kPatchTw, cmax = -1, rmin = 4, rmax = -1;
+        vote_box(__ballot(over & 1u), 0, cnt, cmin, cmax, rmin, rmax);
+        vote_box(__ballot(over & 2u), 1, cnt, cmin, cmax, rmin, rmax);
+        vote_box(__ballot(over & 4u), 2, cnt, cmin, cmax, rmin, rmax);
+        vote_box(__ballot(over & 8u), 3, cnt, cmin, cmax, rmin, rmax);
+        if (cnt > 0) {
+            const int wy = T.y0 + 4 * (tid >> 6);   // the wave's first tile row in the patch
+            wv[kCmpNOver] = (uint32_t)cnt;
+            wv[kCmpX0] = (uint32_t)(a.pw - (T.x0 + cmin));
+            wv[kCmpX1] = (uint32_t)(T.x0 + cmax + 1);
+            wv[kCmpY0] = (uint32_t)(a.ph - (wy + rmin));
+            wv[kCmpY1] = (uint32_t)(wy + rmax + 1);
+        }
+    }
+    if ((tid & 63) == 0) {
+        const int wave = tid >> 6;
+#pragma unroll
+        for (int k = 0; k < kCompareFields; ++k)
+            if (k < kCmpSumAbs ? SUMS : DEV) part[wave][k] = wv[k];
+    }
+    __syncthreads();
+    if (tid < kCompareFields && (tid < kCmpSumAbs ? SUMS : DEV)) {
+        const uint32_t p0 = part[0][tid], p1 = part[1][tid], p2 = part[2][tid], p3 = part[3][tid];
+        CompareAcc* acc = c.acc + T.job;
+        if (tid >= kCmpMaxAbs) {
+            const uint32_t m01 = p0 > p1 ? p0 : p1, m23 = p2 > p3 ? p2 : p3, m = m01 > m23 ? m01 : m23;
+            if (m) atomicMax(&acc->m[tid - kCmpNOver], m);
+        } else {
+            const uint32_t s = p0 + p1 + p2 + p3;
+            if (s == 0) return;
+            if (tid == kCmpNOver) atomicAdd(&acc->m[0], s);
+            else atomicAdd((unsigned long long*)&acc->s[tid], (unsigned long long)s);
+        }
+    }
+}
+
+template <bool SUMS, bool DEV, bool LUT, bool IMG>
+static void launch_compare_form(const CompareArgs& c, unsigned grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_patch_compare<SUMS, DEV, LUT, IMG>), dim3(grid), dim3(256), 0, st, c);
+}
+
+bool launch_patch_compare(CompareArgs c, int form, hipStream_t st) {
+    PatchArgs& a = c.p;
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX) return false;
+    const bool img = a.out != nullptr;
+    const unsigned g = (unsigned)grid;
+    switch (form) {
+    case kCompareRaw:
+        if (img) launch_compare_form<true, true, false, true>(c, g, st);
+        else launch_compare_form<true, true, false, false>(c, g, st);
+        return true;
+    case kCompareSums:
+        launch_compare_form<true, false, false, false>(c, g, st);
+        return true;
+    case kCompareDevLut:
+        if (img) launch_compare_form<false, true, true, true>(c, g, st);
+        else launch_compare_form<false, true, true, false>(c, g, st);
+        return true;
+    }
+    return false;
 }
 
 bool launch_patch_warp(PatchArgs a, hipStream_t st) {

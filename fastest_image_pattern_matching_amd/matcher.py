@@ -264,6 +264,46 @@ def patch_matrix(src_w: int, src_h: int, lt, angle: float, rect_xy=(0, 0)) -> np
     return np.array(m[:], np.float64).reshape(2, 3)
 
 
+# -- patch comparison (fpm_last_compare / fpm_compare_at / fpm_compare_derive) ---------------------------------------
+COMPARE_MAX_AREA = 1 << 22
+# one row per hit: fpm_compare_stats, field for field
+COMPARE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.CompareStats._fields_], align=True)
+assert COMPARE_DTYPE.itemsize == C.sizeof(L.CompareStats)
+
+
+def compare_rect(rect, tw: int, th: int) -> Tuple[int, int, int, int]:
+    """A comparison rectangle (x, y, w, h) for a ``tw`` x ``th`` template as four ints; None = the whole template.
+    Unlike a patch rectangle it must lie inside the template, and hold at most 2^22 pixels (include/fpm.h).  Raises
+    ValueError otherwise.  Pure: no device."""
+    if rect is None:
+        x, y, w, h = 0, 0, int(tw), int(th)
+    else:
+        try:
+            x, y, w, h = (int(v) for v in rect)
+        except (TypeError, ValueError):
+            raise ValueError(f"expected a rectangle (x, y, w, h), got {rect!r}") from None
+        if any(float(v) != i for v, i in zip(rect, (x, y, w, h))):
+            raise ValueError(f"rectangle {tuple(rect)!r} must hold whole numbers")
+    if x < 0 or y < 0 or w < 1 or h < 1 or x + w > tw or y + h > th:
+        raise ValueError(f"rectangle {(x, y, w, h)} must lie inside the {tw} x {th} template")
+    if w * h > COMPARE_MAX_AREA:
+        raise ValueError(f"rectangle {(x, y, w, h)} holds more than 2^22 pixels")
+    return x, y, w, h
+
+
+def compare_derive(n: int, sum_i: int, sum_ii: int, sum_t: int, sum_tt: int, sum_it: int, normalize: bool = False):
+    """fpm_compare_derive: ``(zncc, gain, offset, lut)`` -- what the comparison derives from a hit's integer sums, by the
+    engine's own code (f64 in the order include/fpm.h states; ``lut`` the uint8 [256] table).  Host only (no device).
+    Raises ValueError for sums that are those of no ``n`` bytes."""
+    z, g, o = C.c_double(), C.c_double(), C.c_double()
+    lut = np.zeros(256, np.uint8)
+    rc = L.load().fpm_compare_derive(int(n), int(sum_i), int(sum_ii), int(sum_t), int(sum_tt), int(sum_it),
+                                     1 if normalize else 0, C.byref(z), C.byref(g), C.byref(o), L.u8ptr(lut))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_compare_derive failed with {rc}")
+    return z.value, g.value, o.value, lut
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -608,6 +648,10 @@ class TemplateMatcher:
         r = self._patch_rect(rect)
         if r is not None:
             return r.w, r.h
+        return self._template_size()
+
+    def _template_size(self) -> Tuple[int, int]:
+        """(tw, th) of the learned template."""
         w, h, eq = C.c_int32(), C.c_int32(), C.c_int32()
         d = C.c_double()
         if self._lib.fpm_template_level(self._ctx, 0, C.byref(w), C.byref(h), C.byref(d), C.byref(d), C.byref(d),
@@ -719,6 +763,74 @@ class TemplateMatcher:
         if rc != L.FPM_OK:
             self._patch_fail(rc, "patches_at")
         return (out, mats) if matrices else out
+
+    # -- patch comparison: every hit against the template, reduced on the device (fpm_last_compare / fpm_compare_at) ---
+    def _compare_rect(self, rect):
+        """(fpm_patch_rect or None, w, h) of a comparison: ``rect``, else the user-defined rectangle when one is set and
+        lies inside the template, else the whole template (NULL)."""
+        tw, th = self._template_size()
+        if rect is None and self._user_rect is not None:
+            try:
+                rect = compare_rect(self._user_rect, tw, th)
+            except ValueError:
+                rect = None
+        if rect is None:
+            return None, tw, th
+        x, y, w, h = compare_rect(rect, tw, th)
+        return L.PatchRect(x, y, w, h), w, h
+
+    @staticmethod
+    def _compare_diff(diff, n, h, w):
+        """(array or None, pointer, row_stride, patch_stride) of the difference images asked for by ``diff``."""
+        if not diff:
+            return None, None, 0, 0
+        img = np.zeros((n, h, w), np.uint8)
+        return img, L.u8ptr(img), w, w * h
+
+    def last_compare(self, source: int = 0, rect=None, threshold: int = 16, normalize: bool = False, diff: bool = False):
+        """Every result of the last search compared with the learned template where the pixels are: a structured array
+        (COMPARE_DTYPE), one row per result of ``source`` in result order (``source=-1``: all sources, in source order).
+        Per row the exact integer sums over the rectangle (n, sum_i, sum_ii, sum_t, sum_tt, sum_it: I = the pixels
+        last_patches gives, T = the template's), zncc, and the deviations d = |LUT[I] - T|: sum_abs, max_abs, n_over
+        = pixels with d > ``threshold`` and their inclusive bounding box x0, y0, x1, y1 in rectangle coordinates (w, h,
+        -1, -1 when there is none).  ``normalize`` first fits the hit's gain and offset to the template's (a change
+        of lighting is then no deviation; gain and offset are reported).  ``rect``: (x, y, w, h) inside the template;
+        None = the user-defined rectangle when one is set and lies inside the template, else the whole template.
+        ``diff=True``: also d as uint8 images, ``(stats, (n, h, w))``.  No patch is written anywhere."""
+        r, w, h = self._compare_rect(rect)
+        pr = C.byref(r) if r is not None else None
+        flags = L.COMPARE_NORMALIZE if normalize else 0
+        n = C.c_int32()
+        rc = self._lib.fpm_last_compare(self._ctx, pr, int(source), int(threshold), flags, None, 0, C.byref(n), None, 0, 0)
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_compare")
+        stats = np.zeros(n.value, COMPARE_DTYPE)
+        img, pimg, row, patch = self._compare_diff(diff, n.value, h, w)
+        if n.value:
+            rc = self._lib.fpm_last_compare(self._ctx, pr, int(source), int(threshold), flags,
+                                            stats.ctypes.data_as(C.POINTER(L.CompareStats)), n.value, C.byref(n), pimg,
+                                            row, patch)
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_compare")
+        return (stats, img) if diff else stats
+
+    def compare_at(self, src_index, lts, angles, rect=None, threshold: int = 16, normalize: bool = False,
+                   diff: bool = False):
+        """last_compare at poses the caller supplies, on the staged sources (fpm_compare_at); poses as patches_at.
+        Needs staged sources, not a search."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        r, w, h = self._compare_rect(rect)
+        n = len(idx)
+        stats = np.zeros(n, COMPARE_DTYPE)
+        img, pimg, row, patch = self._compare_diff(diff, n, h, w)
+        rc = self._lib.fpm_compare_at(self._ctx, C.byref(r) if r is not None else None,
+                                      idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
+                                      ang.ctypes.data_as(C.POINTER(C.c_double)), n, int(threshold),
+                                      L.COMPARE_NORMALIZE if normalize else 0,
+                                      stats.ctypes.data_as(C.POINTER(L.CompareStats)), pimg, row, patch)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "compare_at")
+        return (stats, img) if diff else stats
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------
     def pyr_down(self, img) -> np.ndarray:

@@ -246,6 +246,55 @@ int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_
 #define FPM_PATCH_FORM_WARP 1
 int fpm_set_patch_form(fpm_ctx* ctx, int32_t form);
 
+/* --- patch comparison: every hit against the learned template, on the device ---------------------------------------
+ * Locate, rectify, inspect: what a caller does with a patch is compare it with the template it was found by.  These
+ * entries do that where the pixels are -- level 0 of the sources and of the template are both in device memory after a
+ * search -- and return a few numbers per hit; no patch is written.
+ * Rectangle.  (x, y, w, h) in template coordinates, and unlike a patch rectangle inside the template: 0 <= x, 0 <= y,
+ * x + w <= tw, y + h <= th, 1 <= w * h <= 2^22; NULL = the whole template.  Anything else is FPM_E_INVALID_ARG.
+ * Pixels.  I(u, v) is the pixel (u, v) of the patch fpm_last_patches gives for that rectangle and pose (same matrix,
+ * same fixed-point bilinear arithmetic, border 0, the inverted plane under bitwise_not); T(u, v) is template level 0
+ * at (x + u, y + v).
+ * Sums, exact integers: n = w * h, sum_i = sum I, sum_ii = sum I^2, sum_t = sum T, sum_tt = sum T^2, sum_it = sum I T.
+ * With Di = n sum_ii - sum_i^2, Dt = n sum_tt - sum_t^2, N = n sum_it - sum_i sum_t (exact in int64 under the area cap):
+ *     zncc = (double)N / (sqrt((double)Di) * sqrt((double)Dt)), or 0.0 when Di == 0 or Dt == 0.
+ * Normalisation (FPM_COMPARE_NORMALIZE) fits the hit's gain and offset to the template's, so that a change of lighting
+ * is no deviation:
+ *     gain = sqrt((double)Dt) / sqrt((double)Di), or 1.0 when Di == 0
+ *     offset = ((double)sum_t - gain * (double)sum_i) / (double)n
+ *     LUT[v] = (uint8) min(255, max(0, rint(gain * (double)v + offset))), v = 0 .. 255
+ * in f64, the product and the sum rounded separately (no fused multiply-add), rint in the default rounding mode (ties
+ * to even).  Without the flag LUT is the identity, gain = 1, offset = 0.
+ * Deviations.  d(u, v) = |LUT[I(u, v)] - T(u, v)|: sum_abs = sum d, max_abs = max d, n_over = the number of pixels with
+ * d > threshold (threshold 0 .. 255), (x0, y0, x1, y1) = the inclusive bounding box of those pixels in rectangle
+ * coordinates; with n_over == 0: x0 = w, y0 = h, x1 = y1 = -1.
+ * Difference image (diff, may be NULL): d as u8, one w x h image per hit, image i at diff + i * patch_stride, rows
+ * row_stride apart (the rules of fpm_last_patches; the bytes of a row past w are left untouched).
+ * A call without the flag is one launch of k_patch_compare; with it two, with a copy of the sums to the host between
+ * them, where the tables are built.  Additive entries: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_compare_stats {
+    int64_t n, sum_i, sum_ii, sum_t, sum_tt, sum_it, sum_abs;
+    int32_t n_over, max_abs, x0, y0, x1, y1;
+    double zncc, gain, offset;
+} fpm_compare_stats;
+#define FPM_COMPARE_NORMALIZE 1   /* flags */
+
+/* The hits of the last search, in result order; source, cap, *n and every state rule as fpm_last_patches (source = -1:
+ * all sources in source order; cap below the count: FPM_E_CAPACITY with the count in *n, nothing written; cap = 0
+ * with out = NULL asks for the count).  Returns when out (and diff) are filled. */
+int fpm_last_compare(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t threshold, int32_t flags,
+                     fpm_compare_stats* out, int32_t cap, int32_t* n, uint8_t* diff, size_t row_stride,
+                     size_t patch_stride);
+/* The same at caller-supplied poses on the staged sources; poses as fpm_patches_at. */
+int fpm_compare_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                   const double* angles, int32_t n_poses, int32_t threshold, int32_t flags, fpm_compare_stats* out,
+                   uint8_t* diff, size_t row_stride, size_t patch_stride);
+/* host only, no context: what the engine derives from the sums by the rules above.  zncc, gain and offset must not be
+ * NULL; lut may be.  normalize = 0: gain 1, offset 0, the identity table.  FPM_E_INVALID_ARG for n outside 1 .. 2^22
+ * and for sums that are those of no n bytes (negative, above 255 n or 65025 n, or Di < 0 or Dt < 0). */
+int fpm_compare_derive(int64_t n, int64_t sum_i, int64_t sum_ii, int64_t sum_t, int64_t sum_tt, int64_t sum_it,
+                       int32_t normalize, double* zncc, double* gain, double* offset, uint8_t lut[256]);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent
@@ -390,7 +439,10 @@ int fpm_search_bytes(const fpm_ctx* ctx, int64_t* b_pyr, int64_t* b_top, int64_t
 #define FPM_K_NOT 12        /* k_bitwise_not: 255 - source over the staged level 0 (fpm_params.bitwise_not) */
 #define FPM_K_PATCH 13      /* k_patch_warp (or k_warp, fpm_set_patch_form): the patches of fpm_last_patches* / fpm_patches_at;
                                bytes = pixels written + as many source pixels read */
-#define FPM_K_COUNT 14
+#define FPM_K_COMPARE 14    /* k_patch_compare: the launches of fpm_last_compare / fpm_compare_at (one, or two with
+                               FPM_COMPARE_NORMALIZE); bytes = source pixels read + template pixels read + difference
+                               pixels written */
+#define FPM_K_COUNT 15
 int fpm_profile_enable(fpm_ctx* ctx, int32_t enable);
 int fpm_profile_reset(fpm_ctx* ctx);
 int fpm_profile_get(const fpm_ctx* ctx, int32_t kernel, double* total_ms, int64_t* launches,

@@ -27,7 +27,7 @@ FPM_E_INTERNAL = -6
 FMT_COUNT = 7
 
 (K_PYR, K_TOP_WARP, K_TOP_NCC, K_TOP_NMS, K_CAND_INIT, K_ROI_TABLES, K_ROI_WARP, K_ROI_CORR, K_ROI_EVAL, K_ROI_SMALL,
- K_CAND_STEP, K_TOP_MAP, K_NOT, K_PATCH, K_COMPARE) = range(15)
+ K_CAND_STEP, K_TOP_MAP, K_NOT, K_PATCH, K_COMPARE, K_LEARN) = range(16)
 # profiling index -> kernel (include/fpm.h FPM_K_*); top_ncc is k_top_mma (matrix-core top layer) where it applies, else
 # k_ncc_tile for templates up to 128 x 64; top_map = k_top_map, the matrix-core form's fallback (full maps for the jobs
 # its lists left); bitwise_not = k_bitwise_not, 255 - source over the staged level 0 (Params.bitwise_not); patch_warp =
@@ -35,6 +35,12 @@ FMT_COUNT = 7
 # k_patch_compare, the launches of last_compare / compare_at (one, two when normalising), never part of a search either
 KERNEL_NAMES = ["pyr_down", "top_warp", "top_ncc", "top_nms", "cand_init", "roi_tables", "roi_warp", "roi_corr",
                 "roi_eval", "roi_small", "cand_step", "top_map", "bitwise_not", "patch_warp", "patch_compare"]
+# KERNEL_NAMES holds the kernels of searches, patches and comparisons, and keeps its 15 entries (tests/test_gpu_compare.py
+# pins the count).  The learn entries' kernel has its profiling index past them: tmpl_prep = k_tmpl_prep, the one launch of
+# learn_device / learn_at / learn_hit over all template levels, never part of a search.  PROFILE_NAMES names every
+# FPM_K_* index.
+LEARN_KERNEL_NAME = "tmpl_prep"
+PROFILE_NAMES = KERNEL_NAMES + [LEARN_KERNEL_NAME]
 # fpm_set_patch_form
 PATCH_FORM_TILED, PATCH_FORM_WARP = 0, 1
 # fpm_last_compare / fpm_compare_at flags
@@ -45,7 +51,7 @@ KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_wa
                   "roi_warp": ["k_roi_warp3", "k_roi_warp"], "roi_corr": ["k_roi_corr"], "roi_eval": ["k_roi_eval"],
                   "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"],
                   "bitwise_not": ["k_bitwise_not"], "patch_warp": ["k_patch_warp"],
-                  "patch_compare": ["k_patch_compare"]}
+                  "patch_compare": ["k_patch_compare"], "tmpl_prep": ["k_tmpl_prep"]}
 
 
 class Params(C.Structure):
@@ -171,6 +177,12 @@ SIGNATURES = {
                                  C.c_size_t, C.c_size_t]),
     "fpm_compare_derive": (C.c_int, [C.c_int64] * 6 + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                        C.POINTER(C.c_double), _U8P]),
+    "fpm_learn_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, C.c_int32, _P]),
+    "fpm_learn_at": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_float, C.c_float, C.c_double]),
+    "fpm_learn_hit": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_int32]),
+    "fpm_learn_derive": (C.c_int, [C.c_int64] * 3 + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)]),
+    "fpm_template_operands": (C.c_int, [_P, C.POINTER(C.c_int8), C.POINTER(C.c_size_t), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_size_t)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -72,7 +72,9 @@ struct TmplLevel {
     size_t tsum_off;         // offset (elements) of the per-row sums in d_tsum
     double mean, norm, inv_area;
     bool equal1;
-    std::vector<uint8_t> px; // host copy (dense)
+    // host copy (dense).  After a device learn only the top level's is filled; fpm_template_level fetches the others
+    // on first use, behind its const context
+    mutable std::vector<uint8_t> px;
 };
 
 struct SrcLevel {
@@ -213,6 +215,10 @@ struct fpm_ctx {
     hipEvent_t tab_ev = nullptr, out_ev = nullptr;
     DevBuf d_cmpacc;          // the comparison's per-hit records (fpm_last_compare / fpm_compare_at) and their host copy
     PinBuf h_cmpacc;
+    // learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit): k_tmpl_prep's per-level sums, and their
+    // host copy followed by the pixels of the top level
+    DevBuf d_tacc;
+    PinBuf h_tacc;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -1841,6 +1847,28 @@ int check_patch_out(fpm_ctx* ctx, const void* out, const fpm_patch_rect& r, size
     return FPM_OK;
 }
 
+// The checks of pose i of a job list and its matrices: fwd (optional) the forward one, M the inverted one the samplers take.
+int patch_pose_matrix(fpm_ctx* ctx, const fpm_patch_rect& r, const PatchPose& p, int i, double* fwd, double M[6]) {
+    if (p.src < 0 || p.src >= ctx->S) { ctx->err = "pose " + std::to_string(i) + ": bad source index"; return FPM_E_INVALID_ARG; }
+    if (!std::isfinite(p.pose.x) || !std::isfinite(p.pose.y) || !std::isfinite(p.pose.angle)) {
+        ctx->err = "pose " + std::to_string(i) + ": not finite";
+        return FPM_E_INVALID_ARG;
+    }
+    patch_forward(ctx->sw, ctx->sh, p.pose, r.x, r.y, M);
+    if (fwd) std::copy(M, M + 6, fwd);
+    invert_affine(M);
+    // the samplers' coordinates are AB_BITS fixed point in 32 bits: the patch's corners bound every pixel's
+    for (int k = 0; k < 4; ++k) {
+        const double x = (k & 1) ? r.w - 1 : 0, y = (k & 2) ? r.h - 1 : 0;
+        const double sx = M[0] * x + M[1] * y + M[2], sy = M[3] * x + M[4] * y + M[5];
+        if (!(std::fabs(sx) < 1048576.0 && std::fabs(sy) < 1048576.0)) {
+            ctx->err = "pose " + std::to_string(i) + ": farther than 2^20 pixels from the source";
+            return FPM_E_INVALID_ARG;
+        }
+    }
+    return FPM_OK;
+}
+
 size_t patch_tab_bytes(int n) { return round_up(std::max(sizeof(PatchJob), sizeof(WarpJob)) * (size_t)n, (size_t)256); }
 
 // The job table of `poses` (PatchJob when tiled, else WarpJob), built in h_patchtab and sent to d_patchtab on the
@@ -1858,24 +1886,9 @@ int stage_patch_jobs(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pa
     const uint8_t* level0 = ctx->d_src.as<uint8_t>() + l0.off;
     for (int i = 0; i < n; ++i) {
         const PatchPose& p = poses[i];
-        if (p.src < 0 || p.src >= ctx->S) { ctx->err = "pose " + std::to_string(i) + ": bad source index"; return FPM_E_INVALID_ARG; }
-        if (!std::isfinite(p.pose.x) || !std::isfinite(p.pose.y) || !std::isfinite(p.pose.angle)) {
-            ctx->err = "pose " + std::to_string(i) + ": not finite";
-            return FPM_E_INVALID_ARG;
-        }
         double M[6];
-        patch_forward(ctx->sw, ctx->sh, p.pose, r.x, r.y, M);
-        if (matrices) std::copy(M, M + 6, matrices + 6 * (size_t)i);
-        invert_affine(M);
-        // the samplers' coordinates are AB_BITS fixed point in 32 bits: the patch's corners bound every pixel's
-        for (int k = 0; k < 4; ++k) {
-            const double x = (k & 1) ? r.w - 1 : 0, y = (k & 2) ? r.h - 1 : 0;
-            const double sx = M[0] * x + M[1] * y + M[2], sy = M[3] * x + M[4] * y + M[5];
-            if (!(std::fabs(sx) < 1048576.0 && std::fabs(sy) < 1048576.0)) {
-                ctx->err = "pose " + std::to_string(i) + ": farther than 2^20 pixels from the source";
-                return FPM_E_INVALID_ARG;
-            }
-        }
+        const int rc = patch_pose_matrix(ctx, r, p, i, matrices ? matrices + 6 * (size_t)i : nullptr, M);
+        if (rc != FPM_OK) return rc;
         const size_t off = (size_t)i * patch_stride;
         if (tiled) {
             PatchJob& j = ctx->h_patchtab.as<PatchJob>()[i];
@@ -2081,6 +2094,217 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     return FPM_OK;
 }
 
+// ---- learning on the device (fpm_learn_device, fpm_learn_at, fpm_learn_hit, fpm_learn_derive) ----
+constexpr int kLearnMaxSide = 65536;   // k_tmpl_prep keeps a row's sum of squares in 32 bits: 65025 * 65536 < 2^32
+
+// What fpm_learn derives per level, from the level's pixel count and exact sums: mean_stddev's expressions, then those
+// of fpm_learn's statistics block, in their order (the file is built with -ffp-contract=off), so the doubles are the
+// ones fpm_learn gives for the same pixels.  1 / ((double)h * w) there is 1 / (double)n here: the product is exact.
+void learn_derive(int64_t n, int64_t s, int64_t q, double* mean_out, double* norm_out, double* inv_area_out, bool* equal1) {
+    const double scale = 1. / (double)n;
+    const double m = (double)s * scale;
+    const double sdv = std::sqrt(std::max((double)q * scale - m * m, 0.));
+    const double inv_area = 1.0 / (double)n;
+    double norm = sdv * sdv;
+    *equal1 = norm < DBL_EPSILON;
+    norm = std::sqrt(norm);
+    norm /= std::sqrt(inv_area);
+    *mean_out = m; *norm_out = norm; *inv_area_out = inv_area;
+}
+
+// bytes of the i8 operand slab and entries of the row-sum array of a learned template (fpm_learn's o8 and os)
+void operand_sizes(const std::vector<TmplLevel>& lv, size_t* o8, size_t* os) {
+    const TmplLevel& t = lv.back();
+    *o8 = t.off8 + (size_t)t.p8 * round_up(t.h, kMmaRows) + 256;
+    *os = t.tsum_off + round_up(t.h, kMmaRows);
+}
+
+// size limits of a template learned on the device; nothing is touched
+int learn_size(fpm_ctx* ctx, int w, int h) {
+    if (w <= 0 || h <= 0) { ctx->err = "empty template"; return FPM_E_INVALID_ARG; }
+    const int L = top_layer(w, h, (int)std::sqrt((double)ctx->prm.min_reduce_area));
+    if (w > kLearnMaxSide || h > kLearnMaxSide || L + 1 > kTmplPrepMaxLevels) {
+        ctx->err = "template too large to learn on the device: sides up to 65536, at most 16 pyramid levels";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// A failed device learn leaves the context as after fpm_clear_pattern, not half-learned.
+int learn_fail(fpm_ctx* ctx, int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->learned = false;
+    ctx->staged = false;
+    ctx->src_valid = false;
+    ctx->tmpl.clear();
+    ctx->tmpl_gen++;
+    return rc;
+}
+
+// First half of a device learn: fpm_learn's layouts for a w x h template in lv, the buffers, and the slab cleared on
+// the context's stream (its padding stays 0, as after fpm_learn; level 0 is written next, by the caller).  The context
+// holds no template from here until learn_finish.
+int learn_begin(fpm_ctx* ctx, int w, int h, std::vector<TmplLevel>& lv) {
+    ctx->learned = false;
+    ctx->tmpl.clear();
+    ctx->tmpl_gen++;
+    const int L = top_layer(w, h, (int)std::sqrt((double)ctx->prm.min_reduce_area));
+    lv.assign(L + 1, {});
+    size_t off = 0, o8 = 0, os = 0;
+    int lw = w, lh = h;
+    for (int l = 0; l <= L; ++l) {
+        lv[l].w = lw; lv[l].h = lh;
+        lv[l].pitch = round_up(lw + 4, 64);
+        lv[l].off = off;
+        off += round_up((size_t)lv[l].pitch * (lh + 1), (size_t)256);
+        lv[l].p8 = 64 * ((lw + 63) / 64);
+        lv[l].off8 = o8;
+        o8 += (size_t)lv[l].p8 * round_up(lh, kMmaRows);
+        lv[l].tsum_off = os;
+        os += round_up(lh, kMmaRows);
+        lw = (lw + 1) / 2;
+        lh = (lh + 1) / 2;
+    }
+    o8 += 256;   // slack: k_roi_corr prefetches up to 2 64-byte blocks past a row's last
+    if (off > UINT32_MAX || o8 > UINT32_MAX) { ctx->err = "template too large to learn on the device"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(ctx->d_tmpl.ensure(off));
+    HIP_TRY(ctx->d_tmpl8.ensure(o8));
+    HIP_TRY(ctx->d_tsum.ensure(os * sizeof(int32_t)));
+    HIP_TRY(ctx->d_tacc.ensure(2 * sizeof(uint64_t) * kTmplPrepMaxLevels));
+    HIP_TRY(ctx->h_tacc.ensure(2 * sizeof(uint64_t) * kTmplPrepMaxLevels + (size_t)lv[L].w * lv[L].h));
+    HIP_TRY(hipMemsetAsync(ctx->d_tmpl.p, 0, off, ctx->stream));
+    return FPM_OK;
+}
+
+// Second half, level 0 of the slab holding the pixels (written on the context's stream): the pyramid, k_tmpl_prep, the
+// sums and the top level to pinned memory, one synchronisation, the statistics on the host.  The staged sources
+// survive when the slab's layout still fits the new template (same top layer, sizes still allowed): a search, a patch
+// or a comparison then needs no restaging; otherwise they are invalidated as fpm_learn invalidates them.
+int learn_finish(fpm_ctx* ctx, std::vector<TmplLevel>& lv) {
+    const int L = (int)lv.size() - 1;
+    uint8_t* base = ctx->d_tmpl.as<uint8_t>();
+    for (int l = 1; l <= L; ++l)   // cv::buildPyramid (:55) on the device
+        launch_pyr_down(base + lv[l - 1].off, lv[l - 1].w, lv[l - 1].h, lv[l - 1].pitch, 0, base + lv[l].off, lv[l].w,
+                        lv[l].h, lv[l].pitch, 0, 1, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    constexpr size_t kAccBytes = 2 * sizeof(uint64_t) * kTmplPrepMaxLevels;
+    HIP_TRY(hipMemsetAsync(ctx->d_tacc.p, 0, kAccBytes, ctx->stream));
+    TmplPrepArgs a{};
+    a.tmpl = base;
+    a.tmpl8 = ctx->d_tmpl8.as<int8_t>();
+    a.tsum = ctx->d_tsum.as<int32_t>();
+    a.acc = ctx->d_tacc.as<uint64_t>();
+    a.nlv = L + 1;
+    int64_t bytes = 0;   // template pixels read + operand bytes and row sums written
+    for (int l = 0; l <= L; ++l) {
+        TmplPrepLevel& v = a.lv[l];
+        const int rows = round_up(lv[l].h, kMmaRows);
+        v.off = (uint32_t)lv[l].off; v.off8 = (uint32_t)lv[l].off8; v.tsum_off = (uint32_t)lv[l].tsum_off;
+        v.w = lv[l].w; v.h = lv[l].h; v.pitch = lv[l].pitch; v.p8 = lv[l].p8;
+        v.chunk0 = a.nchunks;
+        a.nchunks += rows / kMmaRows;
+        bytes += (int64_t)lv[l].w * lv[l].h + (int64_t)lv[l].p8 * rows + (int64_t)sizeof(int32_t) * rows;
+    }
+    a.slack_off = (uint32_t)(lv[L].off8 + (size_t)lv[L].p8 * round_up(lv[L].h, kMmaRows));
+    {
+        ProfScope ps(ctx, FPM_K_LEARN, bytes + 256);
+        if (!launch_tmpl_prep(a, ctx->stream)) { ctx->err = "template slab layout: rows not 16-byte aligned"; return FPM_E_INTERNAL; }
+    }
+    HIP_TRY(hipGetLastError());
+    const TmplLevel& top = lv[L];
+    HIP_TRY(hipMemcpyAsync(ctx->h_tacc.p, ctx->d_tacc.p, kAccBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(ctx->h_tacc.as<uint8_t>(kAccBytes), top.w, base + top.off, top.pitch, top.w, top.h,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const uint64_t* acc = ctx->h_tacc.as<uint64_t>();
+    for (int l = 0; l <= L; ++l)
+        learn_derive((int64_t)lv[l].w * lv[l].h, (int64_t)acc[2 * l], (int64_t)acc[2 * l + 1], &lv[l].mean, &lv[l].norm,
+                     &lv[l].inv_area, &lv[l].equal1);
+    // the top level's pixels: plan_top_mma builds its B fragments from them; the others come on demand (fpm_template_level)
+    lv[L].px.assign(ctx->h_tacc.as<uint8_t>(kAccBytes), ctx->h_tacc.as<uint8_t>(kAccBytes) + (size_t)top.w * top.h);
+    ctx->border = lv[0].mean < 128 ? 255 : 0;   // :58-59
+    ctx->tmpl = std::move(lv);
+    ctx->learned = true;
+    ctx->tmpl_gen++;
+    ctx->searched = false;   // the last search's poses belong to the template before
+    const std::string err = ctx->err;
+    const bool keep = ctx->src_valid && ctx->S > 0 && ctx->src_L == L && check_sizes(ctx, ctx->sw, ctx->sh) == FPM_OK;
+    ctx->err = err;
+    if (!keep) {
+        ctx->staged = false;
+        ctx->src_valid = false;   // the slab's layout follows the template's pyramid depth
+    }
+    return FPM_OK;
+}
+
+// fpm_learn_device after its checks: the image staged into level 0 by k_stage_gray, ordered after the producer's stream
+int learn_from_image(fpm_ctx* ctx, const void* d_image, int w, int h, size_t stride, size_t plane_stride, int format,
+                     hipStream_t producer) {
+    std::vector<TmplLevel> lv;
+    int rc = learn_begin(ctx, w, h, lv);
+    if (rc != FPM_OK) return rc;
+    if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctx->in_ev, producer));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->in_ev, 0));
+    HIP_TRY(ctx->h_imgtab.ensure(sizeof(void*)));
+    HIP_TRY(ctx->d_imgtab.ensure(sizeof(void*)));
+    ctx->h_imgtab.as<const void*>()[0] = d_image;
+    HIP_TRY(hipMemcpyAsync(ctx->d_imgtab.p, ctx->h_imgtab.p, sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    const bool aligned = (stride & 15) == 0 && (!fmt_planar(format) || (plane_stride & 15) == 0) &&
+                         ((uintptr_t)d_image & 15) == 0;
+    // the slab's level offsets are multiples of 256 and its pitches of 64: the launcher's alignment rule holds.  The
+    // template is learned as given: no inversion, whatever fpm_params.bitwise_not says
+    const TmplLevel& l0 = lv[0];
+    if (!launch_stage_gray(ctx->d_imgtab.as<const uint8_t*>(), 1, w, h, stride, plane_stride, format, aligned,
+                           ctx->d_tmpl.as<uint8_t>() + l0.off, l0.pitch, round_up((size_t)l0.pitch * (h + 1), (size_t)256),
+                           false, ctx->stream)) {
+        ctx->err = "template slab layout: level-0 rows not 16-byte aligned";
+        return FPM_E_INTERNAL;
+    }
+    HIP_TRY(hipGetLastError());
+    return learn_finish(ctx, lv);
+}
+
+// fpm_learn_at / fpm_learn_hit after their checks: the patch of `pose` sampled straight into level 0 (the patch
+// entries' job table and launch, with the template slab as the output)
+int learn_from_pose(fpm_ctx* ctx, const fpm_patch_rect& r, const PatchPose& pose) {
+    std::vector<TmplLevel> lv;
+    int rc = learn_begin(ctx, r.w, r.h, lv);
+    if (rc != FPM_OK) return rc;
+    const TmplLevel& l0 = lv[0];
+    rc = enqueue_patches(ctx, r, std::vector<PatchPose>(1, pose), ctx->d_tmpl.as<uint8_t>() + l0.off, (size_t)l0.pitch,
+                         (size_t)l0.pitch * r.h, nullptr);
+    if (rc != FPM_OK) return rc;
+    return learn_finish(ctx, lv);
+}
+
+// state, rectangle and pose checks shared by fpm_learn_at and fpm_learn_hit; nothing is touched before they pass
+int learn_pose_entry(fpm_ctx* ctx, const fpm_patch_rect* rect, bool need_search, int source, int index, const RawPose* given) {
+    int rc = patch_state(ctx, need_search);
+    fpm_patch_rect r;
+    if (rc == FPM_OK) rc = patch_rect(ctx, rect, &r);
+    if (rc == FPM_OK) rc = learn_size(ctx, r.w, r.h);
+    if (rc != FPM_OK) return rc;
+    if (source < 0 || source >= ctx->S) { ctx->err = "bad source index"; return FPM_E_INVALID_ARG; }
+    PatchPose pose{source, {}};
+    if (given) {
+        pose.pose = *given;
+    } else {
+        if (source >= (int)ctx->poses.size() || index < 0 || index >= (int)ctx->poses[source].size()) {
+            ctx->err = "bad result index";
+            return FPM_E_INVALID_ARG;
+        }
+        pose.pose = ctx->poses[source][index];
+    }
+    double M[6];
+    rc = patch_pose_matrix(ctx, r, pose, 0, nullptr, M);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = learn_from_pose(ctx, r, pose);
+    return rc == FPM_OK ? rc : learn_fail(ctx, rc);
+}
+
 }  // namespace
 
 // =========================================================================================================
@@ -2144,6 +2368,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     if (ctx->in_ev) (void)hipEventDestroy(ctx->in_ev);
     ctx->d_patchtab.release(); ctx->h_patchtab.release(); ctx->d_patch.release();
     ctx->d_cmpacc.release(); ctx->h_cmpacc.release();
+    ctx->d_tacc.release(); ctx->h_tacc.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -2564,6 +2789,61 @@ int fpm_compare_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_
     return compare_to_host(ctx, r, poses, threshold, flags, out, diff, row_stride, patch_stride);
 }
 
+// --- learning on the device -----------------------------------------------------------
+int fpm_learn_derive(int64_t n, int64_t sum, int64_t sum_sq, double* mean, double* norm, double* inv_area,
+                     int32_t* equal1) {
+    if (!mean || !norm || !inv_area || !equal1 || n < 1 || n > ((int64_t)1 << 32)) return FPM_E_INVALID_ARG;
+    if (sum < 0 || sum > 255 * n || sum_sq < 0 || sum_sq > 65025 * n) return FPM_E_INVALID_ARG;
+    if ((unsigned __int128)n * (unsigned __int128)sum_sq < (unsigned __int128)sum * (unsigned __int128)sum)
+        return FPM_E_INVALID_ARG;   // of no pixels (Cauchy-Schwarz)
+    bool eq = false;
+    learn_derive(n, sum, sum_sq, mean, norm, inv_area, &eq);
+    *equal1 = eq ? 1 : 0;
+    return FPM_OK;
+}
+
+// learnPattern (TemplateMatcher.cpp:45-95) on an image already in device memory
+int fpm_learn_device(fpm_ctx* ctx, const void* d_image, int32_t w, int32_t h, size_t stride, size_t plane_stride,
+                     int32_t format, void* producer_stream) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!d_image) { ctx->err = "empty template"; return FPM_E_INVALID_ARG; }
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    int rc = check_image_desc(ctx, 1, w, h, stride, plane_stride, format);
+    if (rc == FPM_OK) rc = learn_size(ctx, w, h);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = check_device_images(ctx, &d_image, 1, image_extent(w, h, stride, plane_stride, format), "template");
+    if (rc != FPM_OK) return rc;
+    rc = learn_from_image(ctx, d_image, w, h, stride, plane_stride, format, (hipStream_t)producer_stream);
+    return rc == FPM_OK ? rc : learn_fail(ctx, rc);
+}
+
+int fpm_learn_at(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, float lt_x, float lt_y, double angle) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    const RawPose pose{lt_x, lt_y, angle};
+    return learn_pose_entry(ctx, rect, false, source, 0, &pose);
+}
+
+int fpm_learn_hit(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t index) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    return learn_pose_entry(ctx, rect, true, source, index, nullptr);
+}
+
+int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count) {
+    if (!ctx || !t8_bytes || !tsum_count) return FPM_E_INVALID_ARG;
+    if (!ctx->learned) return FPM_E_NOT_LEARNED;
+    size_t o8 = 0, os = 0;
+    operand_sizes(ctx->tmpl, &o8, &os);
+    *t8_bytes = o8;
+    *tsum_count = os;
+    if (!t8 && !tsum) return FPM_OK;
+    // both arrays were complete when the learn returned; a search in flight only reads them
+    if (hipSetDevice(ctx->device) != hipSuccess) return FPM_E_DEVICE;
+    if (t8 && hipMemcpy(t8, ctx->d_tmpl8.p, o8, hipMemcpyDeviceToHost) != hipSuccess) return FPM_E_DEVICE;
+    if (tsum && hipMemcpy(tsum, ctx->d_tsum.p, os * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return FPM_E_DEVICE;
+    return FPM_OK;
+}
+
 // --- angle sharding of one search ---------------------------------------------------------
 int fpm_set_angle_shard(fpm_ctx* ctx, int32_t shard, int32_t shards) {
     if (!ctx) return FPM_E_INVALID_ARG;
@@ -2664,6 +2944,14 @@ int fpm_template_level(const fpm_ctx* ctx, int32_t level, int32_t* w, int32_t* h
     if (level < 0 || level >= (int)ctx->tmpl.size()) return FPM_E_INVALID_ARG;
     const TmplLevel& t = ctx->tmpl[level];
     *w = t.w; *h = t.h; *mean = t.mean; *norm = t.norm; *inv_area = t.inv_area; *result_equal1 = t.equal1 ? 1 : 0;
+    if (pixels && t.px.empty()) {
+        // a level of a device-learned template, fetched on first use (the slab was complete when the learn returned)
+        std::vector<uint8_t> px((size_t)t.w * t.h);
+        if (hipSetDevice(ctx->device) != hipSuccess ||
+            hipMemcpy2D(px.data(), t.w, ctx->d_tmpl.as<uint8_t>() + t.off, t.pitch, t.w, t.h, hipMemcpyDeviceToHost) != hipSuccess)
+            return FPM_E_DEVICE;
+        t.px = std::move(px);
+    }
     if (pixels)
         for (int y = 0; y < t.h; ++y) std::memcpy(pixels + (size_t)y * stride, t.px.data() + (size_t)y * t.w, (size_t)t.w);
     return FPM_OK;

@@ -254,6 +254,28 @@ struct CompareArgs {
 enum { kCompareRaw, kCompareSums, kCompareDevLut };
 // k_patch_compare, k_patch_warp's grid.  Returns false, launching nothing, for a grid past 2^31 - 1 or an unknown form.
 bool launch_patch_compare(CompareArgs c, int form, hipStream_t st);
+// ---- learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit): what learnPattern
+// derives from a template pyramid that already lies in the template slab, in one launch over all its levels.
+constexpr int kTmplPrepMaxLevels = 16;   // a 2^26-pixel template at min_reduce_area 1 has 13 levels above level 0
+struct TmplPrepLevel {
+    uint32_t off, off8;      // byte offsets of the level in the template slab and in the i8 operand slab
+    uint32_t tsum_off;       // element offset of its row sums
+    int32_t w, h;
+    int32_t pitch, p8;       // row pitches: the slab's (round_up(w + 4, 64)) and the operand's (64 * ceil(w / 64) <= pitch)
+    int32_t chunk0;          // the level's first workgroup; it has round_up(h, kMmaRows) / kMmaRows of them
+};
+struct TmplPrepArgs {
+    const uint8_t* tmpl;     // the template slab
+    int8_t* tmpl8;           // i8 operand slab: T ^ 0x80 at x < w, y < h, 0 in every other byte of [0, o8)
+    int32_t* tsum;           // per-row sums of T, 0 for the rows h .. round_up(h, kMmaRows) - 1
+    uint64_t* acc;           // [nlv][2] exact sum of T and of T^2 per level (integer atomics), zeroed before the launch
+    uint32_t slack_off;      // the 256 bytes behind the last level (k_roi_corr's prefetch), zeroed by workgroup 0
+    int32_t nlv, nchunks;
+    TmplPrepLevel lv[kTmplPrepMaxLevels];
+};
+// k_tmpl_prep: one workgroup per (level, kMmaRows-row chunk).  Returns false, launching nothing, for a level table the
+// kernel's 16-byte accesses do not fit (offsets and pitches are multiples of 16 in the engine's layouts, p8 <= pitch).
+bool launch_tmpl_prep(const TmplPrepArgs& a, hipStream_t st);
 void launch_ncc_map(const NccJob* jobs, int njobs, int max_out, int tmpl_bytes, hipStream_t st);
 bool ncc_tile_fits(int tw, int th);   // LDS-tiled variant applies (templates up to 128 x 64)
 void launch_ncc_tile(const NccJob* jobs, int njobs, int max_ow, int max_oh, int tw, int th, hipStream_t st);

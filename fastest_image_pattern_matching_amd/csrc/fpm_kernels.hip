@@ -3,6 +3,7 @@
 //   K1  k_pyr_down_s  cv::pyrDown, one level per launch    (TemplateMatcher.cpp:55, :124)
 //       k_pyr_down2   two levels per launch (small inputs)
 //       k_stage_gray  device-memory sources (gray / BGR / RGB(A) / planar) -> level 0, imread's gray conversion
+//       k_tmpl_prep   learnPattern's statistics, row sums and i8 operand of a template pyramid in device memory (:58-91)
 //   K2  k_warp        cv::warpAffine INTER_LINEAR          (TemplateMatcher.cpp:175, :1089)
 //   K3+K4 k_ncc_map   matchTemplate(TM_CCORR) + CCOEFF_Denominator   (:177 -> :514, :523, :527-598)
 //   K5  k_nms         minMaxLoc + getNextMaxLoc / s_BlockMax (:179-210, :1196-1221, DataStructures.h:118-246)
@@ -2915,6 +2916,93 @@ bool launch_patch_warp(PatchArgs a, hipStream_t st) {
     const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
     if (grid > INT_MAX) return false;
     hipLaunchKernelGGL(k_patch_warp, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return true;
+}
+
+// ============================================================================================== template prep
+// What learnPattern derives from the template pyramid (fpm_learn's host block), for a pyramid that lies in the template
+// slab: the i8 MFMA operand T ^ 0x80, the per-row sums of T and the exact sum of T and of T^2 per level, one launch over
+// all levels (fpm_learn_device / fpm_learn_at / fpm_learn_hit).
+// One workgroup per (level, kMmaRows-row chunk), found in the by-value level table; wave v takes rows v, v + 4, v + 8 and
+// v + 12 of the chunk, one lane per 16 bytes of an operand row and turn.  A 16-byte load of the slab row (it stays inside
+// the row: p8 <= pitch), the bytes at x >= w masked off here -- the slab's padding is never relied on and never becomes
+// 0x80 --, v_dot4_u32_u8 against 0x01010101 and against the value itself, one 16-byte store.  Operand rows h ..
+// round_up(h, kMmaRows) - 1 and the bytes w .. p8 - 1 of every row are written as 0, so with the slack behind the last
+// level (workgroup 0) every byte of the operand slab is defined by the launch.  Per row a DPP wave sum (the row's sum of
+// squares fits in u32: 65025 * 65536 < 2^32), per workgroup one pair of 64-bit integer atomics: no result depends on order.
+__device__ __forceinline__ uint32_t tmpl_prep_mask(int n) {   // the low min(max(n, 0), 4) bytes
+    return n >= 4 ? 0xffffffffu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
+}
+
+__global__ __launch_bounds__(256) void k_tmpl_prep(const TmplPrepArgs a) {
+    __shared__ unsigned long long part[4][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    if (b == 0 && tid < 64) ((uint32_t*)(a.tmpl8 + a.slack_off))[tid] = 0u;
+    int l = 0;
+    for (int k = 1; k < a.nlv; ++k)
+        if (b >= a.lv[k].chunk0) l = k;
+    const TmplPrepLevel& L = a.lv[l];
+    const int w = L.w, h = L.h, p8 = L.p8;
+    const int y0 = (b - L.chunk0) * kMmaRows + wave;
+    unsigned long long t1 = 0, t2 = 0;
+#pragma unroll 1
+    for (int i = 0; i < kMmaRows / 4; ++i) {
+        const int y = y0 + 4 * i;            // < round_up(h, kMmaRows)
+        const bool in = y < h;               // wave-uniform
+        const uint8_t* src = a.tmpl + L.off + (size_t)y * L.pitch;
+        int8_t* dst = a.tmpl8 + L.off8 + (size_t)y * p8;
+        uint32_t s1 = 0, s2 = 0;
+        for (int x = lane << 4; x < p8; x += 64 << 4) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (in && x < w) {
+                v = *(const uint4*)(src + x);
+                const int n = w - x;         // >= 1 bytes of the template from x on
+                const uint32_t m0 = tmpl_prep_mask(n), m1 = tmpl_prep_mask(n - 4), m2 = tmpl_prep_mask(n - 8),
+                               m3 = tmpl_prep_mask(n - 12);
+                v.x &= m0; v.y &= m1; v.z &= m2; v.w &= m3;
+                s1 = __builtin_amdgcn_udot4(v.x, 0x01010101u, s1, false);
+                s1 = __builtin_amdgcn_udot4(v.y, 0x01010101u, s1, false);
+                s1 = __builtin_amdgcn_udot4(v.z, 0x01010101u, s1, false);
+                s1 = __builtin_amdgcn_udot4(v.w, 0x01010101u, s1, false);
+                s2 = __builtin_amdgcn_udot4(v.x, v.x, s2, false);
+                s2 = __builtin_amdgcn_udot4(v.y, v.y, s2, false);
+                s2 = __builtin_amdgcn_udot4(v.z, v.z, s2, false);
+                s2 = __builtin_amdgcn_udot4(v.w, v.w, s2, false);
+                v.x = (v.x ^ 0x80808080u) & m0; v.y = (v.y ^ 0x80808080u) & m1;
+                v.z = (v.z ^ 0x80808080u) & m2; v.w = (v.w ^ 0x80808080u) & m3;
+            }
+            *(uint4*)(dst + x) = v;
+        }
+        s1 = wave_fold<false>(s1);
+        s2 = wave_fold<false>(s2);
+        if (lane == 0) a.tsum[L.tsum_off + y] = (int32_t)s1;
+        t1 += s1;
+        t2 += s2;
+    }
+    if (lane == 0) { part[wave][0] = t1; part[wave][1] = t2; }
+    __syncthreads();
+    if (tid < 2) {
+        const unsigned long long s = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+        if (s) atomicAdd((unsigned long long*)&a.acc[2 * l + tid], s);
+    }
+}
+
+bool launch_tmpl_prep(const TmplPrepArgs& a, hipStream_t st) {
+    if (a.nlv < 1 || a.nlv > kTmplPrepMaxLevels || !a.tmpl || !a.tmpl8 || !a.tsum || !a.acc) return false;
+    if (((uintptr_t)a.tmpl & 15) || ((uintptr_t)a.tmpl8 & 15) || ((uintptr_t)a.tsum & 3) || ((uintptr_t)a.acc & 7) ||
+        (a.slack_off & 3))
+        return false;
+    int chunks = 0;
+    for (int l = 0; l < a.nlv; ++l) {
+        const TmplPrepLevel& v = a.lv[l];
+        if (v.w < 1 || v.w > 65536 || v.h < 1 || v.p8 < v.w || v.p8 > v.pitch || (v.p8 & 15) || (v.pitch & 15) ||
+            (v.off & 15) || (v.off8 & 15) || v.chunk0 != chunks)
+            return false;
+        chunks += (v.h + kMmaRows - 1) / kMmaRows;
+    }
+    if (chunks != a.nchunks) return false;
+    hipLaunchKernelGGL(k_tmpl_prep, dim3((unsigned)chunks), dim3(256), 0, st, a);
     return true;
 }
 

@@ -304,6 +304,27 @@ def compare_derive(n: int, sum_i: int, sum_ii: int, sum_t: int, sum_tt: int, sum
     return z.value, g.value, o.value, lut
 
 
+class LearnError(ValueError):
+    """A device learn (learn_device / learn_at / learn_hit) the library rejected; ``code`` is its FPM_E_* status."""
+
+    def __init__(self, code: int, message: str):
+        super().__init__(message)
+        self.code = int(code)
+
+
+def learn_derive(n: int, total: int, total_sq: int):
+    """fpm_learn_derive: ``(mean, norm, inv_area, equal1)`` of a template level from its pixel count and the exact sums of
+    its pixels and of their squares, by the engine's own code (fpm_learn's f64 expressions in their order).  Host only
+    (no device).  Raises ValueError for sums that are those of no ``n`` bytes."""
+    mean, norm, inv = C.c_double(), C.c_double(), C.c_double()
+    eq = C.c_int32()
+    rc = L.load().fpm_learn_derive(int(n), int(total), int(total_sq), C.byref(mean), C.byref(norm), C.byref(inv),
+                                   C.byref(eq))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_learn_derive failed with {rc}")
+    return mean.value, norm.value, inv.value, bool(eq.value)
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -362,6 +383,63 @@ class TemplateMatcher:
 
     def clearPattern(self):
         self._lib.fpm_clear_pattern(self._ctx)
+
+    # -- learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit) -------------------------------------
+    def _learn_done(self, rc, what):
+        self._check(rc, what)
+        if rc != L.FPM_OK:
+            raise LearnError(rc, f"{what} failed with {rc}: {self.last_error()}")
+
+    def learn_device(self, img, channel_order: str = "bgr", layout=None, stream=None):
+        """learnPattern on an image already in device memory (fpm_learn_device): a uint8 torch tensor as match_device
+        takes it (gray, interleaved or planar, contiguous or a view), converted as match_device converts a frame.  Nothing
+        crosses the host but the level statistics' sums and the top level's pixels; the learned template equals
+        learnPattern's for the same gray pixels in every byte and every double.  setBitwiseNot is not looked at.  Staged
+        sources survive when the new template has the top layer they were staged for (see learn_at).  Raises LearnError
+        (a ValueError with the status in ``code``) when the call is rejected."""
+        ptr, h, w, row, plane, fmt = self._device_image(img, channel_order, layout)
+        prod = self._producer_stream(stream)
+        self._push()
+        rc = self._lib.fpm_learn_device(self._ctx, ptr, w, h, row, plane, fmt, prod)
+        self._learn_done(rc, "learn_device")
+
+    def learn_at(self, source: int, lt, angle: float, rect=None):
+        """learnPattern on the patch patches_at gives for (``source``, ``lt``, ``angle``, ``rect``), sampled on the device
+        straight into the template (fpm_learn_at): teach from a region of a staged frame.  ``rect`` None = the
+        user-defined rectangle when one is set, else the frame of the template learned now.  Needs staged sources (stage
+        / stage_device, or the source of the last match).  They stay staged when the new template's top layer equals the
+        one they were staged for: match_staged, patches_at and compare_at then work without restaging; otherwise stage
+        again, as after learnPattern.  The poses of the last search are dropped either way."""
+        r = self._patch_rect(rect)
+        self._push()
+        rc = self._lib.fpm_learn_at(self._ctx, C.byref(r) if r is not None else None, int(source),
+                                    float(np.float32(lt[0])), float(np.float32(lt[1])), float(angle))
+        self._learn_done(rc, "learn_at")
+
+    def learn_hit(self, index: int, source: int = 0, rect=None):
+        """learn_at at the raw pose of result ``index`` of ``source`` of the last search, the pose last_patches uses
+        (fpm_learn_hit): re-teach on what the matcher just found.  Needs a finished search on the staged sources."""
+        r = self._patch_rect(rect)
+        self._push()
+        rc = self._lib.fpm_learn_hit(self._ctx, C.byref(r) if r is not None else None, int(source), int(index))
+        self._learn_done(rc, "learn_hit")
+
+    def template_operands(self):
+        """(t8 int8 [bytes], tsum int32 [rows]): the matrix-core operand slab (T ^ 0x80 per level, zero padded, slack
+        included) and the per-row sums as they lie in device memory (fpm_template_operands); for parity tests."""
+        nb, ns = C.c_size_t(), C.c_size_t()
+        rc = self._check(self._lib.fpm_template_operands(self._ctx, None, C.byref(nb), None, C.byref(ns)),
+                         "template_operands")
+        if rc != L.FPM_OK:
+            raise ValueError("template not learned")
+        t8 = np.zeros(nb.value, np.int8)
+        ts = np.zeros(ns.value, np.int32)
+        rc = self._check(self._lib.fpm_template_operands(self._ctx, t8.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(nb),
+                                                         ts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ns)),
+                         "template_operands")
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_template_operands failed with {rc}")
+        return t8, ts
 
     # -- search ---------------------------------------------------------------------------------------------
     def match(self, sourceImage) -> List[SingleTargetMatch]:

@@ -295,6 +295,49 @@ int fpm_compare_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_
 int fpm_compare_derive(int64_t n, int64_t sum_i, int64_t sum_ii, int64_t sum_t, int64_t sum_tt, int64_t sum_it,
                        int32_t normalize, double* zncc, double* gain, double* offset, uint8_t lut[256]);
 
+/* --- learning on the device: the template from a device image, a pose or a hit (no reference equivalent: learnPattern
+ * takes a host cv::Mat, TemplateMatcher.cpp:45) ---------------------------------------------------------------------
+ * fpm_learn uploads the image, builds the pyramid on the device, copies every level back and walks it on the host.
+ * These entries learn where the pixels are: level 0 of the template slab is written by a kernel (k_stage_gray for an
+ * image, k_patch_warp for a pose), the pyramid kernels build the levels, one launch of k_tmpl_prep makes what the
+ * search needs of them (the i8 operand, the per-row sums, the exact sum of T and of T^2 per level), and the host derives
+ * the level statistics from those sums after one stream synchronisation.  The learned template equals what fpm_learn
+ * learns from the same pixels in every byte and every double (fpm_template_info, fpm_template_level,
+ * fpm_template_operands).
+ * State after a successful call: the template is learned, and the poses of the last search are dropped
+ * (fpm_last_patches*, fpm_last_compare and fpm_learn_hit return FPM_E_INVALID_ARG until the next search).  Unlike
+ * fpm_learn the entries KEEP the staged sources when the source slab's layout still fits the new template -- its top
+ * layer (getTopLayer at the current min_reduce_area) equals the one the sources were staged for and the size rules of
+ * fpm_match still hold -- so fpm_match_staged*, fpm_patches_at and fpm_compare_at work without restaging: teach from
+ * frame 0 of a batch, search the batch, one upload.  Otherwise the sources are invalidated as fpm_learn invalidates
+ * them.
+ * Errors.  FPM_E_INVALID_ARG while a search is in flight and for what the argument and state rules reject (sides above
+ * 65536 and pyramids of more than 16 levels included); such a call leaves the context untouched.  A failure once the
+ * template slab has been touched (a device error) leaves the context as after fpm_clear_pattern, not half-learned.
+ * Additive entries: FPM_ABI_VERSION is unchanged, as for the device-memory entries above. */
+/* learnPattern on an image in device memory; arguments as fpm_match_device's image.  fpm_params.bitwise_not is not looked
+ * at: the template is learned as given */
+int fpm_learn_device(fpm_ctx* ctx, const void* d_image, int32_t width, int32_t height, size_t stride,
+                     size_t plane_stride, int32_t format, void* producer_stream);
+/* learnPattern on the patch fpm_patches_at gives for (rect, source, lt, angle): sampled by k_patch_warp (k_warp under
+ * FPM_PATCH_FORM_WARP) straight into level 0 of the template slab.  rect NULL = the frame of the template learned now
+ * (FPM_E_NOT_LEARNED without one).  Rectangle, pose and state rules as fpm_patches_at: staged sources are needed, and
+ * with fpm_params.bitwise_not in force for them the plane sampled is 255 - source, the plane the search correlates with */
+int fpm_learn_at(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, float lt_x, float lt_y, double angle);
+/* the same at the raw pose of result `index` of `source` of the last search (the pose fpm_last_patches uses); state rules
+ * as fpm_last_patches, FPM_E_INVALID_ARG for an index outside the source's results */
+int fpm_learn_hit(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t index);
+/* host only, no context: what learning derives for a level from its pixel count and the exact sums of its pixels and of
+ * their squares -- cv::meanStdDev's mean, then norm, inv_area and vecResultEqual1 by TemplateMatcher.cpp:66-91, in
+ * fpm_learn's own f64 expressions and order.  FPM_E_INVALID_ARG for n outside 1 .. 2^32 and for sums that are those of
+ * no n bytes (negative, above 255 n or 65025 n, or n sum_sq < sum^2) */
+int fpm_learn_derive(int64_t n, int64_t sum, int64_t sum_sq, double* mean, double* norm, double* inv_area,
+                     int32_t* equal1);
+/* introspection for parity tests: the whole i8 operand slab (T ^ 0x80 per level, zero padded, the 256 bytes of slack
+ * behind the last level included) and the row-sum array as they lie in device memory.  *t8_bytes and *tsum_count always
+ * receive the sizes; t8 and tsum (each may be NULL) must hold that many bytes / entries */
+int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent
@@ -442,7 +485,9 @@ int fpm_search_bytes(const fpm_ctx* ctx, int64_t* b_pyr, int64_t* b_top, int64_t
 #define FPM_K_COMPARE 14    /* k_patch_compare: the launches of fpm_last_compare / fpm_compare_at (one, or two with
                                FPM_COMPARE_NORMALIZE); bytes = source pixels read + template pixels read + difference
                                pixels written */
-#define FPM_K_COUNT 15
+#define FPM_K_LEARN 15      /* k_tmpl_prep: the one launch of fpm_learn_device / fpm_learn_at / fpm_learn_hit over all levels;
+                               bytes = template pixels read + operand bytes (slack included) and row sums written */
+#define FPM_K_COUNT 16
 int fpm_profile_enable(fpm_ctx* ctx, int32_t enable);
 int fpm_profile_reset(fpm_ctx* ctx);
 int fpm_profile_get(const fpm_ctx* ctx, int32_t kernel, double* total_ms, int64_t* launches,

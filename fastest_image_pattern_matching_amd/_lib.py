@@ -52,6 +52,10 @@ KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_wa
                   "roi_small": ["k_roi_small"], "cand_step": ["k_cand_step"], "top_map": ["k_top_map"],
                   "bitwise_not": ["k_bitwise_not"], "patch_warp": ["k_patch_warp"],
                   "patch_compare": ["k_patch_compare"], "tmpl_prep": ["k_tmpl_prep"]}
+# fpm_model_profile's `which`: the variation model's kernels have no FPM_K_* index
+MODEL_TRAIN, MODEL_PREPARE, MODEL_INSPECT = 0, 1, 2
+MODEL_KERNEL_SYMBOLS = ["k_model_accum", "k_model_prepare", "k_model_inspect"]
+MODEL_MAX_SAMPLES = 65535
 
 
 class Params(C.Structure):
@@ -104,6 +108,15 @@ class CompareStats(C.Structure):
                 ("n_over", C.c_int32), ("max_abs", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
                 ("x1", C.c_int32), ("y1", C.c_int32),
                 ("zncc", C.c_double), ("gain", C.c_double), ("offset", C.c_double)]
+
+
+class InspectStats(C.Structure):
+    """fpm_inspect_stats — one hit against the variation model (fpm_last_inspect / fpm_inspect_at)."""
+
+    _fields_ = [("n", C.c_int64), ("sum_excess", C.c_int64),
+                ("n_low", C.c_int32), ("n_high", C.c_int32), ("max_excess", C.c_int32), ("x0", C.c_int32),
+                ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("gain", C.c_double), ("offset", C.c_double)]
 
 
 class RoiRecord(C.Structure):
@@ -183,6 +196,23 @@ SIGNATURES = {
     "fpm_learn_derive": (C.c_int, [C.c_int64] * 3 + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)]),
     "fpm_template_operands": (C.c_int, [_P, C.POINTER(C.c_int8), C.POINTER(C.c_size_t), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t)]),
+    "fpm_model_clear": (C.c_int, [_P]),
+    "fpm_model_set_chunk": (C.c_int, [_P, C.c_int32]),
+    "fpm_model_train_last": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_model_train_at": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_double), C.c_int32, C.c_int32]),
+    "fpm_model_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(PatchRect)]),
+    "fpm_model_sums": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fpm_model_images": (C.c_int, [_P, C.c_int32, C.c_int32, _U8P, _U8P, _U8P, C.c_size_t]),
+    "fpm_last_inspect": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(InspectStats), C.c_int32,
+                                   C.POINTER(C.c_int32), _U8P, C.c_size_t, C.c_size_t]),
+    "fpm_inspect_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_int32, C.POINTER(InspectStats), _U8P, C.c_size_t,
+                                 C.c_size_t]),
+    "fpm_model_learn": (C.c_int, [_P]),
+    "fpm_model_derive": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3),
+    "fpm_model_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -26,6 +26,7 @@
 #include "../../include/fpm.h"
 #include "fpm_host.h"
 #include "fpm_kernels.h"
+#include "fpm_model.h"
 
 using namespace fpm;
 
@@ -148,6 +149,9 @@ struct KProf {
     double ms = 0;
     int64_t launches = 0, bytes = 0;
 };
+// Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile), which
+// have no FPM_K_* index: FPM_K_COUNT stays what it is.
+enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfSlots };
 
 }  // namespace
 
@@ -188,7 +192,7 @@ struct fpm_ctx {
     int64_t alg_bytes[3] = {0, 0, 0};   // SURVEY.md §8(d) algorithmic bytes of the last search: B_pyr, B_top, B_ref
     // profiling
     bool prof = false;
-    KProf kp[FPM_K_COUNT];
+    KProf kp[kProfSlots];
     // the whole device-resident search captured once per (plan, source slab) and replayed as one hipGraph
     hipGraphExec_t graph = nullptr;
     uint64_t graph_plan = ~0ull;
@@ -219,6 +223,18 @@ struct fpm_ctx {
     // host copy followed by the pixels of the top level
     DevBuf d_tacc;
     PinBuf h_tacc;
+    // variation model (fpm_model_* / fpm_last_inspect / fpm_inspect_at): model_n samples over model_rect summed in
+    // d_model (two dense u32 planes, sum then sum of squares); model_n = 0: no model.  d_band = the u8 mean / lo / hi
+    // planes derived for (band_a, band_kq) from generation band_gen of the sums (prepared when the key changes).
+    int model_n = 0;
+    fpm_patch_rect model_rect{0, 0, 0, 0};
+    int model_chunk = 0;      // fpm_model_set_chunk: jobs per workgroup of k_model_accum, 0 = the engine's choice
+    uint64_t model_gen = 0;
+    DevBuf d_model, d_band;
+    int band_a = -1, band_kq = -1;
+    uint64_t band_gen = ~0ull;
+    DevBuf d_insacc;          // the inspection's per-hit records and their host copy
+    PinBuf h_insacc;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -261,7 +277,7 @@ struct ProfScope {
 
 void prof_collect(fpm_ctx* ctx) {
     if (!ctx->prof) return;
-    for (int k = 0; k < FPM_K_COUNT; ++k) {
+    for (int k = 0; k < kProfSlots; ++k) {
         KProf& p = ctx->kp[k];
         for (size_t i = 0; i < p.used; ++i) {
             float ms = 0;
@@ -2015,6 +2031,37 @@ void compare_derive(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt,
     }
 }
 
+// The first half of a normalised comparison (and of normalised training and inspection of the variation model): the
+// sums launch into c.acc = d_cmpacc (zero-filled by the caller), the sums to h_cmpacc, a table per hit from them, the
+// tables to the device beside the job table (stage_patch_jobs' `extra` bytes: 256 n), their address in *d_luts.
+// Synchronises the stream once, between the sums and the tables.
+int compare_norm_tables(fpm_ctx* ctx, CompareArgs c, const fpm_patch_rect& r, int n, const uint8_t** d_luts) {
+    const size_t accb = sizeof(CompareAcc) * (size_t)n, lut_off = patch_tab_bytes(n);
+    c.p.out = nullptr;
+    {
+        ProfScope ps(ctx, FPM_K_COMPARE, 2 * (int64_t)n * r.w * r.h);   // source pixels read + template pixels read
+        if (!launch_patch_compare(c, kCompareSums, ctx->stream)) {
+            ctx->err = "too many patch tiles for one launch";
+            return FPM_E_INVALID_ARG;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_cmpacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // also: the job table has left h_patchtab
+    const int64_t area = (int64_t)r.w * r.h;
+    uint8_t* luts = ctx->h_patchtab.as<uint8_t>(lut_off);
+    for (int i = 0; i < n; ++i) {
+        double z, g, o;
+        compare_derive(area, (int64_t)h[i].s[kCmpSumI], (int64_t)h[i].s[kCmpSumII], (int64_t)h[i].s[kCmpSumT],
+                       (int64_t)h[i].s[kCmpSumTT], (int64_t)h[i].s[kCmpSumIT], true, &z, &g, &o, luts + (size_t)256 * i);
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.as<uint8_t>(lut_off), luts, (size_t)256 * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    *d_luts = ctx->d_patchtab.as<uint8_t>(lut_off);
+    return FPM_OK;
+}
+
 // The comparison of `poses` (n >= 1): one launch, or with FPM_COMPARE_NORMALIZE the sums, the tables built here from
 // them, and the deviations through the tables.  Returns when out (and diff) are filled.
 int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int threshold, int flags,
@@ -2027,7 +2074,7 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
         HIP_TRY(ctx->d_patch.ensure(pbytes * (size_t)n));
         d = ctx->d_patch.as<uint8_t>();
     }
-    const size_t accb = sizeof(CompareAcc) * (size_t)n, lut_off = patch_tab_bytes(n);
+    const size_t accb = sizeof(CompareAcc) * (size_t)n;
     int rc = stage_patch_jobs(ctx, r, poses, d, pitch, pbytes, nullptr, true, norm ? (size_t)256 * n : 0);
     if (rc != FPM_OK) return rc;
     HIP_TRY(ctx->d_cmpacc.ensure(accb));
@@ -2044,28 +2091,17 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     // bytes: source pixels read + template pixels read (+ difference pixels written), per launch
     const int64_t px = (int64_t)n * r.w * r.h;
     const char* too_many = "too many patch tiles for one launch";
-    {
+    CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
+    if (!norm) {
         ProfScope ps(ctx, FPM_K_COMPARE, (2 + (c.p.out ? 1 : 0)) * px);
-        if (!launch_patch_compare(c, norm ? kCompareSums : kCompareRaw, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
+        if (!launch_patch_compare(c, kCompareRaw, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
     }
     HIP_TRY(hipGetLastError());
-    CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
     if (norm) {
-        // the sums to the host, a table per hit from them, the tables to the device beside the job table, then the
-        // second launch, which samples the footprints again
-        HIP_TRY(hipMemcpyAsync(h, ctx->d_cmpacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));   // also: the job table has left h_patchtab
-        const int64_t area = (int64_t)r.w * r.h;
-        uint8_t* luts = ctx->h_patchtab.as<uint8_t>(lut_off);
-        for (int i = 0; i < n; ++i) {
-            double z, g, o;
-            compare_derive(area, (int64_t)h[i].s[kCmpSumI], (int64_t)h[i].s[kCmpSumII], (int64_t)h[i].s[kCmpSumT],
-                           (int64_t)h[i].s[kCmpSumTT], (int64_t)h[i].s[kCmpSumIT], true, &z, &g, &o, luts + (size_t)256 * i);
-        }
-        HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.as<uint8_t>(lut_off), luts, (size_t)256 * n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+        // the sums and the tables, then the second launch, which samples the footprints again
+        rc = compare_norm_tables(ctx, c, r, n, &c.luts);
+        if (rc != FPM_OK) return rc;
         c.p = patch_args(ctx, r, n, d, pitch, pbytes);
-        c.luts = ctx->d_patchtab.as<uint8_t>(lut_off);
         {
             ProfScope ps(ctx, FPM_K_COMPARE, (2 + (d ? 1 : 0)) * px);
             if (!launch_patch_compare(c, kCompareDevLut, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
@@ -2138,6 +2174,7 @@ int learn_fail(fpm_ctx* ctx, int rc) {
     ctx->src_valid = false;
     ctx->tmpl.clear();
     ctx->tmpl_gen++;
+    ctx->model_n = 0;
     return rc;
 }
 
@@ -2242,6 +2279,7 @@ int learn_finish(fpm_ctx* ctx, std::vector<TmplLevel>& lv) {
 int learn_from_image(fpm_ctx* ctx, const void* d_image, int w, int h, size_t stride, size_t plane_stride, int format,
                      hipStream_t producer) {
     std::vector<TmplLevel> lv;
+    ctx->model_n = 0;   // the variation model belongs to the template before
     int rc = learn_begin(ctx, w, h, lv);
     if (rc != FPM_OK) return rc;
     if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
@@ -2270,6 +2308,7 @@ int learn_from_image(fpm_ctx* ctx, const void* d_image, int w, int h, size_t str
 // entries' job table and launch, with the template slab as the output)
 int learn_from_pose(fpm_ctx* ctx, const fpm_patch_rect& r, const PatchPose& pose) {
     std::vector<TmplLevel> lv;
+    ctx->model_n = 0;   // the variation model belongs to the template before
     int rc = learn_begin(ctx, r.w, r.h, lv);
     if (rc != FPM_OK) return rc;
     const TmplLevel& l0 = lv[0];
@@ -2303,6 +2342,219 @@ int learn_pose_entry(fpm_ctx* ctx, const fpm_patch_rect* rect, bool need_search,
     HIP_TRY(hipSetDevice(ctx->device));
     rc = learn_from_pose(ctx, r, pose);
     return rc == FPM_OK ? rc : learn_fail(ctx, rc);
+}
+
+// ---- variation model (fpm_model_*, fpm_last_inspect, fpm_inspect_at) ----
+const char* kInFlight = "a search is in flight (fpm_match_staged_finish first)";
+
+bool same_rect(const fpm_patch_rect& a, const fpm_patch_rect& b) { return a.x == b.x && a.y == b.y && a.w == b.w && a.h == b.h; }
+
+int model_pitch(int w) { return round_up(w + 4, 64); }   // the template slab's rule: k_model_inspect reads dword pairs
+
+// Jobs per workgroup of k_model_accum for n jobs over `tiles` tiles.  With enough tiles to fill the device every tile
+// takes all its jobs (one owner per pixel: plain adds, no atomics); with fewer the jobs are cut into as many chunks as
+// bring the grid to kModelWgPerCu workgroups per compute unit, each chunk adding to the planes with atomics -- but no
+// chunk below kModelMinChunk jobs, where the atomics cost more than the idle compute units (DESIGN.md section 17 has
+// the sweep both constants come from).
+constexpr int kModelWgPerCu = 12;
+constexpr int kModelMinChunk = 4;
+int model_chunk_for(fpm_ctx* ctx, int n, int64_t tiles) {
+    if (ctx->model_chunk > 0) return std::min(ctx->model_chunk, n);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) cus = 256;
+    const int64_t want = (int64_t)kModelWgPerCu * cus;
+    const int64_t nchunks = std::min<int64_t>(n, std::max<int64_t>(1, (want + tiles - 1) / tiles));
+    return std::min(n, std::max((int)((n + nchunks - 1) / nchunks), kModelMinChunk));
+}
+
+// The arguments of the sums launch of a normalised call over the model's rectangle, with d_cmpacc sized and cleared.
+int model_norm_args(fpm_ctx* ctx, const fpm_patch_rect& r, int n, CompareArgs* c) {
+    const size_t accb = sizeof(CompareAcc) * (size_t)n;
+    HIP_TRY(ctx->d_cmpacc.ensure(accb));
+    HIP_TRY(ctx->h_cmpacc.ensure(accb));
+    HIP_TRY(hipMemsetAsync(ctx->d_cmpacc.p, 0, accb, ctx->stream));
+    const TmplLevel& t0 = ctx->tmpl[0];
+    *c = CompareArgs{};
+    c->p = patch_args(ctx, r, n, nullptr, 0, 0);
+    c->tmpl = ctx->d_tmpl.as<uint8_t>() + t0.off;
+    c->tp = t0.pitch;
+    c->rx = r.x; c->ry = r.y;
+    c->acc = ctx->d_cmpacc.as<CompareAcc>();
+    return FPM_OK;
+}
+
+// Adds `poses` (n >= 1) to the model.  Everything that can reject the call comes before the first launch, so a call
+// that fails adds nothing.
+int model_train(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int flags) {
+    const int n = (int)poses.size();
+    const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
+    if (ctx->model_n > 0 && !same_rect(r, ctx->model_rect)) {
+        ctx->err = "the variation model was trained on another rectangle (fpm_model_clear first)";
+        return FPM_E_INVALID_ARG;
+    }
+    if (n > kModelMaxSamples - ctx->model_n) { ctx->err = "the variation model holds at most 65535 samples"; return FPM_E_CAPACITY; }
+    int rc = stage_patch_jobs(ctx, r, poses, nullptr, 0, 0, nullptr, true, norm ? (size_t)256 * n : 0);
+    if (rc != FPM_OK) return rc;
+    const size_t px = (size_t)r.w * r.h, plane = px * sizeof(uint32_t);
+    HIP_TRY(ctx->d_model.ensure(2 * plane));
+    if (ctx->model_n == 0) HIP_TRY(hipMemsetAsync(ctx->d_model.p, 0, 2 * plane, ctx->stream));
+    ModelAccumArgs m{};
+    m.p = patch_args(ctx, r, n, nullptr, 0, 0);
+    m.sum = ctx->d_model.as<uint32_t>();
+    m.sum_sq = m.sum + px;
+    if (norm) {
+        CompareArgs c;
+        rc = model_norm_args(ctx, r, n, &c);
+        if (rc == FPM_OK) rc = compare_norm_tables(ctx, c, r, n, &m.luts);
+        if (rc != FPM_OK) return rc;
+    }
+    const int64_t tiles = (int64_t)((r.w + 63) / 64) * ((r.h + 15) / 16);
+    {
+        // bytes: source pixels read + plane bytes written
+        ProfScope ps(ctx, kProfModelTrain, (int64_t)n * r.w * r.h + 2 * (int64_t)plane);
+        if (!launch_model_accum(m, model_chunk_for(ctx, n, tiles), ctx->stream)) {
+            ctx->err = "too many patch tiles for one launch";
+            return FPM_E_INVALID_ARG;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    ctx->model_rect = r;
+    ctx->model_n += n;
+    ctx->model_gen++;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    return FPM_OK;
+}
+
+// the model's rectangle; FPM_E_INVALID_ARG without a model.  It lies inside the template: every entry that changes the
+// template drops the model, except fpm_model_learn, which makes the rectangle the new template's frame.
+int model_need(fpm_ctx* ctx, fpm_patch_rect* r) {
+    if (ctx->model_n <= 0) { ctx->err = "no variation model (fpm_model_train_last / fpm_model_train_at first)"; return FPM_E_INVALID_ARG; }
+    *r = ctx->model_rect;
+    return FPM_OK;
+}
+
+int model_args(fpm_ctx* ctx, int a, int kq) {
+    if (a < 0 || a > 255 || kq < 0 || kq > 255) {
+        ctx->err = "abs threshold must be 0 .. 255 and the sigma multiple 0 .. 255 sixteenths";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// mean / lo / hi for (a, kq) in d_band, prepared on the context's stream when the key changed (no wait)
+int model_band_ensure(fpm_ctx* ctx, int a, int kq) {
+    const fpm_patch_rect& r = ctx->model_rect;
+    const int pitch = model_pitch(r.w);
+    const size_t plane = (size_t)pitch * r.h;
+    if (ctx->band_a == a && ctx->band_kq == kq && ctx->band_gen == ctx->model_gen) return FPM_OK;
+    ctx->band_gen = ~0ull;
+    HIP_TRY(ctx->d_band.ensure(3 * plane));
+    HIP_TRY(hipMemsetAsync(ctx->d_band.p, 0, 3 * plane, ctx->stream));   // the padding of the rows is read (and masked off)
+    const size_t px = (size_t)r.w * r.h;
+    ModelPrepareArgs p{};
+    p.sum = ctx->d_model.as<uint32_t>();
+    p.sum_sq = p.sum + px;
+    p.w = r.w; p.h = r.h; p.n = ctx->model_n;
+    p.a = a; p.kq = kq;
+    p.mean = ctx->d_band.as<uint8_t>();
+    p.lo = p.mean + plane;
+    p.hi = p.lo + plane;
+    p.pitch = pitch;
+    {
+        ProfScope ps(ctx, kProfModelPrepare, (int64_t)px * (2 * (int64_t)sizeof(uint32_t) + 3));   // planes in and out
+        launch_model_prepare(p, ctx->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    ctx->band_a = a; ctx->band_kq = kq; ctx->band_gen = ctx->model_gen;
+    return FPM_OK;
+}
+
+// The inspection of `poses` (n >= 1) against the model: the planes for (a, kq), one launch of k_model_inspect (after
+// the sums launch and the tables with FPM_COMPARE_NORMALIZE).  Returns when out (and img) are filled.
+int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int a, int kq, int flags,
+                    fpm_inspect_stats* out, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    const int n = (int)poses.size();
+    const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
+    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
+    uint8_t* d = nullptr;   // the excess images: the context's pitched buffer, as for the host patches
+    if (img) {
+        HIP_TRY(ctx->d_patch.ensure(pbytes * (size_t)n));
+        d = ctx->d_patch.as<uint8_t>();
+    }
+    int rc = stage_patch_jobs(ctx, r, poses, d, pitch, pbytes, nullptr, true, norm ? (size_t)256 * n : 0);
+    if (rc == FPM_OK) rc = model_band_ensure(ctx, a, kq);
+    if (rc != FPM_OK) return rc;
+    const size_t accb = sizeof(InspectAcc) * (size_t)n;
+    HIP_TRY(ctx->d_insacc.ensure(accb));
+    HIP_TRY(ctx->h_insacc.ensure(accb));
+    HIP_TRY(hipMemsetAsync(ctx->d_insacc.p, 0, accb, ctx->stream));   // also "no pixel outside its interval"
+    const int mp = model_pitch(r.w);
+    InspectArgs c{};
+    c.p = patch_args(ctx, r, n, d, pitch, pbytes);
+    c.lo = ctx->d_band.as<uint8_t>() + (size_t)mp * r.h;
+    c.hi = c.lo + (size_t)mp * r.h;
+    c.mp = mp;
+    c.acc = ctx->d_insacc.as<InspectAcc>();
+    if (norm) {
+        CompareArgs s;
+        rc = model_norm_args(ctx, r, n, &s);
+        if (rc == FPM_OK) rc = compare_norm_tables(ctx, s, r, n, &c.luts);
+        if (rc != FPM_OK) return rc;
+    }
+    {
+        // bytes: source pixels read + lo and hi read (+ excess pixels written)
+        ProfScope ps(ctx, kProfModelInspect, (3 + (d ? 1 : 0)) * (int64_t)n * r.w * r.h);
+        if (!launch_model_inspect(c, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
+    }
+    HIP_TRY(hipGetLastError());
+    InspectAcc* h = ctx->h_insacc.as<InspectAcc>();
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_insacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
+    if (d) {
+        rc = copy_patches_out(ctx, r, (size_t)n, d, pitch, pbytes, img, row_stride, patch_stride);
+        if (rc != FPM_OK) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const CompareAcc* sums = ctx->h_cmpacc.as<CompareAcc>();
+    for (int i = 0; i < n; ++i) {
+        fpm_inspect_stats& s = out[i];
+        const uint32_t* f = h[i].f;
+        s.n = (int64_t)r.w * r.h;
+        s.sum_excess = (int64_t)f[kInsSumExcess];
+        s.n_low = (int32_t)f[kInsNLow]; s.n_high = (int32_t)f[kInsNHigh]; s.max_excess = (int32_t)f[kInsMaxExcess];
+        s.x0 = r.w - (int32_t)f[kInsX0]; s.y0 = r.h - (int32_t)f[kInsY0];
+        s.x1 = (int32_t)f[kInsX1] - 1; s.y1 = (int32_t)f[kInsY1] - 1;
+        s.gain = 1.0; s.offset = 0.0;
+        if (norm) {
+            double z;
+            compare_derive(s.n, (int64_t)sums[i].s[kCmpSumI], (int64_t)sums[i].s[kCmpSumII], (int64_t)sums[i].s[kCmpSumT],
+                           (int64_t)sums[i].s[kCmpSumTT], (int64_t)sums[i].s[kCmpSumIT], true, &z, &s.gain, &s.offset, nullptr);
+        }
+    }
+    return FPM_OK;
+}
+
+// fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
+// the device learn's second half
+int learn_from_model(fpm_ctx* ctx) {
+    const fpm_patch_rect r = ctx->model_rect;
+    std::vector<TmplLevel> lv;
+    int rc = learn_begin(ctx, r.w, r.h, lv);
+    if (rc != FPM_OK) return rc;
+    const size_t px = (size_t)r.w * r.h;
+    ModelPrepareArgs p{};
+    p.sum = ctx->d_model.as<uint32_t>();
+    p.sum_sq = p.sum + px;
+    p.w = r.w; p.h = r.h; p.n = ctx->model_n;
+    p.mean = ctx->d_tmpl.as<uint8_t>() + lv[0].off;
+    p.pitch = lv[0].pitch;
+    {
+        ProfScope ps(ctx, kProfModelPrepare, (int64_t)px * (2 * (int64_t)sizeof(uint32_t) + 1));
+        launch_model_prepare(p, ctx->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return learn_finish(ctx, lv);
 }
 
 }  // namespace
@@ -2369,6 +2621,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_patchtab.release(); ctx->h_patchtab.release(); ctx->d_patch.release();
     ctx->d_cmpacc.release(); ctx->h_cmpacc.release();
     ctx->d_tacc.release(); ctx->h_tacc.release();
+    ctx->d_model.release(); ctx->d_band.release(); ctx->d_insacc.release(); ctx->h_insacc.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -2402,6 +2655,7 @@ int fpm_learn(fpm_ctx* ctx, const uint8_t* gray, int32_t w, int32_t h, size_t st
     ctx->learned = false;
     ctx->staged = false;
     ctx->src_valid = false;   // the slab's layout follows the template's pyramid depth
+    ctx->model_n = 0;         // the variation model belongs to the template before
     ctx->tmpl.clear();
     const int L = top_layer(w, h, (int)std::sqrt((double)ctx->prm.min_reduce_area));
     std::vector<TmplLevel> lv(L + 1);
@@ -2483,6 +2737,7 @@ int fpm_clear_pattern(fpm_ctx* ctx) {
     ctx->src_valid = false;
     ctx->tmpl.clear();
     ctx->tmpl_gen++;
+    ctx->model_n = 0;
     return FPM_OK;
 }
 
@@ -2827,6 +3082,171 @@ int fpm_learn_at(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, float
 int fpm_learn_hit(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t index) {
     if (!ctx) return FPM_E_INVALID_ARG;
     return learn_pose_entry(ctx, rect, true, source, index, nullptr);
+}
+
+// --- variation model ------------------------------------------------------------------
+int fpm_model_derive(int32_t n, int64_t sum, int64_t sum_sq, int32_t a, int32_t kq, int32_t* mean, int32_t* lo,
+                     int32_t* hi) {
+    if (!mean || !lo || !hi || n < 1 || n > kModelMaxSamples || a < 0 || a > 255 || kq < 0 || kq > 255) return FPM_E_INVALID_ARG;
+    // sums of n bytes and of their squares: v <= v^2 <= 255 v and v^2 = v (mod 2) hold per sample, so for the sums
+    if (sum < 0 || sum > 255 * (int64_t)n || sum_sq < sum || sum_sq > 255 * sum || ((sum_sq ^ sum) & 1)) return FPM_E_INVALID_ARG;
+    if ((int64_t)n * sum_sq < sum * sum) return FPM_E_INVALID_ARG;   // of no samples (Cauchy-Schwarz)
+    const ModelBand b = model_band((uint32_t)n, (uint32_t)sum, (uint32_t)sum_sq, (uint32_t)a, (uint32_t)kq);
+    *mean = b.mean; *lo = b.lo; *hi = b.hi;
+    return FPM_OK;
+}
+
+int fpm_model_clear(fpm_ctx* ctx) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = kInFlight; return FPM_E_INVALID_ARG; }
+    ctx->model_n = 0;
+    return FPM_OK;
+}
+
+int fpm_model_set_chunk(fpm_ctx* ctx, int32_t jobs) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (jobs < 0) { ctx->err = "chunk must be 0 (the engine's choice) or a number of jobs"; return FPM_E_INVALID_ARG; }
+    ctx->model_chunk = jobs;
+    return FPM_OK;
+}
+
+int fpm_model_info(const fpm_ctx* ctx, int32_t* n, fpm_patch_rect* rect) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = ctx->model_n;
+    if (rect) *rect = ctx->model_n > 0 ? ctx->model_rect : fpm_patch_rect{0, 0, 0, 0};
+    return FPM_OK;
+}
+
+int fpm_model_train_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t flags, int32_t* n_added) {
+    if (!ctx || !n_added) return FPM_E_INVALID_ARG;
+    *n_added = 0;
+    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown training flags"; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    int32_t n = 0;
+    int rc = last_patches_begin(ctx, rect, source, INT32_MAX, &n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = model_train(ctx, r, poses, flags);
+    if (rc == FPM_OK) *n_added = n;
+    return rc;
+}
+
+int fpm_model_train_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                       const double* angles, int32_t n_poses, int32_t flags) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown training flags"; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    int rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return model_train(ctx, r, poses, flags);
+}
+
+int fpm_model_sums(fpm_ctx* ctx, uint32_t* sum, uint32_t* sum_sq) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = kInFlight; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    const int rc = model_need(ctx, &r);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)r.w * r.h, plane = px * sizeof(uint32_t);
+    // training returns with the stream drained: the planes are complete
+    if (sum) HIP_TRY(hipMemcpy(sum, ctx->d_model.p, plane, hipMemcpyDeviceToHost));
+    if (sum_sq) HIP_TRY(hipMemcpy(sum_sq, ctx->d_model.as<uint32_t>() + px, plane, hipMemcpyDeviceToHost));
+    return FPM_OK;
+}
+
+int fpm_model_images(fpm_ctx* ctx, int32_t a, int32_t kq, uint8_t* mean, uint8_t* lo, uint8_t* hi, size_t row_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = kInFlight; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    int rc = model_need(ctx, &r);
+    if (rc == FPM_OK) rc = model_args(ctx, a, kq);
+    if (rc != FPM_OK) return rc;
+    if (row_stride < (size_t)r.w) { ctx->err = "row_stride below the model's width"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = model_band_ensure(ctx, a, kq);
+    if (rc != FPM_OK) return rc;
+    const size_t pitch = (size_t)model_pitch(r.w), plane = pitch * r.h;
+    uint8_t* outs[3] = {mean, lo, hi};
+    for (int k = 0; k < 3; ++k)
+        if (outs[k])
+            HIP_TRY(hipMemcpy2DAsync(outs[k], row_stride, ctx->d_band.as<uint8_t>() + k * plane, pitch, r.w, r.h,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    return FPM_OK;
+}
+
+static int inspect_args(fpm_ctx* ctx, int32_t a, int32_t kq, int32_t flags) {
+    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown inspection flags"; return FPM_E_INVALID_ARG; }
+    return model_args(ctx, a, kq);
+}
+
+int fpm_last_inspect(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out,
+                     int32_t cap, int32_t* n, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = inspect_args(ctx, a, kq, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r, mr;
+    std::vector<PatchPose> poses;
+    rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = model_need(ctx, &mr);
+    if (rc == FPM_OK) rc = last_patches_begin(ctx, &mr, source, cap, n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
+    if (img && (rc = check_patch_out(ctx, img, r, row_stride, patch_stride)) != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return inspect_to_host(ctx, r, poses, a, kq, flags, out, img, row_stride, patch_stride);
+}
+
+int fpm_inspect_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                   int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out, uint8_t* img, size_t row_stride,
+                   size_t patch_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = inspect_args(ctx, a, kq, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r, mr;
+    rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = model_need(ctx, &mr);
+    if (rc == FPM_OK) rc = compare_rect(ctx, &mr, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
+    if (img && (rc = check_patch_out(ctx, img, r, row_stride, patch_stride)) != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return inspect_to_host(ctx, r, poses, a, kq, flags, out, img, row_stride, patch_stride);
+}
+
+int fpm_model_learn(fpm_ctx* ctx) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = kInFlight; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    int rc = model_need(ctx, &r);
+    if (rc == FPM_OK) rc = learn_size(ctx, r.w, r.h);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = learn_from_model(ctx);
+    if (rc != FPM_OK) return learn_fail(ctx, rc);
+    ctx->model_rect = fpm_patch_rect{0, 0, r.w, r.h};   // the new template's frame: the region the model was trained on
+    return FPM_OK;
+}
+
+int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || which < 0 || which > 2 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfModelTrain + which];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
 }
 
 int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count) {

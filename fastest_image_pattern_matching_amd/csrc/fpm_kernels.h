@@ -254,6 +254,46 @@ struct CompareArgs {
 enum { kCompareRaw, kCompareSums, kCompareDevLut };
 // k_patch_compare, k_patch_warp's grid.  Returns false, launching nothing, for a grid past 2^31 - 1 or an unknown form.
 bool launch_patch_compare(CompareArgs c, int form, hipStream_t st);
+// ---- variation model (fpm_model_* / fpm_last_inspect / fpm_inspect_at): the patches of a job table
+// summed per pixel into two u32 planes, the planes turned into u8 mean / lo / hi planes, and patches held against lo / hi.
+struct ModelAccumArgs {
+    PatchArgs p;             // jobs, sources and patch size as for k_patch_warp; out unused
+    uint32_t* sum;           // dense pw x ph planes: sum v and sum v^2 over the samples
+    uint32_t* sum_sq;
+    const uint8_t* luts;     // [njobs][256] (normalised training), 4-byte aligned; null = the pixels as sampled
+    int32_t chunk;           // consecutive jobs per workgroup (set by launch_model_accum from its argument)
+    int32_t nchunks;         // ceil(njobs / chunk); 1: one owner per pixel, plain adds; else atomic adds
+};
+// k_model_accum: one workgroup per (chunk of jobs, 64 x 16 tile).  chunk 1 .. njobs.  Returns false, launching
+// nothing, for a bad chunk or a grid past 2^31 - 1.
+bool launch_model_accum(ModelAccumArgs m, int chunk, hipStream_t st);
+struct ModelPrepareArgs {
+    const uint32_t* sum;     // dense w x h
+    const uint32_t* sum_sq;
+    int32_t w, h, n;         // n = samples, 1 .. 65535
+    int32_t a, kq;           // absolute threshold 0 .. 255; sigma multiple in sixteenths 0 .. 255
+    uint8_t* mean;           // each may be null; rows pitch bytes apart
+    uint8_t* lo;
+    uint8_t* hi;
+    int32_t pitch;
+};
+void launch_model_prepare(const ModelPrepareArgs& a, hipStream_t st);
+// The fields a workgroup of k_model_inspect reduces, and the hit's record (zero-filled before the launch): sums first,
+// then maxima; the box of the pixels outside their interval is kept as CompareAcc keeps its own.
+enum { kInsSumExcess, kInsNLow, kInsNHigh, kInsMaxExcess, kInsX0, kInsY0, kInsX1, kInsY1, kInspectFields };
+struct InspectAcc {
+    uint32_t f[kInspectFields];   // sum_excess <= 2^22 * 255 fits
+};
+struct InspectArgs {
+    PatchArgs p;             // out = the excess images or null
+    const uint8_t* lo;       // the model's planes in rectangle coordinates, row pitch mp (>= pw + 4, a multiple of 64)
+    const uint8_t* hi;
+    int32_t mp;
+    const uint8_t* luts;     // [njobs][256] or null
+    InspectAcc* acc;         // [njobs]
+};
+// k_model_inspect, k_patch_warp's grid; the table form when luts is set.  Returns false for a grid past 2^31 - 1.
+bool launch_model_inspect(InspectArgs c, hipStream_t st);
 // ---- learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit): what learnPattern
 // derives from a template pyramid that already lies in the template slab, in one launch over all its levels.
 constexpr int kTmplPrepMaxLevels = 16;   // a 2^26-pixel template at min_reduce_area 1 has 13 levels above level 0

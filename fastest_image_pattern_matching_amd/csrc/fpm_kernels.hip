@@ -31,6 +31,7 @@
 
 #include "../../include/fpm.h"   // FPM_FMT_* (k_stage_gray)
 #include "fpm_kernels.h"
+#include "fpm_model.h"
 #include "fpm_rrect.h"
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember, per (device, kernel), the largest dynamic
@@ -2642,18 +2643,15 @@ struct PatchTile {
     const uint8_t* img;      // level 0 of the job's source
 };
 
-// The tile of this workgroup: the fixed-point terms into `tab`, the footprint into `FT` where it lies inside the
-// image and fits.  Holds barriers: every lane of the workgroup calls it.  On return tab and FT may be read.
-__device__ __forceinline__ PatchTile patch_tile_stage(const PatchArgs& a, int32_t* tab, uint8_t* FT, int tid) {
+// Tile (tx, ty) of patch p: the fixed-point terms into `tab`, the footprint into `FT` where it lies inside the
+// image and fits.  Holds barriers: every lane of the workgroup calls it, with the same p, tx and ty.  On return tab and
+// FT may be read; a caller that stages another tile afterwards (k_model_accum) puts a barrier before it.
+__device__ __forceinline__ PatchTile patch_tile_stage_at(const PatchArgs& a, int32_t* tab, uint8_t* FT, int tid, int p,
+                                                         int tx, int ty) {
     int32_t* const ad = tab;
     int32_t* const bd = tab + kPatchTw;
     int32_t* const X0 = tab + 2 * kPatchTw;
     int32_t* const Y0 = X0 + kPatchTh;
-    // neighbouring tiles share footprint lines and output lines: keep them on one XCD's L2 (speed only)
-    const int b = xcd_remap(blockIdx.x, gridDim.x);
-    const int tiles = a.tiles_x * a.tiles_y;
-    const int p = b / tiles, t = b - p * tiles;
-    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
     const int x0 = tx * kPatchTw, y0 = ty * kPatchTh;
     const PatchJob& j = a.jobs[p];
     if (tid < kPatchTw) {
@@ -2692,6 +2690,16 @@ __device__ __forceinline__ PatchTile patch_tile_stage(const PatchArgs& a, int32_
         __syncthreads();
     }
     return {p, x0, y0, bxa, by0, in_lds, img};
+}
+
+// The tile of this workgroup in a grid of one workgroup per (patch, tile): k_patch_warp, k_patch_compare, k_model_inspect.
+__device__ __forceinline__ PatchTile patch_tile_stage(const PatchArgs& a, int32_t* tab, uint8_t* FT, int tid) {
+    // neighbouring tiles share footprint lines and output lines: keep them on one XCD's L2 (speed only)
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int p = b / tiles, t = b - p * tiles;
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    return patch_tile_stage_at(a, tab, FT, tid, p, tx, ty);
 }
 
 // The first `nu` (0 .. 4) of the 4 adjacent pixels of tile row r from tile column gx, packed low byte first; the
@@ -2916,6 +2924,223 @@ bool launch_patch_warp(PatchArgs a, hipStream_t st) {
     const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
     if (grid > INT_MAX) return false;
     hipLaunchKernelGGL(k_patch_warp, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return true;
+}
+
+// ============================================================================================== variation model
+// k_model_accum (fpm_model_train_last / fpm_model_train_at): the per-pixel sum and sum of squares
+// of the patches of a job table, none of them written.  k_patch_warp's tile and 4 pixels per lane; a workgroup owns one
+// tile and `chunk` consecutive jobs, stages and samples each job's footprint in turn (patch_tile_stage_at /
+// patch_sample4) and keeps 4 + 4 running sums per lane in registers: 65535 samples of 255^2 fit 32 bits.  At the end it
+// adds them to the planes: with one chunk per tile (SINGLE) every pixel has one owner in the launch and the add is a
+// plain read-modify-write; otherwise it is an integer atomic whose result nobody reads.  Integer sums either way: the
+// planes do not depend on the order of the workgroups.
+//   LUT: the sample is L[pixel], L = the job's 256-byte table, staged in LDS anew for every job
+// The job loop's bounds come from blockIdx, so its barriers are workgroup-uniform; the barrier at the end of a turn
+// keeps the next job's tables and footprint from overwriting what a slower wave still samples.
+template <bool LUT, bool SINGLE>
+__global__ __launch_bounds__(256) void k_model_accum(const ModelAccumArgs m) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
+    const PatchArgs& a = m.p;
+    const int tid = threadIdx.x;
+    // a tile's chunks are neighbours in the grid: the footprints of one tile across jobs share nothing, those of
+    // neighbouring tiles of one job do, so the tile index runs fastest
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int c = b / tiles, t = b - c * tiles;
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const int j0 = c * m.chunk, j1 = j0 + m.chunk < a.njobs ? j0 + m.chunk : a.njobs;
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = tx * kPatchTw + gx, y = ty * kPatchTh + r;
+    const int left = a.pw - x;
+    const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
+    uint32_t s[4] = {0u, 0u, 0u, 0u}, q[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (int j = j0; j < j1; ++j) {
+        if (LUT) {   // patch_tile_stage_at's first barrier orders these writes before any read
+            if (tid < 64) ((uint32_t*)lut)[tid] = ((const uint32_t*)(m.luts + (size_t)j * 256))[tid];
+        }
+        const PatchTile T = patch_tile_stage_at(a, tab, FT, tid, j, tx, ty);
+        const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t i = (iw >> (8 * u)) & 255u;
+            const uint32_t v = u < nu ? (LUT ? (uint32_t)lut[i] : i) : 0u;   // past the edge: nothing (L[0] may not be 0)
+            s[u] += v;
+            q[u] += v * v;
+        }
+        __syncthreads();
+    }
+    if (nu == 0) return;
+    const size_t i0 = (size_t)y * a.pw + x;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (u >= nu) break;
+        if (SINGLE) {
+            m.sum[i0 + u] += s[u];
+            m.sum_sq[i0 + u] += q[u];
+        } else if (s[u]) {   // v = 0 throughout changes neither plane
+            atomicAdd(&m.sum[i0 + u], s[u]);
+            atomicAdd(&m.sum_sq[i0 + u], q[u]);
+        }
+    }
+}
+
+bool launch_model_accum(ModelAccumArgs m, int chunk, hipStream_t st) {
+    PatchArgs& a = m.p;
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    if (chunk < 1 || chunk > a.njobs || !m.sum || !m.sum_sq) return false;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    m.chunk = chunk;
+    m.nchunks = (a.njobs + chunk - 1) / chunk;
+    const int64_t grid = (int64_t)m.nchunks * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX) return false;
+    const dim3 g((unsigned)grid), blk(256);
+    const bool single = m.nchunks == 1;
+    if (m.luts) {
+        if (single) hipLaunchKernelGGL((k_model_accum<true, true>), g, blk, 0, st, m);
+        else hipLaunchKernelGGL((k_model_accum<true, false>), g, blk, 0, st, m);
+    } else {
+        if (single) hipLaunchKernelGGL((k_model_accum<false, true>), g, blk, 0, st, m);
+        else hipLaunchKernelGGL((k_model_accum<false, false>), g, blk, 0, st, m);
+    }
+    return true;
+}
+
+// k_model_prepare: mean, lo and hi of every pixel from the planes (model_band, fpm_model.h: the code fpm_model_derive
+// runs on the host), as u8 planes with a row pitch; a plane that is null is not written.  One pixel per lane.
+__global__ __launch_bounds__(256) void k_model_prepare(const ModelPrepareArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)a.w * a.h) return;
+    const int y = (int)(i / a.w), x = (int)(i - (int64_t)y * a.w);
+    const ModelBand b = model_band((uint32_t)a.n, a.sum[i], a.sum_sq[i], (uint32_t)a.a, (uint32_t)a.kq);
+    const size_t o = (size_t)y * a.pitch + x;
+    if (a.mean) a.mean[o] = (uint8_t)b.mean;
+    if (a.lo) a.lo[o] = (uint8_t)b.lo;
+    if (a.hi) a.hi[o] = (uint8_t)b.hi;
+}
+
+void launch_model_prepare(const ModelPrepareArgs& a, hipStream_t st) {
+    if (a.w <= 0 || a.h <= 0) return;
+    const int64_t px = (int64_t)a.w * a.h;   // <= 2^22
+    hipLaunchKernelGGL(k_model_prepare, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// k_model_inspect (fpm_last_inspect / fpm_inspect_at): k_patch_compare's deviation half with the model's lo and hi
+// planes beneath the pixels in place of the template.  Per pixel the excess e = lo - v below the interval, v - hi
+// above it, else 0 (v = L[pixel] in the table form); per hit sum e, max e, the counts of pixels below and above and the
+// box of both.  Lanes past the patch's edge go through every barrier with nu = 0 and add nothing; the reduction is
+// k_patch_compare's: DPP for the sum and the maximum, lane votes for the counts and the box, LDS across the four
+// waves, one integer atomic per non-zero field and workgroup into the zero-filled record.
+//   IMG: e is also stored as the excess image (PatchArgs::out, as k_patch_warp stores the patch)
+__device__ __forceinline__ uint32_t plane_read4(const uint8_t* row, int x, int pitch) {
+    // 4 bytes from column x: an aligned dword pair funnel-shifted to the first byte; the second dword is read only
+    // where it is inside the row
+    const int c0 = x & ~3;
+    const uint32_t lo = *(const uint32_t*)(row + c0);
+    const uint32_t hi = (x & 3) && c0 + 4 < pitch ? *(const uint32_t*)(row + c0 + 4) : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)x);
+}
+
+template <bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_model_inspect(const InspectArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
+    __shared__ uint32_t part[4][kInspectFields];
+    const PatchArgs& a = c.p;
+    const int tid = threadIdx.x;
+    if (LUT) {
+        // the job index as patch_tile_stage derives it; the helper's first barrier orders these writes before any read
+        const int job = xcd_remap(blockIdx.x, gridDim.x) / (a.tiles_x * a.tiles_y);
+        if (tid < 64) ((uint32_t*)lut)[tid] = ((const uint32_t*)(c.luts + (size_t)job * 256))[tid];
+    }
+    const PatchTile T = patch_tile_stage(a, tab, FT, tid);
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = T.x0 + gx, y = T.y0 + r;
+    const int left = a.pw - x;
+    const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
+    const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
+    uint32_t lw = 0, hw = 0;
+    if (nu > 0) {
+        lw = plane_read4(c.lo + (size_t)y * c.mp, x, c.mp);
+        hw = plane_read4(c.hi + (size_t)y * c.mp, x, c.mp);
+    }
+    uint32_t ew = 0, emax = 0, low = 0, high = 0;   // low / high: bit u = pixel u lies below / above its interval
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (iw >> (8 * u)) & 255, lo = (lw >> (8 * u)) & 255, hi = (hw >> (8 * u)) & 255;
+        const int v = LUT ? (int)lut[i] : i;
+        const bool in = u < nu, isl = in && v < lo, ish = in && !isl && v > hi;
+        const uint32_t e = isl ? (uint32_t)(lo - v) : (ish ? (uint32_t)(v - hi) : 0u);
+        ew |= e << (8 * u);
+        emax = e > emax ? e : emax;
+        low |= (uint32_t)isl << u;
+        high |= (uint32_t)ish << u;
+    }
+    if (IMG && nu > 0)
+        patch_store4(a.out + a.jobs[T.job].out_off + (size_t)y * a.row_stride + x, ew, nu, a.dword != 0);
+    uint32_t wv[kInspectFields];
+#pragma unroll
+    for (int k = 0; k < kInspectFields; ++k) wv[k] = 0;
+    wv[kInsSumExcess] = wave_fold<false>(__builtin_amdgcn_udot4(ew, 0x01010101u, 0u, false));
+    wv[kInsMaxExcess] = wave_fold<true>(emax);
+    // the counts and the box from the lanes' votes, in scalar registers
+    const uint32_t out = low | high;
+    int cnt = 0, cmin = kPatchTw, cmax = -1, rmin = 4, rmax = -1;
+    vote_box(__ballot(out & 1u), 0, cnt, cmin, cmax, rmin, rmax);
+    vote_box(__ballot(out & 2u), 1, cnt, cmin, cmax, rmin, rmax);
+    vote_box(__ballot(out & 4u), 2, cnt, cmin, cmax, rmin, rmax);
+    vote_box(__ballot(out & 8u), 3, cnt, cmin, cmax, rmin, rmax);
+    if (cnt > 0) {
+        const int nlow = __popcll(__ballot(low & 1u)) + __popcll(__ballot(low & 2u)) + __popcll(__ballot(low & 4u)) +
+                         __popcll(__ballot(low & 8u));
+        const int wy = T.y0 + 4 * (tid >> 6);   // the wave's first tile row in the patch
+        wv[kInsNLow] = (uint32_t)nlow;
+        wv[kInsNHigh] = (uint32_t)(cnt - nlow);
+        wv[kInsX0] = (uint32_t)(a.pw - (T.x0 + cmin));
+        wv[kInsX1] = (uint32_t)(T.x0 + cmax + 1);
+        wv[kInsY0] = (uint32_t)(a.ph - (wy + rmin));
+        wv[kInsY1] = (uint32_t)(wy + rmax + 1);
+    }
+    if ((tid & 63) == 0) {
+        const int wave = tid >> 6;
+#pragma unroll
+        for (int k = 0; k < kInspectFields; ++k) part[wave][k] = wv[k];
+    }
+    __syncthreads();
+    if (tid < kInspectFields) {
+        const uint32_t p0 = part[0][tid], p1 = part[1][tid], p2 = part[2][tid], p3 = part[3][tid];
+        uint32_t* f = &c.acc[T.job].f[tid];
+        if (tid >= kInsMaxExcess) {
+            const uint32_t m01 = p0 > p1 ? p0 : p1, m23 = p2 > p3 ? p2 : p3, m = m01 > m23 ? m01 : m23;
+            if (m) atomicMax(f, m);
+        } else {
+            const uint32_t s = p0 + p1 + p2 + p3;
+            if (s) atomicAdd(f, s);
+        }
+    }
+}
+
+bool launch_model_inspect(InspectArgs c, hipStream_t st) {
+    PatchArgs& a = c.p;
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX) return false;
+    const dim3 g((unsigned)grid), blk(256);
+    const bool img = a.out != nullptr;
+    if (c.luts) {
+        if (img) hipLaunchKernelGGL((k_model_inspect<true, true>), g, blk, 0, st, c);
+        else hipLaunchKernelGGL((k_model_inspect<true, false>), g, blk, 0, st, c);
+    } else {
+        if (img) hipLaunchKernelGGL((k_model_inspect<false, true>), g, blk, 0, st, c);
+        else hipLaunchKernelGGL((k_model_inspect<false, false>), g, blk, 0, st, c);
+    }
     return true;
 }
 

@@ -325,6 +325,41 @@ def learn_derive(n: int, total: int, total_sq: int):
     return mean.value, norm.value, inv.value, bool(eq.value)
 
 
+# -- variation model (fpm_model_* / fpm_last_inspect / fpm_inspect_at / fpm_model_derive) -----------------------------
+# one row per hit: fpm_inspect_stats, field for field
+INSPECT_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.InspectStats._fields_], align=True)
+assert INSPECT_DTYPE.itemsize == C.sizeof(L.InspectStats)
+
+
+def model_thresholds(abs_threshold, k) -> Tuple[int, int]:
+    """(a, kq) of the library for an absolute threshold 0 .. 255 and a sigma multiple ``k`` (a float, taken to
+    sixteenths by round; 0 .. 255 sixteenths).  Raises ValueError outside those ranges.  Pure: no device."""
+    a = int(abs_threshold)
+    if a != abs_threshold or not 0 <= a <= 255:
+        raise ValueError(f"abs_threshold {abs_threshold!r} must be a whole number 0 .. 255")
+    kf = float(k)
+    if not np.isfinite(kf):
+        raise ValueError(f"k {k!r} must be finite")
+    kq = int(round(kf * 16.0))
+    if not 0 <= kq <= 255:
+        raise ValueError(f"k {k!r} is {kq} sixteenths: 0 .. 255 expected")
+    return a, kq
+
+
+def model_derive(n: int, total: int, total_sq: int, abs_threshold: int = 8, k: float = 3.0):
+    """fpm_model_derive: ``(mean, lo, hi)`` of one pixel of a variation model from its sample count and the exact sums of
+    the samples and of their squares, by the code the device runs (exact integers; ``lo == hi + 1`` is the empty
+    interval).  Host only (no device).  Raises ValueError for sums that are those of no ``n`` bytes."""
+    a, kq = model_thresholds(abs_threshold, k)
+    mean, lo, hi = C.c_int32(), C.c_int32(), C.c_int32()
+    if not (-2 ** 31 <= int(n) < 2 ** 31 and -2 ** 63 <= int(total) < 2 ** 63 and -2 ** 63 <= int(total_sq) < 2 ** 63):
+        raise ValueError("fpm_model_derive: argument out of range")
+    rc = L.load().fpm_model_derive(int(n), int(total), int(total_sq), a, kq, C.byref(mean), C.byref(lo), C.byref(hi))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_model_derive failed with {rc}")
+    return mean.value, lo.value, hi.value
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -909,6 +944,139 @@ class TemplateMatcher:
         if rc != L.FPM_OK:
             self._patch_fail(rc, "compare_at")
         return (stats, img) if diff else stats
+
+    # -- variation model: per-pixel tolerances trained from hits, inspection on the device (fpm_model_* / fpm_*inspect*) --
+    def model_clear(self):
+        """Drops the variation model (fpm_model_clear)."""
+        rc = self._lib.fpm_model_clear(self._ctx)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_clear")
+
+    def model_set_chunk(self, jobs: int = 0):
+        """fpm_model_set_chunk: samples per workgroup of the training kernel; 0 = the engine's choice.  The sums do not
+        depend on it (parity tests and measurements)."""
+        rc = self._lib.fpm_model_set_chunk(self._ctx, int(jobs))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_set_chunk")
+
+    def model_train_last(self, source: int = -1, rect=None, normalize: bool = False) -> int:
+        """Adds the hits of the last search (``source=-1``: of all sources) to the variation model, where the pixels
+        are: per pixel of ``rect`` the sum and the sum of squares of what last_patches gives there, in two uint32 planes
+        on the device (fpm_model_train_last); returns the number of samples added.  ``rect``: as last_compare's, fixed
+        by the first call after model_clear.  ``normalize``: the samples go through the hit's gain / offset table first,
+        as in last_compare.  At most 65535 samples; restaging keeps the model, every learn entry but model_learn drops
+        it."""
+        r, _, _ = self._compare_rect(rect)
+        n = C.c_int32()
+        rc = self._lib.fpm_model_train_last(self._ctx, C.byref(r) if r is not None else None, int(source),
+                                            L.COMPARE_NORMALIZE if normalize else 0, C.byref(n))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_train_last")
+        return n.value
+
+    def model_train_at(self, src_index, lts, angles, rect=None, normalize: bool = False) -> int:
+        """model_train_last at poses the caller supplies, on the staged sources (fpm_model_train_at); poses as
+        patches_at.  Needs staged sources, not a search."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        r, _, _ = self._compare_rect(rect)
+        rc = self._lib.fpm_model_train_at(self._ctx, C.byref(r) if r is not None else None,
+                                          idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
+                                          ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx),
+                                          L.COMPARE_NORMALIZE if normalize else 0)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_train_at")
+        return len(idx)
+
+    def model_info(self):
+        """``(n, (x, y, w, h))`` of the variation model: its sample count and rectangle; ``(0, None)`` without one."""
+        n, r = C.c_int32(), L.PatchRect()
+        self._lib.fpm_model_info(self._ctx, C.byref(n), C.byref(r))
+        return (n.value, (r.x, r.y, r.w, r.h)) if n.value else (0, None)
+
+    def _model_size(self, what):
+        n, rect = self.model_info()
+        if not n:
+            raise ValueError(f"{what}: no variation model (model_train_last / model_train_at first)")
+        return rect[2], rect[3]
+
+    def model_sums(self):
+        """``(S, Q)``: the model's per-pixel sum and sum of squares, uint32 (h, w) each (fpm_model_sums)."""
+        w, h = self._model_size("model_sums")
+        s, q = np.zeros((h, w), np.uint32), np.zeros((h, w), np.uint32)
+        rc = self._lib.fpm_model_sums(self._ctx, s.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      q.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_sums")
+        return s, q
+
+    def model_images(self, abs_threshold: int = 8, k: float = 3.0):
+        """``(mean, lo, hi)``: uint8 (h, w) images of the model for an absolute threshold and a sigma multiple ``k``
+        (model_thresholds), as the device derives them: a pixel value u is inside where lo <= u <= hi, which is mean +-
+        max(abs_threshold, k sigma) in exact integers (include/fpm.h); lo == hi + 1 where no value is."""
+        a, kq = model_thresholds(abs_threshold, k)
+        w, h = self._model_size("model_images")
+        out = [np.zeros((h, w), np.uint8) for _ in range(3)]
+        rc = self._lib.fpm_model_images(self._ctx, a, kq, L.u8ptr(out[0]), L.u8ptr(out[1]), L.u8ptr(out[2]), w)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "model_images")
+        return tuple(out)
+
+    def last_inspect(self, source: int = 0, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
+                     image: bool = False):
+        """Every result of the last search held against the variation model where the pixels are: a structured array
+        (INSPECT_DTYPE), one row per result of ``source`` in result order (``source=-1``: all sources).  Per row, over
+        the model's rectangle: n, sum_excess, n_low and n_high = the pixels below lo and above hi, max_excess, their
+        inclusive bounding box x0, y0, x1, y1 in rectangle coordinates (w, h, -1, -1 when there is none), and the
+        gain and offset of ``normalize`` (1 and 0 without).  ``image=True``: also the excess per pixel as uint8 images,
+        ``(stats, (n, h, w))``.  No patch is written anywhere."""
+        a, kq = model_thresholds(abs_threshold, k)
+        w, h = self._model_size("last_inspect")
+        flags = L.COMPARE_NORMALIZE if normalize else 0
+        n = C.c_int32()
+        rc = self._lib.fpm_last_inspect(self._ctx, int(source), a, kq, flags, None, 0, C.byref(n), None, 0, 0)
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_inspect")
+        stats = np.zeros(n.value, INSPECT_DTYPE)
+        img, pimg, row, patch = self._compare_diff(image, n.value, h, w)
+        if n.value:
+            rc = self._lib.fpm_last_inspect(self._ctx, int(source), a, kq, flags,
+                                            stats.ctypes.data_as(C.POINTER(L.InspectStats)), n.value, C.byref(n), pimg,
+                                            row, patch)
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_inspect")
+        return (stats, img) if image else stats
+
+    def inspect_at(self, src_index, lts, angles, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
+                   image: bool = False):
+        """last_inspect at poses the caller supplies, on the staged sources (fpm_inspect_at); poses as patches_at."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        a, kq = model_thresholds(abs_threshold, k)
+        w, h = self._model_size("inspect_at")
+        n = len(idx)
+        stats = np.zeros(n, INSPECT_DTYPE)
+        img, pimg, row, patch = self._compare_diff(image, n, h, w)
+        rc = self._lib.fpm_inspect_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                      n, a, kq, L.COMPARE_NORMALIZE if normalize else 0,
+                                      stats.ctypes.data_as(C.POINTER(L.InspectStats)), pimg, row, patch)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "inspect_at")
+        return (stats, img) if image else stats
+
+    def model_learn(self):
+        """Learns the model's mean image as the new template, on the device (fpm_model_learn): re-teach from many good
+        parts instead of one.  State afterwards as after learn_at; the model survives with the rectangle (0, 0, w, h).
+        Raises LearnError when the call is rejected."""
+        self._push()
+        self._learn_done(self._lib.fpm_model_learn(self._ctx), "model_learn")
+
+    def model_profile(self, which: int):
+        """``(ms, launches, bytes)`` of L.MODEL_TRAIN / L.MODEL_PREPARE / L.MODEL_INSPECT, collected under profile(True)
+        and cleared by profile_reset (fpm_model_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_model_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError(f"fpm_model_profile({which}) failed")
+        return ms.value, n.value, b.value
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------
     def pyr_down(self, img) -> np.ndarray:

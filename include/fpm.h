@@ -338,6 +338,95 @@ int fpm_learn_derive(int64_t n, int64_t sum, int64_t sum_sq, double* mean, doubl
  * receive the sizes; t8 and tsum (each may be NULL) must hold that many bytes / entries */
 int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count);
 
+/* --- variation model: per-pixel tolerances trained from hits, inspection on the device (no reference equivalent) -----
+ * fpm_last_compare holds every pixel of a hit against one taught image with one threshold; an edge pixel of a good part
+ * moves by tens of gray levels under a quarter-pixel pose residue while a flat one moves by two.  A variation model is
+ * trained from many good samples instead: it keeps a per-pixel mean and a per-pixel spread, and a pixel is a defect only
+ * where it leaves mean +- max(a, k sigma).  Everything it needs is resident after a staged search (level 0 of every
+ * source, the raw poses, the template), so training and inspection write no crop.
+ * Model.  One per context: a rectangle (x, y, w, h) in template coordinates under the comparison's rules (inside the
+ * template, 1 <= w * h <= 2^22, NULL = the whole template), a sample count n, and two w x h planes of uint32 in device
+ * memory, S = sum v and Q = sum v^2 over the samples.  v is the pixel fpm_last_patches gives for that rectangle and
+ * pose (same matrix, same fixed-point bilinear arithmetic, border 0, the inverted plane under bitwise_not); with
+ * FPM_COMPARE_NORMALIZE v is LUT[that pixel], the hit's table built exactly as fpm_last_compare builds it (the sums
+ * launch against the template, fpm_compare_derive's rule, the tables to the device).  n <= 65535, so Q <= 65535 * 65025
+ * < 2^32: a training call that would exceed it returns FPM_E_CAPACITY.  A training call that fails adds nothing.
+ * The first training call after a clear fixes the rectangle; a later one with another rectangle is FPM_E_INVALID_ARG.
+ * The model is dropped by fpm_model_clear, by every learn entry but fpm_model_learn (fpm_learn, fpm_learn_device,
+ * fpm_learn_at, fpm_learn_hit), by fpm_clear_pattern and by fpm_destroy.  Restaging sources keeps it: training over
+ * several batches is the point.
+ * Derived per pixel, in exact integers (one function, run by the device and by fpm_model_derive), for an absolute
+ * threshold a = 0 .. 255 and a sigma multiple kq = 0 .. 255 in sixteenths:
+ *     V = n Q - S^2                                   (<= 2^46)
+ *     B = max(n a, isqrt((kq^2 V) >> 8))              (isqrt = the exact floor square root; the product is < 2^62)
+ *     mean = (2 S + n) / (2 n)                        (integer division: the mean rounded half up)
+ *     lo = max(0, ceil((S - B) / n)),  hi = min(255, floor((S + B) / n))
+ * B / n = max(a, (kq / 16) sigma) with sigma = sqrt(V) / n.  A value u = 0 .. 255 is inside iff |n u - S| <= B, which is
+ * iff lo <= u <= hi; lo = hi + 1 is the empty interval and can occur (n = 2, S = 21, a = 0, kq = 0: lo 11, hi 10).
+ * Excess: e(u) = lo - u for u < lo (low), else u - hi for u > hi (high), else 0.
+ * Inspection record per hit: n = w * h; sum_excess = sum e; n_low, n_high = the pixels below and above their interval;
+ * max_excess = max e; (x0, y0, x1, y1) = the inclusive bounding box of the pixels with e > 0 in rectangle coordinates,
+ * x0 = w, y0 = h, x1 = y1 = -1 when there is none; gain and offset of the hit's table (1 and 0 without the flag).  u is
+ * v as above, so with FPM_COMPARE_NORMALIZE a change of lighting is no excess.
+ * Excess image (img, may be NULL): e as u8, one w x h image per hit, image i at img + i * patch_stride, rows row_stride
+ * apart (the rules of fpm_last_patches; the bytes of a row past w are left untouched).
+ * Launches.  Training: k_model_accum, one per call.  The u8 planes mean / lo / hi: k_model_prepare, once per (a, kq,
+ * state of the sums); the inspection entries and fpm_model_images prepare only when that key changed.  Inspection:
+ * k_model_inspect, one per call.  With FPM_COMPARE_NORMALIZE the sums launch of k_patch_compare and a copy of the sums
+ * to the host come first, as in fpm_last_compare.
+ * State.  While a search is in flight every entry below is FPM_E_INVALID_ARG except fpm_model_info,
+ * fpm_model_set_chunk, fpm_model_derive and fpm_model_profile.  Additive entries: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_inspect_stats {
+    int64_t n, sum_excess;
+    int32_t n_low, n_high, max_excess, x0, y0, x1, y1;
+    double gain, offset;
+} fpm_inspect_stats;
+
+int fpm_model_clear(fpm_ctx* ctx);
+/* Training's work split: a workgroup of k_model_accum takes one 64 x 16 tile and `jobs` consecutive samples.  0 (the
+ * default) lets the engine choose: all samples of a call when the rectangle's tiles alone fill the device (one owner
+ * per pixel, plain adds), else as many chunks as bring the grid to 12 workgroups per compute unit, of at least 4 samples
+ * each (integer atomic adds).
+ * The sums are the same integers for every value; the entry is there for parity tests and measurements, as seg_chunks
+ * is in fpm_op_pyr_down2. */
+int fpm_model_set_chunk(fpm_ctx* ctx, int32_t jobs);
+/* Adds the hits of the last search (source = -1: of all sources) to the model; *n_added receives how many were added
+ * (0 when the call fails).  State and source rules as fpm_last_compare; rect as described above. */
+int fpm_model_train_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t flags, int32_t* n_added);
+/* The same at caller-supplied poses on the staged sources; poses and state rules as fpm_compare_at. */
+int fpm_model_train_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                       const double* angles, int32_t n_poses, int32_t flags);
+/* *n = the sample count, 0 = no model (rect, may be NULL, then receives zeros) */
+int fpm_model_info(const fpm_ctx* ctx, int32_t* n, fpm_patch_rect* rect);
+/* S and Q to the host, dense w x h each (each may be NULL).  FPM_E_INVALID_ARG without a model, as for every entry below. */
+int fpm_model_sums(fpm_ctx* ctx, uint32_t* sum, uint32_t* sum_sq);
+/* mean, lo and hi for (a, kq) to the host as w x h images with rows row_stride (>= w) apart; each may be NULL */
+int fpm_model_images(fpm_ctx* ctx, int32_t a, int32_t kq, uint8_t* mean, uint8_t* lo, uint8_t* hi, size_t row_stride);
+/* The hits of the last search against the model, over the model's rectangle; source, cap, *n, state rules and the image
+ * buffer as fpm_last_compare's.  flags: FPM_COMPARE_NORMALIZE or 0.  Returns when out (and img) are filled. */
+int fpm_last_inspect(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out,
+                     int32_t cap, int32_t* n, uint8_t* img, size_t row_stride, size_t patch_stride);
+/* The same at caller-supplied poses on the staged sources; poses as fpm_patches_at. */
+int fpm_inspect_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                   int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out, uint8_t* img, size_t row_stride,
+                   size_t patch_stride);
+/* Learns the model's mean image as the new template through the device learn's path: k_model_prepare writes it into
+ * level 0 of the template slab, then everything fpm_learn_at does after sampling.  State afterwards as after
+ * fpm_learn_at (staged sources kept when the top layer is unchanged, the last poses dropped), except that the model
+ * survives, with the rectangle (0, 0, w, h) -- the new template's frame: a hit of the new template and that rectangle
+ * sample the region the model was trained on. */
+int fpm_model_learn(fpm_ctx* ctx);
+/* host only, no context: mean, lo and hi of one pixel by the rule above.  FPM_E_INVALID_ARG for n outside 1 .. 65535, a
+ * or kq outside 0 .. 255, and sums that are those of no n bytes: sum outside 0 .. 255 n, sum_sq outside sum .. 255 sum
+ * or of other parity than sum (v <= v^2 <= 255 v and v^2 = v mod 2 for every byte), or n sum_sq < sum^2 */
+int fpm_model_derive(int32_t n, int64_t sum, int64_t sum_sq, int32_t a, int32_t kq, int32_t* mean, int32_t* lo,
+                     int32_t* hi);
+/* Timing of the model's kernels, collected under fpm_profile_enable and cleared by fpm_profile_reset like the FPM_K_*
+ * counters (there is no FPM_K_* index for them; the normalising sums launch counts under FPM_K_COMPARE).  which: 0 =
+ * k_model_accum (bytes = source pixels read + plane bytes written), 1 = k_model_prepare (plane bytes in and out), 2 =
+ * k_model_inspect (source pixels + lo and hi read + excess pixels written). */
+int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent

@@ -126,6 +126,15 @@ class RoiRecord(C.Structure):
                 ("vec", C.c_float * 9)]
 
 
+class Peak(C.Structure):
+    """fpm_peak — one top-layer peak (fpm_op_peaks)."""
+
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("score", C.c_float)]
+
+
+PEAKS_STATS_CALL, PEAKS_STATS_JOB = 8, 4   # FPM_PEAKS_STATS_CALL / _JOB
+PEAKS_RAN_BLOCKS, PEAKS_RAN_NMS, PEAKS_RAN_FAST, PEAKS_RAN_GREEDY = 1, 2, 4, 8   # stats[0] of fpm_op_peaks
+
 # every symbol include/fpm.h declares, with (restype, argtypes)
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
@@ -163,6 +172,10 @@ SIGNATURES = {
     "fpm_op_refine": (C.c_int, [_P, C.POINTER(_U8P), C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_int32,
                                 C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.POINTER(RoiRecord), _U8P, C.POINTER(C.c_int32)]),
+    "fpm_op_peaks": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                               C.c_int32, C.c_int32, C.c_uint32, C.POINTER(Peak), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32)]),
     "fpm_op_overlap_filter": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32, C.c_double,
                                         C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "fpm_template_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

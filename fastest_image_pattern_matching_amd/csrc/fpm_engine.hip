@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -108,6 +109,7 @@ struct Plan {
     std::vector<int32_t> order;                // k_top_fused workgroup -> job (costliest angles first)
     size_t canvas_bytes = 0, map_floats = 0, blk_count = 0;
     int max_canvas = 0, max_map = 0, max_nblk = 0, max_cells = 0, max_nitems = 0;
+    NmsMaxima nmax;                            // the top-layer maps' maxima for launch_nms / launch_top_greedy
     int off_skey = 0, nzero = 0;   // d_livecnt layout: strip keys' offset, words zeroed by k_warp
     // the matrix-core top layer (k_top_mma + k_nms_greedy on its candidate lists): layout and
     // constants of the launch (pointers set at plan time), the unit list and B fragments in d_tmu, the values of the
@@ -447,7 +449,9 @@ int plan_top_mma(fpm_ctx* ctx, Plan& P, const TmplLevel& tt) {
     const double thr = P.layer_score[L];
     int max_mw = 0, max_mh = 0;
     for (int a = 0; a < P.nang; ++a) { max_mw = std::max(max_mw, P.map_w[a]); max_mh = std::max(max_mh, P.map_h[a]); }
+    // (MaxOverlap < 0: a painted rectangle of more than twice the template outgrows the 3 x 3 cells k_nms_greedy files it in)
     if (L < 1 || J <= 0 || !top_mma_fits(tt.w, tt.h) || tt.equal1 || !(thr > 0.01) || max_mw <= 0 ||
+        !(ctx->prm.max_overlap >= 0.0) ||
         std::max(max_mw, max_mh) >= 65536 || P.cap > 256 || P.max_cells > 12 * 1024)
         return FPM_OK;
     // strip width: one strip up to 192 output columns, else the fewest strips of at most 192, evened out
@@ -602,7 +606,7 @@ int build_plan(fpm_ctx* ctx) {
     P.canvas_pitch.resize(P.nang); P.map_w.resize(P.nang); P.map_h.resize(P.nang); P.nblk.resize(P.nang);
     std::vector<std::array<double, 6>> mats(P.nang);
     size_t co = 0, mo = 0, bo = 0;
-    P.max_canvas = 0; P.max_map = 0; P.max_nblk = 0; P.max_cells = 0; P.max_nitems = 0;
+    P.max_canvas = 0; P.max_map = 0; P.nmax = NmsMaxima{};
     for (int a = 0; a < P.nang; ++a) {
         int bw, bh;
         best_rotation_size(top.w, top.h, tt.w, tt.h, P.angles[a], &bw, &bh);
@@ -626,25 +630,17 @@ int build_plan(fpm_ctx* ctx) {
         P.map_h[a] = ok ? bh - tt.h + 1 : 0;
         P.map_off[a] = mo;
         mo += round_up((size_t)P.map_w[a] * P.map_h[a], (size_t)64);
-        int nb = 0;
-        if (P.by_block && ok) {   // s_BlockMax blocks (BlockGeom in fpm_kernels.hip: Qt or MFC layout)
-            const int bw = mfc ? 2 * tt.w : tt.w, bh = mfc ? 2 * tt.h : tt.h;
-            const int ncol = P.map_w[a] / bw, nrow = P.map_h[a] / bh;
-            const int rw = P.map_w[a] - ncol * bw, rh = P.map_h[a] - nrow * bh;
-            if (!mfc) nb = ncol * nrow + (rw > 0) + (rh > 0) + (rw > 0 && rh > 0);
-            else nb = (ncol == 0 || nrow == 0) ? 0 : ncol * nrow + ((rw > 0 && rh > 0) ? 2 : 1);
-            P.max_nitems = std::max(P.max_nitems, nms_block_items(P.map_w[a], P.map_h[a], tt.w, tt.h, mfc ? 1 : 0));
-        }
-        if (ok)   // coverage cells of the greedy peak forms (k_nms_greedy), plain and s_BlockMax alike
-            P.max_cells = std::max(P.max_cells, ((P.map_w[a] + tt.w - 1) / tt.w) * ((P.map_h[a] + tt.h - 1) / tt.h));
+        // s_BlockMax blocks (BlockGeom in fpm_kernels.hip: Qt or MFC layout) and the peak launchers' maxima, by the
+        // function fpm_op_peaks uses for its maps
+        const int nb = nms_maxima_add(P.nmax, P.map_w[a], P.map_h[a], tt.w, tt.h, P.by_block ? 1 : 0, mfc ? 1 : 0);
         P.nblk[a] = nb;
-        P.max_nblk = std::max(P.max_nblk, nb);
         P.blk_off[a] = bo;
         bo += round_up((size_t)nb, (size_t)64);
         P.max_canvas = std::max(P.max_canvas, bw * bh);
         P.max_map = std::max(P.max_map, P.map_w[a] * P.map_h[a]);
     }
     P.canvas_bytes = co; P.map_floats = mo; P.blk_count = bo;
+    P.max_nblk = P.nmax.max_blocks; P.max_cells = P.nmax.max_cells; P.max_nitems = P.nmax.max_items;
     // refinement angle tree: level d has nang * n3^(d+1) nodes (TemplateMatcher.cpp:282-298)
     P.nodes.assign(L, {});
     P.node_off.assign(L, 0);
@@ -945,12 +941,8 @@ int enqueue_search(fpm_ctx* ctx) {
         cand_fused = top_init;
     }
     if (use_mma) {
-        int mdim = 0;
-        long mpx = 0;
-        for (int a = 0; a < P.nang; ++a) {
-            mdim = std::max(mdim, std::max(P.map_w[a], P.map_h[a]));
-            mpx = std::max(mpx, (long)P.map_w[a] * P.map_h[a]);
-        }
+        const int mdim = P.nmax.max_map_dim;
+        const long mpx = P.nmax.max_map_px;
         TopMmaArgs ta = P.tma;
         {   // canvases, correlation, scores and the lists of outputs >= the layer score; profiling bytes: the top level
             // read per angle (its share of B_top; the map is never written)
@@ -1011,12 +1003,8 @@ int enqueue_search(fpm_ctx* ctx) {
             na.skey = (uint64_t*)(P.d_livecnt.as<int32_t>() + P.off_skey);
             na.sdone = P.d_livecnt.as<int32_t>() + P.off_skey + 6 * J;
         }
-        int mdim = 0;
-        long mpx = 0;
-        for (int a = 0; a < P.nang; ++a) {
-            mdim = std::max(mdim, std::max(P.map_w[a], P.map_h[a]));
-            mpx = std::max(mpx, (long)P.map_w[a] * P.map_h[a]);
-        }
+        const int mdim = P.nmax.max_map_dim;
+        const long mpx = P.nmax.max_map_px;
         // plain path: k_nms also initialises the candidates (the live counter was zeroed by k_warp)
         cand_fused = !P.by_block && P.cap <= kNmsInitCap && (size_t)J * P.cap == (size_t)P.C;
         launch_nms(na, J, P.max_nblk, mdim, P.max_cells, st, P.max_nitems, cand_fused ? &ca : nullptr, mpx);
@@ -3690,6 +3678,156 @@ int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int
         std::copy(hr[i].vec, hr[i].vec + 9, r.vec);
     }
     *pixels_written = want_px ? 1 : 0;
+    return FPM_OK;
+}
+
+// The top-layer peak pass on caller-supplied maps, by the search's own launchers: form 0 as enqueue_search's split branch
+// (fused_lds == 0 && !use_mma), form 1 as its use_mma branch with the lists k_top_mma would have written built on the host.
+int fpm_op_peaks(fpm_ctx* ctx, const float* const* maps, const int32_t* mw, const int32_t* mh, int32_t n_maps,
+                 int32_t tw, int32_t th, int32_t cap, int32_t by_block, int32_t mfc, double thr, double overlap,
+                 int32_t form, int32_t list_cap, uint32_t list_seed, fpm_peak* peaks, int32_t* counts,
+                 int32_t* stats) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (!maps || !mw || !mh || !peaks || !counts || n_maps < 1 || n_maps > 65535 || tw < 1 || th < 1 || tw >= 65536 ||
+        th >= 65536 || cap < 1 || (int64_t)n_maps * cap > FPM_PEAKS_MAX_SLOTS || (form != 0 && form != 1) ||
+        list_cap < 0 || !std::isfinite(thr) || !(std::fabs(overlap) <= 16.0)) {
+        ctx->err = "bad peaks arguments";
+        return FPM_E_INVALID_ARG;
+    }
+    by_block = by_block ? 1 : 0;
+    mfc = (mfc && by_block) ? 1 : 0;
+    const int n = n_maps;
+    NmsMaxima mx;
+    std::vector<size_t> map_off(n), blk_off(n);
+    size_t mo = 0, bo = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!maps[i] || mw[i] < 1 || mh[i] < 1 || mw[i] >= 65536 || mh[i] >= 65536) {
+            ctx->err = "bad map";
+            return FPM_E_INVALID_ARG;
+        }
+        map_off[i] = mo;
+        mo += round_up((size_t)mw[i] * mh[i], (size_t)64);
+        if (mo > (size_t)FPM_PEAKS_MAX_PIXELS) { ctx->err = "maps too large"; return FPM_E_INVALID_ARG; }
+        const int nb = nms_maxima_add(mx, mw[i], mh[i], tw, th, by_block, mfc);   // as build_plan
+        blk_off[i] = bo;
+        bo += round_up((size_t)nb, (size_t)64);
+    }
+    // form 1: what plan_top_mma admits to the list path (the greedy forms need thr > 0 and hold 256 peaks)
+    if (form == 1 && (!(thr > 0.01) || !(overlap >= 0.0) || cap > 256 || mx.max_cells > 12 * 1024)) {
+        ctx->err = "peaks: the list form needs thr > 0.01, overlap >= 0, cap <= 256 and at most 12288 cells per map";
+        return FPM_E_INVALID_ARG;
+    }
+    const int def_cap = by_block ? kNmsCandCap : 512;   // plan_top_mma's tcand_cap
+    const int lcap = form == 1 ? (list_cap > 0 ? std::min(list_cap, def_cap) : def_cap) : (by_block ? kNmsCandCap : 0);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // scratch: the maps in d_op_a; jobs, block maxima, peaks, counts, list counts, strip keys and lists in d_op_b
+    const size_t o_jobs = 0, o_bmax = round_up(sizeof(NmsJob) * n, (size_t)256),
+                 o_bloc = o_bmax + round_up(sizeof(float) * std::max<size_t>(bo, 1), (size_t)256),
+                 o_peaks = o_bloc + round_up(sizeof(int32_t) * std::max<size_t>(bo, 1), (size_t)256),
+                 o_counts = o_peaks + round_up(sizeof(Peak) * (size_t)n * cap, (size_t)256),
+                 o_zero = o_counts + round_up(sizeof(int32_t) * n, (size_t)256),   // [n] list counts, [n][3] u64, [n][3]
+                 o_skey = o_zero + round_up(sizeof(int32_t) * n, (size_t)8), o_sdone = o_skey + sizeof(uint64_t) * 3 * n,
+                 o_cand = round_up(o_sdone + sizeof(int32_t) * 3 * n, (size_t)256),
+                 o_cval = o_cand + round_up(sizeof(int32_t) * (size_t)lcap * n, (size_t)256),
+                 o_end = o_cval + (form == 1 ? round_up(sizeof(float) * (size_t)lcap * n, (size_t)256) : 0);
+    HIP_TRY(ctx->d_op_a.ensure(sizeof(float) * mo));
+    HIP_TRY(ctx->d_op_b.ensure(o_end));
+    std::vector<NmsJob> jobs(n);
+    std::vector<int32_t> k_true(n, 0);
+    for (int i = 0; i < n; ++i) {
+        NmsJob& j = jobs[i];
+        j.map = ctx->d_op_a.as<float>() + map_off[i];
+        j.bmax = ctx->d_op_b.as<float>(o_bmax) + blk_off[i];
+        j.bloc = ctx->d_op_b.as<int32_t>(o_bloc) + blk_off[i];
+        j.mw = mw[i]; j.mh = mh[i];
+        const size_t px = (size_t)mw[i] * mh[i];
+        HIP_TRY(hipMemcpyAsync(j.map, maps[i], sizeof(float) * px, hipMemcpyHostToDevice, st));
+        for (size_t k = 0; k < px; ++k) k_true[i] += (double)maps[i][k] >= thr ? 1 : 0;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_jobs), jobs.data(), sizeof(NmsJob) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_op_b.as<char>(o_peaks), 0, sizeof(Peak) * (size_t)n * cap, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_op_b.as<char>(o_counts), 0xff, sizeof(int32_t) * n, st));   // -1: no kernel took the job
+    HIP_TRY(hipMemsetAsync(ctx->d_op_b.as<char>(o_zero), 0, o_cand - o_zero, st));   // as k_warp / the pyramid launch zero them
+    NmsArgs na{};
+    na.jobs = ctx->d_op_b.as<NmsJob>(o_jobs);
+    na.peaks = ctx->d_op_b.as<Peak>(o_peaks);
+    na.counts = ctx->d_op_b.as<int32_t>(o_counts);
+    na.tw = tw; na.th = th; na.cap = cap; na.by_block = by_block; na.mfc = mfc;
+    na.thr = thr; na.overlap = overlap;
+    int32_t* d_ccnt = ctx->d_op_b.as<int32_t>(o_zero);
+    NmsLaunchInfo gi{}, ni{};
+    std::vector<int32_t> hl;
+    std::vector<float> hv;
+    if (form == 0) {
+        if (by_block) {
+            na.cand = ctx->d_op_b.as<int32_t>(o_cand); na.cand_cnt = d_ccnt; na.cand_cap = kNmsCandCap;
+            na.skey = ctx->d_op_b.as<uint64_t>(o_skey);
+            na.sdone = ctx->d_op_b.as<int32_t>(o_sdone);
+        }
+        launch_nms(na, n, mx.max_blocks, mx.max_map_dim, mx.max_cells, st, mx.max_items, nullptr, mx.max_map_px, &ni);
+    } else {
+        // k_top_mma's lists: every pixel >= thr once, in no particular order (here: shuffled), the first lcap stored
+        hl.assign((size_t)lcap * n, 0);
+        hv.assign((size_t)lcap * n, 0.f);
+        std::mt19937 rng(list_seed);
+        std::vector<int32_t> idx;
+        for (int i = 0; i < n; ++i) {
+            idx.clear();
+            const int32_t px = mw[i] * mh[i];
+            for (int32_t k = 0; k < px; ++k)
+                if ((double)maps[i][k] >= thr) idx.push_back(k);
+            for (size_t k = idx.size(); k > 1; --k) std::swap(idx[k - 1], idx[rng() % k]);
+            for (size_t k = 0; k < idx.size() && k < (size_t)lcap; ++k) {
+                hl[(size_t)i * lcap + k] = idx[k];
+                hv[(size_t)i * lcap + k] = maps[i][idx[k]];
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_cand), hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice,
+                               st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_cval), hv.data(), sizeof(float) * hv.size(), hipMemcpyHostToDevice,
+                               st));
+        HIP_TRY(hipMemcpyAsync(d_ccnt, k_true.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        NmsArgs ga = na;
+        ga.cand = ctx->d_op_b.as<int32_t>(o_cand); ga.cand_val = ctx->d_op_b.as<float>(o_cval);
+        ga.cand_cnt = d_ccnt; ga.cand_cap = lcap;
+        ga.reset_untaken = by_block;
+        launch_top_greedy(ga, n, mx.max_cells, st, nullptr, &gi);
+        NmsArgs fa = na;
+        fa.cand = ga.cand; fa.cand_cnt = ga.cand_cnt; fa.cand_cap = lcap;
+        if (by_block) {
+            fa.skey = ctx->d_op_b.as<uint64_t>(o_skey);
+            fa.sdone = ctx->d_op_b.as<int32_t>(o_sdone);
+        }
+        launch_nms(fa, n, mx.max_blocks, mx.max_map_dim, mx.max_cells, st, mx.max_items, nullptr, mx.max_map_px, &ni);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<Peak> hp((size_t)n * cap);
+    std::vector<int32_t> hc(n), hk(n, 0);
+    HIP_TRY(hipMemcpyAsync(hp.data(), ctx->d_op_b.as<char>(o_peaks), sizeof(Peak) * hp.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hc.data(), ctx->d_op_b.as<char>(o_counts), sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (form == 1 || by_block) HIP_TRY(hipMemcpyAsync(hk.data(), d_ccnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) {
+        counts[i] = hc[i];
+        for (int k = 0; k < hc[i] && k < cap; ++k) {
+            fpm_peak& p = peaks[(size_t)i * cap + k];
+            const Peak& q = hp[(size_t)i * cap + k];
+            p.x = q.x; p.y = q.y; p.score = q.score;
+        }
+    }
+    if (stats) {
+        stats[0] = (int32_t)(gi.kernels | ni.kernels);
+        stats[1] = ni.lds_blocks; stats[2] = ni.cand_lds;
+        stats[3] = form == 1 ? gi.greedy_cap : ni.greedy_cap;
+        stats[4] = ni.blk_lds; stats[5] = lcap; stats[6] = mx.max_blocks; stats[7] = mx.max_cells;
+        for (int i = 0; i < n; ++i) {
+            int32_t* s = stats + FPM_PEAKS_STATS_CALL + FPM_PEAKS_STATS_JOB * i;
+            s[0] = k_true[i]; s[1] = hk[i]; s[2] = hk[i] < 0 ? 1 : 0;
+            s[3] = by_block ? -1 : nms_plain_form(ni.blk_lds, cap, (long)mw[i] * mh[i]);
+        }
+    }
     return FPM_OK;
 }
 

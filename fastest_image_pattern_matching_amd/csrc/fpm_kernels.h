@@ -326,10 +326,30 @@ constexpr int kNmsCandCap = 8192;   // s_BlockMax candidates (pixels >= the top-
 // ci (plain getNextMaxLoc path only, cap <= kNmsInitCap): k_nms also does k_cand_init's work for its job's
 // candidate slots (one launch fewer); the live counter must have been zeroed by an earlier launch
 constexpr int kNmsInitCap = 128;
+// what a peak launcher decided (fpm_op_peaks reports it; the search passes null)
+enum { kNmsRanBlocks = 1, kNmsRanNms = 2, kNmsRanFast = 4, kNmsRanGreedy = 8 };
+struct NmsLaunchInfo {
+    uint32_t kernels;        // kNmsRan* of the kernels launched
+    int32_t lds_blocks;      // NmsArgs::lds_blocks of the k_nms_fast / k_nms launch
+    int32_t cand_lds;        // NmsArgs::cand_lds of the k_nms_fast launch
+    int32_t greedy_cap;      // k_nms_greedy's sort capacity (0: not launched)
+    int32_t blk_lds;         // k_nms carried the LDS of its plain path's block maxima
+};
 // max_map_px: the largest map's pixel count (sizes k_nms's dynamic LDS; -1 = unknown)
 void launch_nms(const NmsArgs& a, int njobs, int max_blocks, int max_map_dim, int max_cells, hipStream_t st,
-                int max_items = 0, const CandInitArgs* ci = nullptr, long max_map_px = -1);
+                int max_items = 0, const CandInitArgs* ci = nullptr, long max_map_px = -1,
+                NmsLaunchInfo* info = nullptr);
 int nms_block_items(int mw, int mh, int tw, int th, int mfc);
+// the launch maxima of launch_nms / launch_top_greedy over a set of top-layer maps (0 x 0: a map that does not exist)
+struct NmsMaxima {
+    int max_blocks = 0, max_map_dim = 0, max_cells = 0, max_items = 0;
+    long max_map_px = 0;
+};
+// adds one map; returns its s_BlockMax block count (0 in plain mode)
+int nms_maxima_add(NmsMaxima& m, int mw, int mh, int tw, int th, int by_block, int mfc);
+// k_nms's plain path on a map of n pixels: 0 = full-map scans (little work), 1 = 64-pixel block maxima in LDS,
+// 2 = full-map scans (more blocks than the LDS holds); blk_lds as NmsLaunchInfo
+int nms_plain_form(int blk_lds, int cap, long n);
 void launch_cand_init(const CandInitArgs& a, hipStream_t st);
 // K2-K5 fused for small canvases (plain peak path): LDS bytes of one (source, angle) job, and the launch (one
 // workgroup per job; zero / nzero as launch_warp)
@@ -378,8 +398,10 @@ void top_mma_layout(TopMmaArgs& a, int sw, int max_rows);
 bool top_mma_fits(int tw, int th);   // template shapes the kernel takes (R = 2 up to 17 wide, R = 1 up to 49)
 void launch_top_mma(const TopMmaArgs& a, hipStream_t st);
 // k_nms_greedy over k_top_mma's lists (a.cand_val set): plain getNextMaxLoc key (by_block 0) or s_BlockMax key; with ci
-// (plain, cap <= kNmsInitCap) the candidate init of the jobs it takes
-void launch_top_greedy(const NmsArgs& a, int njobs, int max_cells, hipStream_t st, const CandInitArgs* ci);
+// (plain, cap <= kNmsInitCap) the candidate init of the jobs it takes.  Needs a.overlap >= 0, as every use of the greedy
+// form (its cell lists hold a rectangle of at most twice the template): plan_top_mma keeps other searches off this path
+void launch_top_greedy(const NmsArgs& a, int njobs, int max_cells, hipStream_t st, const CandInitArgs* ci,
+                       NmsLaunchInfo* info = nullptr);
 void launch_roi_tables(const RoiArgs& a, hipStream_t st);
 void launch_roi_warp(const RoiArgs& a, hipStream_t st);
 void launch_roi_corr(const RoiArgs& a, hipStream_t st);

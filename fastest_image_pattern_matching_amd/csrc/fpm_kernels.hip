@@ -1148,6 +1148,19 @@ int nms_block_items(int mw, int mh, int tw, int th, int mfc) {
     g.init(mw, mh, tw, th, mfc);
     return g.items(mw, mh);
 }
+int nms_maxima_add(NmsMaxima& m, int mw, int mh, int tw, int th, int by_block, int mfc) {
+    m.max_map_dim = std::max(m.max_map_dim, std::max(mw, mh));
+    m.max_map_px = std::max(m.max_map_px, (long)mw * mh);
+    if (mw <= 0 || mh <= 0) return 0;
+    // coverage cells of the greedy peak forms (k_nms_greedy), plain and s_BlockMax alike
+    m.max_cells = std::max(m.max_cells, ((mw + tw - 1) / tw) * ((mh + th - 1) / th));
+    if (!by_block) return 0;
+    BlockGeom g;
+    g.init(mw, mh, tw, th, mfc);
+    m.max_blocks = std::max(m.max_blocks, g.nb);
+    m.max_items = std::max(m.max_items, g.items(mw, mh));
+    return g.nb;
+}
 
 // wave argmax (value, key) with lowest-key tie-break, by DPP steps (no LDS round trip per step): quad swaps, row
 // half-mirror, row mirror, then row_bcast15 / row_bcast31 fold the rows into lane 63, read back to every lane
@@ -1374,6 +1387,11 @@ __device__ void cand_init_job(const CandInitArgs& c, int mode, int job, int cnt,
 constexpr int kNmsPlainBlk = 4096;   // plain path: 64-pixel block maxima kept in LDS (maps up to 256 K pixels)
 constexpr long kNmsBlkMinWork = 1 << 16;   // ... used when peak slots x map pixels reach this
 constexpr size_t kNmsPlainBlkLds = (size_t)8 * kNmsPlainBlk;   // dynamic LDS of k_nms's block maxima
+// k_nms's choice for a plain map of n pixels, restated for the host (its `chunked` below: keep the two in step)
+int nms_plain_form(int blk_lds, int cap, long n) {
+    const bool work = (long)cap * n >= kNmsBlkMinWork, fits = ((n + 63) >> 6) <= kNmsPlainBlk;
+    return blk_lds && fits && work ? 1 : (work && !fits ? 2 : 0);
+}
 // ci_mode 0: peaks only; 1-3: also the job's candidate slots (cand_init_job; plain path, cap <= kNmsInitCap).
 // blk_lds: the launch carries kNmsPlainBlkLds of dynamic LDS for the plain path's block maxima (launch_nms gives it
 // only where some job can take that path, so the other launches keep their occupancy)
@@ -1984,35 +2002,46 @@ constexpr int kNmsLdsBlocksMax = 12 * 1024;   // block maxima kept in LDS up to 
 constexpr int kNmsLdsBytes = 160 * 1024 - 4096;   // k_nms_fast dynamic LDS budget (statics take the rest)
 
 void launch_nms(const NmsArgs& a0, int njobs, int max_blocks, int max_map_dim, int max_cells, hipStream_t st,
-                int max_items, const CandInitArgs* ci, long max_map_px) {
+                int max_items, const CandInitArgs* ci, long max_map_px, NmsLaunchInfo* info) {
     if (njobs <= 0) return;
     NmsArgs a = a0;
     CandInitArgs cz{};
+    NmsLaunchInfo li{};
+    struct Report {   // the decisions below, handed out on every return
+        NmsLaunchInfo* out; const NmsLaunchInfo& li;
+        ~Report() { if (out) *out = li; }
+    } report{info, li};
     // k_nms's block maxima (its plain path on maps where peak slots x pixels >= kNmsBlkMinWork): LDS only if some map
     // can take that path (max_map_px < 0: unknown, always)
     const int blk = max_map_px < 0 || (long)a.cap * max_map_px >= kNmsBlkMinWork;
     const size_t blds = blk ? kNmsPlainBlkLds : 0;
+    li.blk_lds = blk;
     if (!a.by_block && ci && a.cap <= kNmsInitCap) {   // plain path with the candidate init fused
         hipLaunchKernelGGL(k_nms, dim3(njobs), dim3(256), blds, st, a, *ci,
                            ci->refine == 0 ? 1 : (ci->refine == 2 ? 3 : 2), blk);
+        li.kernels |= kNmsRanNms;
         return;
     }
     if (a.by_block && max_blocks > 0) {
         const int items = max_items > max_blocks ? max_items : max_blocks;
         hipLaunchKernelGGL(k_nms_blocks, dim3((items + 3) / 4 < 16384 ? (items + 3) / 4 : 16384, njobs),
                            dim3(256), 0, st, a);
-        // the greedy form takes what it can (thr > 0: an empty strip's stale 0 is never a peak); k_nms the rest
-        const bool greedy = a.cand && !a.stamps && a.thr > 0.0 && max_map_dim < 65536 && a.cap <= 256 &&
-                            nms_greedy_lds(max_cells) <= (size_t)kNmsLdsBytes;
+        li.kernels |= kNmsRanBlocks;
+        // the greedy form takes what it can (thr > 0: an empty strip's stale 0 is never a peak; overlap >= 0: a painted
+        // rectangle of at most twice the template, which is what its 3 x 3 cell lists hold); k_nms the rest
+        const bool greedy = a.cand && !a.stamps && a.thr > 0.0 && a.overlap >= 0.0 && max_map_dim < 65536 &&
+                            a.cap <= 256 && nms_greedy_lds(max_cells) <= (size_t)kNmsLdsBytes;
         if (greedy) ensure_lds_attr((const void*)k_nms_greedy, kNmsLdsBytes);
         if (a.mfc) {   // MFC block semantics: greedy form + k_nms (k_nms_fast is Qt-only)
             if (greedy) {
                 NmsArgs gA = a;
                 gA.lds_blocks = max_cells;
                 hipLaunchKernelGGL(k_nms_greedy, dim3(njobs), dim3(256), nms_greedy_lds(max_cells), st, gA, cz, 0);
+                li.kernels |= kNmsRanGreedy; li.greedy_cap = kGreedyMax;
             }
             a.lds_blocks = 0;
             hipLaunchKernelGGL(k_nms, dim3(njobs), dim3(256), blds, st, a, cz, 0, blk);
+            li.kernels |= kNmsRanNms;
             return;
         }
         const size_t fixed = nms_fast_lds(max_blocks, a.cap, 0);
@@ -2027,13 +2056,17 @@ void launch_nms(const NmsArgs& a0, int njobs, int max_blocks, int max_map_dim, i
                 NmsArgs gA = a;
                 gA.lds_blocks = max_cells;
                 hipLaunchKernelGGL(k_nms_greedy, dim3(njobs), dim3(256), nms_greedy_lds(max_cells), st, gA, cz, 0);
+                li.kernels |= kNmsRanGreedy; li.greedy_cap = kGreedyMax;
             }
             hipLaunchKernelGGL(k_nms_fast, dim3(njobs), dim3(256), lds, st, a);
+            li.kernels |= kNmsRanFast;
+            li.lds_blocks = a.lds_blocks; li.cand_lds = a.cand_lds;
             return;
         }
     }
     a.lds_blocks = 0;
     hipLaunchKernelGGL(k_nms, dim3(njobs), dim3(256), blds, st, a, cz, 0, blk);
+    li.kernels |= kNmsRanNms;
 }
 
 // ============================================================================================== init
@@ -5713,7 +5746,8 @@ void launch_top_mma(const TopMmaArgs& a, hipStream_t st) {
     else launch_top_form<16, 64, TM_CP1>(a, grid, lds, st);
 }
 
-void launch_top_greedy(const NmsArgs& a0, int njobs, int max_cells, hipStream_t st, const CandInitArgs* ci) {
+void launch_top_greedy(const NmsArgs& a0, int njobs, int max_cells, hipStream_t st, const CandInitArgs* ci,
+                       NmsLaunchInfo* info) {
     if (njobs <= 0) return;
     NmsArgs a = a0;
     a.lds_blocks = max_cells;
@@ -5728,6 +5762,7 @@ void launch_top_greedy(const NmsArgs& a0, int njobs, int max_cells, hipStream_t 
     const size_t lds = nms_greedy_lds(max_cells, gc);
     ensure_lds_attr((const void*)k_nms_greedy, lds);
     hipLaunchKernelGGL(k_nms_greedy, dim3(njobs), dim3(256), lds, st, a, fuse ? *ci : cz, mode);
+    if (info) { info->kernels |= kNmsRanGreedy; info->greedy_cap = gc; }
 }
 
 // ============================================================================================== pack

@@ -62,6 +62,10 @@ assert CANDIDATE_DTYPE.itemsize == C.sizeof(L.Candidate)
 ROI_RECORD_DTYPE = np.dtype([("score", "<f4"), ("mx", "<i4"), ("my", "<i4"), ("on_border", "<i4"), ("vec", "<f4", 9)])
 assert ROI_RECORD_DTYPE.itemsize == C.sizeof(L.RoiRecord)
 
+# fpm_peak as a numpy record (include/fpm.h), 12 bytes
+PEAK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("score", "<f4")])
+assert PEAK_DTYPE.itemsize == C.sizeof(L.Peak)
+
 
 def merge_candidates(params: "L.Params", tmpl_w: int, tmpl_h: int, cands: np.ndarray) -> List[SingleTargetMatch]:
     """fpm_merge_candidates: the coupled tail of TemplateMatcher::match (TemplateMatcher.cpp:214, 262-432) over one
@@ -1191,6 +1195,40 @@ class TemplateMatcher:
         if rc != L.FPM_OK:
             raise ValueError(f"fpm_op_refine failed with {rc}: {self.last_error()}")
         return rec, (px if wrote.value else None)
+
+    def peaks(self, maps, tw: int, th: int, cap: int, by_block: bool, mfc: bool, thr: float, overlap: float,
+              form: int = 0, list_cap: int = 0, list_seed: int = 0):
+        """fpm_op_peaks: the search's top-layer peak pass on caller-supplied f32 score maps (finite values), one job
+        each; needs no learned template.  form 0: the split kernels, 1: the candidate-list path.  Returns (peaks: one
+        PEAK_DTYPE array per map, stats: dict of the call-level entries, 'counts' and 'jobs', an (n, 4) int array, as
+        include/fpm.h lists them)."""
+        ms = [np.ascontiguousarray(m, np.float32) for m in maps]
+        if any(m.ndim != 2 for m in ms):
+            raise ValueError("maps must be 2-D")
+        n = len(ms)
+        mw = np.array([m.shape[1] for m in ms], np.int32)
+        mh = np.array([m.shape[0] for m in ms], np.int32)
+        cap = int(cap)
+        pk = np.zeros((max(n, 1), max(cap, 1)), PEAK_DTYPE)
+        cnt = np.full(max(n, 1), -7, np.int32)
+        st = np.zeros(L.PEAKS_STATS_CALL + L.PEAKS_STATS_JOB * max(n, 1), np.int32)
+        FP = C.POINTER(C.c_float)
+        ptrs = (FP * max(n, 1))(*[m.ctypes.data_as(FP) for m in ms])
+        IP = C.POINTER(C.c_int32)
+        rc = self._lib.fpm_op_peaks(self._ctx, ptrs, mw.ctypes.data_as(IP), mh.ctypes.data_as(IP), n, int(tw), int(th),
+                                    cap, 1 if by_block else 0, 1 if mfc else 0, float(thr), float(overlap), int(form),
+                                    int(list_cap), int(list_seed) & 0xffffffff, pk.ctypes.data_as(C.POINTER(L.Peak)),
+                                    cnt.ctypes.data_as(IP), st.ctypes.data_as(IP))
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_op_peaks failed with {rc}: {self.last_error()}")
+        bad = np.flatnonzero((cnt[:n] < 0) | (cnt[:n] > cap))   # (the operator pre-fills the device counts with -1)
+        if len(bad):
+            raise RuntimeError(f"fpm_op_peaks: no kernel wrote a valid count for jobs {bad.tolist()}")
+        out = [pk[i, :int(cnt[i])].copy() for i in range(n)]
+        stats = dict(kernels=int(st[0]), lds_blocks=int(st[1]), cand_lds=int(st[2]), greedy_cap=int(st[3]),
+                     blk_lds=int(st[4]), list_cap=int(st[5]), max_blocks=int(st[6]), max_cells=int(st[7]),
+                     counts=cnt[:n].copy(), jobs=st[L.PEAKS_STATS_CALL:].reshape(-1, L.PEAKS_STATS_JOB)[:n].copy())
+        return out, stats
 
     def overlap_filter(self, corners, scores, max_overlap: float, device: bool = True):
         """filterWithRotatedRect (TemplateMatcher.cpp:1133-1194) on rectangles given as rows (ltx, lty, rtx, rty, rbx,

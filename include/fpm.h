@@ -534,6 +534,41 @@ typedef struct fpm_roi_record {
 int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int32_t w, int32_t h, size_t stride,
                   int32_t layer, const float* lt, const double* angles, int32_t n, int32_t n3, int32_t fold,
                   int32_t round_rois, fpm_roi_record* rec, uint8_t* roi_pixels, int32_t* pixels_written);
+/* The search's top-layer peak pass (getNextMaxLoc, TemplateMatcher.cpp:1196-1221, and s_BlockMax, DataStructures.h:
+ * 150-246 / MatchToolDlg.h:93-210) on score maps the caller supplies, through the search's own launchers and form
+ * selection (launch_nms: k_nms_blocks, k_nms_greedy, k_nms_fast, k_nms; launch_top_greedy).  No learned template is
+ * needed; the plan, the staged sources, the last results, the model and the profile counters stay as they were.
+ * Additive entry: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_peak {
+    int32_t x, y;         /* ptMaxLoc                                                                        */
+    float score;          /* dMaxValue                                                                       */
+} fpm_peak;
+#define FPM_PEAKS_MAX_PIXELS (1 << 26)   /* total pixels of one call's maps */
+#define FPM_PEAKS_MAX_SLOTS (1 << 24)    /* n_maps * cap */
+#define FPM_PEAKS_STATS_CALL 8           /* call-level stats entries; then FPM_PEAKS_STATS_JOB per map */
+#define FPM_PEAKS_STATS_JOB 4
+/* maps: n_maps dense f32 maps of mw[i] x mh[i] (1 .. 65535 each way; n_maps <= 65535), one job each, copied to device
+ * memory unchanged.  Contract: the maps hold finite values (no NaN, no infinities), as the NCC maps of a search do.
+ * tw, th (1 .. 65535), cap (= max_pos + MATCH_CANDIDATE_NUM), by_block, mfc, thr (= vecLayerScore[top]) and overlap
+ * (finite, |overlap| <= 16; negative values enlarge the painted rectangle) are the NmsArgs fields of a search.  form 0: the split path (one launch_nms; in block mode with
+ * k_nms_blocks' candidate lists and strip scratch).  form 1: the list path of the matrix-core top layer: the op lists
+ * each map's pixels with (double)v >= thr and their values, in an order shuffled by list_seed, keeps the first list_cap
+ * of them (0 = the engine's capacity: 8192 in block mode, 512 plain; larger values are clamped to it) with the true
+ * count, runs launch_top_greedy and then the fallback launch_nms on the maps.  form 1 takes what the search's plan
+ * admits to that path: thr > 0.01, overlap >= 0, cap <= 256, at most 12288 coverage cells per map.
+ * peaks: [n_maps][cap], the first counts[i] of map i written.  stats (may be NULL): FPM_PEAKS_STATS_CALL +
+ * FPM_PEAKS_STATS_JOB * n_maps entries: [0] kernels launched (1 k_nms_blocks, 2 k_nms, 4 k_nms_fast, 8 k_nms_greedy),
+ * [1] lds_blocks and [2] cand_lds of the k_nms_fast launch, [3] k_nms_greedy's sort capacity (0: not launched), [4]
+ * k_nms carried the LDS of its plain path's block maxima, [5] the list capacity in effect, [6] max_blocks, [7]
+ * max_cells; per map [0] pixels with (double)v >= thr (the list's true count), [1] the map's list count read back after
+ * the launches (-1: taken by k_nms_greedy; else k_nms_blocks' count in block mode), [2] taken by k_nms_greedy, [3]
+ * k_nms's plain form for the map, computed on the host from the kernel's rule (-1 block mode, 0 full scans on little work, 1 block maxima, 2 full scans on a map
+ * beyond the block maxima's LDS).  An argument outside these ranges returns FPM_E_INVALID_ARG with nothing launched
+ * and nothing written. */
+int fpm_op_peaks(fpm_ctx* ctx, const float* const* maps, const int32_t* mw, const int32_t* mh, int32_t n_maps,
+                 int32_t tw, int32_t th, int32_t cap, int32_t by_block, int32_t mfc, double thr, double overlap,
+                 int32_t form, int32_t list_cap, uint32_t list_seed, fpm_peak* peaks, int32_t* counts,
+                 int32_t* stats);
 /* Learned-template introspection: number of pyramid levels, per-level size and statistics
  * (s_TemplData, DataStructures.h:16-55). */
 int fpm_template_info(const fpm_ctx* ctx, int32_t* levels, int32_t* border_color);

@@ -64,6 +64,8 @@ def load(path: str = ORACLE_LIB):
                                        C.POINTER(C.c_float)]
     lib.orc_filter_rotated_rect.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int, C.c_double,
                                             C.POINTER(C.c_int32)]
+    lib.orc_peak_sequence.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_double, C.c_int, C.c_double, C.POINTER(C.c_double)]
     lib.fpm_params_default.argtypes = [C.POINTER(Params)]
     _libs[path] = lib
     return lib
@@ -136,6 +138,17 @@ def cross_corr_f32(img: np.ndarray, templ: np.ndarray) -> np.ndarray:
                                    out.ctypes.data_as(C.POINTER(C.c_float)))
     assert rc == 0
     return out
+
+
+def peak_sequence(m, tw, th, by_block, mfc, overlap, iters, thr):
+    """The top-layer peak extraction on an f32 map: the first peak and up to `iters` getNextMaxLoc calls, as
+    (value, x, y) -- Qt s_BlockMax (by_block, not mfc), MFC s_BlockMax (by_block, mfc) or the plain loop."""
+    lib = load()
+    m = np.ascontiguousarray(m, np.float32)
+    out = np.zeros((iters + 1) * 3, np.float64)
+    n = lib.orc_peak_sequence(m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[1], m.shape[0], tw, th, int(by_block),
+                              int(mfc), overlap, iters, thr, out.ctypes.data_as(C.POINTER(C.c_double)))
+    return [(float(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(n)]
 
 
 def filter_rotated_rect(corners, scores, max_overlap):

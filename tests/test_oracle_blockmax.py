@@ -12,7 +12,6 @@ OpenCV semantics used: minMaxLoc = first maximum in
 an empty array gives value 0 and location (-1, -1); Rect & Rect = the intersection or Rect() when empty;
 rectangle(FILLED) fills the rect clipped to the image, nothing when w <= 0 or h <= 0.
 """
-import ctypes as C
 import itertools
 
 import numpy as np
@@ -168,15 +167,7 @@ def reference_sequence(m, tw, th, by_block, mfc, overlap, iters, thr):
     return out
 
 
-def oracle_sequence(m, tw, th, by_block, mfc, overlap, iters, thr):
-    lib = oracle.load()
-    lib.orc_peak_sequence.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_double, C.c_int, C.c_double, C.POINTER(C.c_double)]
-    m = np.ascontiguousarray(m, np.float32)
-    out = np.zeros((iters + 1) * 3, np.float64)
-    n = lib.orc_peak_sequence(m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[1], m.shape[0], tw, th, int(by_block),
-                              int(mfc), overlap, iters, thr, out.ctypes.data_as(C.POINTER(C.c_double)))
-    return [(float(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(n)]
+oracle_sequence = oracle.peak_sequence   # (moved to tests/oracle.py; the old name stays importable)
 
 
 def _map(w, h, seed, levels):

@@ -56,6 +56,12 @@ KERNEL_SYMBOLS = {"pyr_down": ["k_pyr_down_s", "k_pyr_down"], "top_warp": ["k_wa
 MODEL_TRAIN, MODEL_PREPARE, MODEL_INSPECT = 0, 1, 2
 MODEL_KERNEL_SYMBOLS = ["k_model_accum", "k_model_prepare", "k_model_inspect"]
 MODEL_MAX_SAMPLES = 65535
+# fpm_align_*: the call flag of fpm_align_last beside COMPARE_NORMALIZE, the result flags, the rectangle's caps; the kernel
+# has no FPM_K_* index (fpm_align_profile)
+ALIGN_ADOPT = 2
+ALIGN_SINGULAR, ALIGN_STEP_CLAMPED, ALIGN_KEPT_START = 1, 2, 4
+ALIGN_MAX_AREA, ALIGN_MAX_SIDE, ALIGN_MAX_ITERS, ALIGN_MAX_STEP = 1 << 20, 4096, 8, 1024.0
+ALIGN_KERNEL_SYMBOL = "k_patch_align"
 
 
 class Params(C.Structure):
@@ -117,6 +123,21 @@ class InspectStats(C.Structure):
                 ("n_low", C.c_int32), ("n_high", C.c_int32), ("max_excess", C.c_int32), ("x0", C.c_int32),
                 ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
                 ("gain", C.c_double), ("offset", C.c_double)]
+
+
+class AlignSums(C.Structure):
+    """fpm_align_sums -- the exact sums of one Gauss-Newton step of a hit's pose (fpm_align_sums_at)."""
+
+    _fields_ = [(n, C.c_int64) for n in ("n_used", "h_xx", "h_xy", "h_yy", "h_xt", "h_yt", "h_tt", "g_x", "g_y", "g_t",
+                                         "ssd")]
+
+
+class AlignResult(C.Structure):
+    """fpm_align_result -- one hit's aligned pose (fpm_align_at / fpm_align_last)."""
+
+    _fields_ = [("lt_x", C.c_float), ("lt_y", C.c_float), ("angle", C.c_double), ("ssd_start", C.c_int64),
+                ("ssd", C.c_int64), ("n_used", C.c_int64), ("evals", C.c_int32), ("best_eval", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RoiRecord(C.Structure):
@@ -226,6 +247,18 @@ SIGNATURES = {
     "fpm_model_derive": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3),
     "fpm_model_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64)]),
+    "fpm_align_sums_at": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(AlignSums)]),
+    "fpm_align_at": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                               C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                               C.POINTER(AlignResult)]),
+    "fpm_align_last": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                 C.POINTER(AlignResult), C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_align_solve": (C.c_int, [C.POINTER(AlignSums)] + [C.POINTER(C.c_double)] * 3),
+    "fpm_align_update": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PatchRect), C.c_float, C.c_float, C.c_double,
+                                   C.c_double, C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_double)]),
+    "fpm_align_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

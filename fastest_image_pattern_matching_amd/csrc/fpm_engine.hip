@@ -151,9 +151,9 @@ struct KProf {
     double ms = 0;
     int64_t launches = 0, bytes = 0;
 };
-// Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile), which
-// have no FPM_K_* index: FPM_K_COUNT stays what it is.
-enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfSlots };
+// Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
+// alignment's one (fpm_align_profile), which have no FPM_K_* index: FPM_K_COUNT stays what it is.
+enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfSlots };
 
 }  // namespace
 
@@ -237,6 +237,8 @@ struct fpm_ctx {
     uint64_t band_gen = ~0ull;
     DevBuf d_insacc;          // the inspection's per-hit records and their host copy
     PinBuf h_insacc;
+    DevBuf d_alnacc;          // the alignment's per-hit records (fpm_align_*) and their host copy
+    PinBuf h_alnacc;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -2523,6 +2525,178 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     return FPM_OK;
 }
 
+// ---- pose alignment (fpm_align_*) ----
+static_assert(sizeof(fpm_align_sums) == sizeof(AlignAcc), "the kernel's record is fpm_align_sums, field for field");
+static_assert(sizeof(fpm_align_result) == 56, "fpm_align_result has no padding");
+
+// A comparison rectangle under the alignment's narrower caps (include/fpm.h derives the sums' bound from them).
+int align_rect(fpm_ctx* ctx, const fpm_patch_rect* rect, fpm_patch_rect* r) {
+    const int rc = compare_rect(ctx, rect, r);
+    if (rc != FPM_OK) return rc;
+    if (r->w > kAlignMaxSide || r->h > kAlignMaxSide || (int64_t)r->w * r->h > kAlignMaxArea) {
+        ctx->err = "bad alignment rectangle: at most 2^20 pixels and sides of at most 4096";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// The step of one record (include/fpm.h states the expression order; -ffp-contract=off).  true = singular, step 0.
+bool align_solve(const fpm_align_sums& m, double* du, double* dv, double* dphi) {
+    *du = *dv = *dphi = 0.0;
+    if (m.n_used < 3) return true;
+    const double hxx = (double)m.h_xx, hxy = (double)m.h_xy, hyy = (double)m.h_yy, hxt = (double)m.h_xt,
+                 hyt = (double)m.h_yt, htt = (double)m.h_tt, gx = (double)m.g_x, gy = (double)m.g_y, gt = (double)m.g_t;
+    const double c00 = hyy * htt - hyt * hyt, c01 = hxt * hyt - hxy * htt, c02 = hxy * hyt - hxt * hyy;
+    const double c11 = hxx * htt - hxt * hxt, c12 = hxy * hxt - hxx * hyt, c22 = hxx * hyy - hxy * hxy;
+    const double det = (hxx * c00 + hxy * c01) + hxt * c02;
+    if (!(det > 0.0) || !std::isfinite(det)) return true;
+    const double q0 = -(((c00 * gx + c01 * gy) + c02 * gt) / det);
+    const double q1 = -(((c01 * gx + c11 * gy) + c12 * gt) / det);
+    const double q2 = -(((c02 * gx + c12 * gy) + c22 * gt) / det);
+    const double u = 2.0 * q0, v = 2.0 * q1, p = 4.0 * q2;
+    if (!std::isfinite(u) || !std::isfinite(v) || !std::isfinite(p)) return true;
+    *du = u; *dv = v; *dphi = p;
+    return false;
+}
+
+// The pose whose patch map is A o D (include/fpm.h), as a difference from the current pose: a zero step returns it.
+RawPose align_update(int sw, int sh, const fpm_patch_rect& r, const RawPose& p, double du, double dv, double dphi) {
+    double A[6];
+    patch_forward(sw, sh, p, r.x, r.y, A);
+    invert_affine(A);
+    const double kx = r.x + (r.w - 1) / 2.0, ky = r.y + (r.h - 1) / 2.0;
+    const double angle2 = p.angle + dphi * kR2D;
+    const double ra = p.angle * kD2R, rb = angle2 * kD2R;
+    const double dc = std::cos(ra) - std::cos(rb), ds = std::sin(ra) - std::sin(rb);
+    const double mx = (A[0] * du + A[1] * dv) + (dc * kx - ds * ky);
+    const double my = (A[3] * du + A[4] * dv) + (ds * kx + dc * ky);
+    return RawPose{(float)((double)p.x + mx), (float)((double)p.y + my), angle2};
+}
+
+// Would the step move a corner of the rectangle by more than max_step?  (Patch pixels are source pixels: scale 1.)
+bool align_step_too_far(const fpm_patch_rect& r, double du, double dv, double dphi, double max_step) {
+    const double c = std::cos(dphi), s = std::sin(dphi), hx = (r.w - 1) / 2.0, hy = (r.h - 1) / 2.0;
+    const double lim = max_step * max_step;
+    for (int k = 0; k < 4; ++k) {
+        const double ex = (k & 1) ? hx : -hx, ey = (k & 2) ? hy : -hy;
+        const double mx = ((c * ex - s * ey) - ex) + du, my = ((s * ex + c * ey) - ey) + dv;
+        if (mx * mx + my * my > lim) return true;
+    }
+    return false;
+}
+
+// The job table of the start poses and, with FPM_COMPARE_NORMALIZE, the hits' tables built there as fpm_last_compare
+// builds them (*luts stays null otherwise).  The tables lie behind the job table and survive its later restaging.
+int align_begin(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, bool norm, const uint8_t** luts) {
+    const int n = (int)poses.size();
+    *luts = nullptr;
+    int rc = stage_patch_jobs(ctx, r, poses, nullptr, 0, 0, nullptr, true, norm ? (size_t)256 * n : 0);
+    if (rc != FPM_OK || !norm) return rc;
+    CompareArgs c;
+    rc = model_norm_args(ctx, r, n, &c);
+    if (rc == FPM_OK) rc = compare_norm_tables(ctx, c, r, n, luts);
+    return rc;
+}
+
+// One evaluation: the job table of `poses` (restaged unless the caller has just staged it), the records cleared, one
+// launch of k_patch_align, the records to `out`.  Synchronises the stream.
+int align_launch(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, bool restage, bool norm,
+                 const uint8_t* luts, fpm_align_sums* out) {
+    const int n = (int)poses.size();
+    const size_t accb = sizeof(AlignAcc) * (size_t)n;
+    if (restage) {
+        const int rc = stage_patch_jobs(ctx, r, poses, nullptr, 0, 0, nullptr, true, norm ? (size_t)256 * n : 0);
+        if (rc != FPM_OK) return rc;
+    }
+    HIP_TRY(ctx->d_alnacc.ensure(accb));
+    HIP_TRY(ctx->h_alnacc.ensure(accb));
+    HIP_TRY(hipMemsetAsync(ctx->d_alnacc.p, 0, accb, ctx->stream));
+    const TmplLevel& t0 = ctx->tmpl[0];
+    AlignArgs c{};
+    c.p = patch_args(ctx, r, n, nullptr, 0, 0);
+    c.tmpl = ctx->d_tmpl.as<uint8_t>() + t0.off;
+    c.tp = t0.pitch;
+    c.tw = t0.w; c.th = t0.h;
+    c.rx = r.x; c.ry = r.y;
+    c.luts = luts;
+    c.acc = ctx->d_alnacc.as<AlignAcc>();
+    {
+        ProfScope ps(ctx, kProfAlign, 2 * (int64_t)n * r.w * r.h);   // source pixels read + template pixels read
+        if (!launch_patch_align(c, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_alnacc.p, ctx->d_alnacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    std::memcpy(out, ctx->h_alnacc.p, accb);   // two's complement: the u64 records are the int64 sums
+    return FPM_OK;
+}
+
+int align_sums_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int flags,
+                       fpm_align_sums* out) {
+    const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
+    const uint8_t* luts = nullptr;
+    const int rc = align_begin(ctx, r, poses, norm, &luts);
+    return rc != FPM_OK ? rc : align_launch(ctx, r, poses, false, norm, luts, out);
+}
+
+// The iteration from `start` (n >= 1): iters + 1 evaluations, the host's solve and update between them.  out and
+// aligned (the returned poses, may be null) are written only when the whole call succeeds.
+int align_iterate(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& start, int iters, double max_step,
+                  int flags, fpm_align_result* out, std::vector<PatchPose>* aligned) {
+    const int n = (int)start.size();
+    const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
+    const uint8_t* luts = nullptr;
+    int rc = align_begin(ctx, r, start, norm, &luts);
+    if (rc != FPM_OK) return rc;
+    std::vector<PatchPose> cur = start, best = start;
+    std::vector<fpm_align_sums> sums((size_t)n);
+    std::vector<fpm_align_result> res((size_t)n);
+    std::vector<char> frozen((size_t)n, 0), moved((size_t)n, 0);
+    for (int k = 0; k <= iters; ++k) {
+        rc = align_launch(ctx, r, cur, k > 0, norm, luts, sums.data());
+        if (rc != FPM_OK) return rc;
+        for (int i = 0; i < n; ++i) {
+            fpm_align_result& o = res[i];
+            const fpm_align_sums& s = sums[i];
+            if (k == 0) {
+                o = fpm_align_result{};
+                o.ssd_start = o.ssd = s.ssd;
+                o.n_used = s.n_used;
+                o.evals = 1;
+            } else if (moved[i]) {
+                o.evals = k + 1;
+                if (s.ssd < o.ssd) { o.ssd = s.ssd; o.n_used = s.n_used; o.best_eval = k; best[i] = cur[i]; }
+            }
+            moved[i] = 0;
+            if (k == iters || frozen[i]) continue;
+            double du, dv, dphi;
+            if (align_solve(s, &du, &dv, &dphi)) { frozen[i] = 1; o.flags |= FPM_ALIGN_SINGULAR; continue; }
+            bool far = align_step_too_far(r, du, dv, dphi, max_step);
+            PatchPose next = cur[i];
+            if (!far) {
+                // the samplers' range, by the check the next staging makes
+                next.pose = align_update(ctx->sw, ctx->sh, r, cur[i].pose, du, dv, dphi);
+                const std::string err = ctx->err;
+                double M[6];
+                far = patch_pose_matrix(ctx, r, next, i, nullptr, M) != FPM_OK;
+                ctx->err = err;
+            }
+            if (far) { frozen[i] = 1; o.flags |= FPM_ALIGN_STEP_CLAMPED; continue; }
+            cur[i] = next;
+            moved[i] = 1;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        fpm_align_result& o = res[i];
+        o.lt_x = best[i].pose.x; o.lt_y = best[i].pose.y; o.angle = best[i].pose.angle;
+        if (o.best_eval == 0) o.flags |= FPM_ALIGN_KEPT_START;
+        out[i] = o;
+    }
+    if (aligned) *aligned = best;
+    return FPM_OK;
+}
+
 // fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
 // the device learn's second half
 int learn_from_model(fpm_ctx* ctx) {
@@ -2610,6 +2784,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_cmpacc.release(); ctx->h_cmpacc.release();
     ctx->d_tacc.release(); ctx->h_tacc.release();
     ctx->d_model.release(); ctx->d_band.release(); ctx->d_insacc.release(); ctx->h_insacc.release();
+    ctx->d_alnacc.release(); ctx->h_alnacc.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -3231,6 +3406,94 @@ int fpm_model_learn(fpm_ctx* ctx) {
 int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
     if (!ctx || which < 0 || which > 2 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
     const KProf& p = ctx->kp[kProfModelTrain + which];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
+}
+
+// --- pose alignment --------------------------------------------------------------------
+int fpm_align_solve(const fpm_align_sums* sums, double* du, double* dv, double* dphi) {
+    if (!sums || !du || !dv || !dphi) return FPM_E_INVALID_ARG;
+    return align_solve(*sums, du, dv, dphi) ? 1 : 0;
+}
+
+int fpm_align_update(int32_t src_w, int32_t src_h, const fpm_patch_rect* rect, float lt_x, float lt_y, double angle,
+                     double du, double dv, double dphi, float* lt2_x, float* lt2_y, double* angle2) {
+    if (!rect || !lt2_x || !lt2_y || !angle2 || src_w <= 0 || src_h <= 0 || rect->w < 1 || rect->h < 1) return FPM_E_INVALID_ARG;
+    const RawPose q = align_update(src_w, src_h, *rect, RawPose{lt_x, lt_y, angle}, du, dv, dphi);
+    *lt2_x = q.x; *lt2_y = q.y; *angle2 = q.angle;
+    return FPM_OK;
+}
+
+static int align_args(fpm_ctx* ctx, int32_t iters, double max_step, int32_t flags, int32_t known) {
+    if (iters < 1 || iters > 8) { ctx->err = "iters must be 1 .. 8"; return FPM_E_INVALID_ARG; }
+    if (!(max_step > 0.0) || !(max_step <= 1024.0)) { ctx->err = "max_step must be above 0 and at most 1024 pixels"; return FPM_E_INVALID_ARG; }
+    if (flags & ~known) { ctx->err = "unknown alignment flags"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+int fpm_align_sums_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                      const double* angles, int32_t n_poses, int32_t flags, fpm_align_sums* out) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown alignment flags"; return FPM_E_INVALID_ARG; }
+    fpm_patch_rect r;
+    int rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!out) { ctx->err = "null sums buffer"; return FPM_E_INVALID_ARG; }
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return align_sums_to_host(ctx, r, poses, flags, out);
+}
+
+int fpm_align_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                 const double* angles, int32_t n_poses, int32_t iters, double max_step, int32_t flags,
+                 fpm_align_result* out) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = align_args(ctx, iters, max_step, flags, FPM_COMPARE_NORMALIZE);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!out) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return align_iterate(ctx, r, poses, iters, max_step, flags, out, nullptr);
+}
+
+int fpm_align_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t iters, double max_step,
+                   int32_t flags, fpm_align_result* out, int32_t cap, int32_t* n) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = align_args(ctx, iters, max_step, flags, FPM_COMPARE_NORMALIZE | FPM_ALIGN_ADOPT);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses, aligned;
+    rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);   // the narrower caps before the comparison's own
+    if (rc == FPM_OK) rc = last_patches_begin(ctx, &r, source, cap, n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    if (!out) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = align_iterate(ctx, r, poses, iters, max_step, flags & FPM_COMPARE_NORMALIZE, out, &aligned);
+    if (rc != FPM_OK || !(flags & FPM_ALIGN_ADOPT)) return rc;
+    // the aligned poses become the last poses, in last_poses' order; the results and candidates stay what they were
+    size_t i = 0;
+    for (int s = 0; s < (int)ctx->poses.size() && s < ctx->S; ++s)
+        if (source < 0 || s == source)
+            for (RawPose& p : ctx->poses[s]) p = aligned[i++].pose;
+    return FPM_OK;
+}
+
+int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfAlign];
     *ms = p.ms;
     *launches = p.launches;
     *bytes = p.bytes;

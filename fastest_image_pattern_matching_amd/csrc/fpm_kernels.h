@@ -294,6 +294,27 @@ struct InspectArgs {
 };
 // k_model_inspect, k_patch_warp's grid; the table form when luts is set.  Returns false for a grid past 2^31 - 1.
 bool launch_model_inspect(InspectArgs c, hipStream_t st);
+// ---- pose alignment (fpm_align_*): the patches of a job table against the template and its
+// central-difference gradient beneath them, reduced to the eleven exact sums of one Gauss-Newton step per patch.
+// The record's fields, in fpm_align_sums' order; signed ones are kept in two's complement.
+enum { kAlnN, kAlnHxx, kAlnHxy, kAlnHyy, kAlnHxt, kAlnHyt, kAlnHtt, kAlnGx, kAlnGy, kAlnGt, kAlnSsd, kAlignFields };
+constexpr int kAlignMaxSide = 4096;             // with the area cap every sum stays below 2^62 (include/fpm.h)
+constexpr int64_t kAlignMaxArea = (int64_t)1 << 20;
+struct AlignAcc {
+    uint64_t f[kAlignFields];   // zero-filled before the launch
+};
+struct AlignArgs {
+    PatchArgs p;             // jobs, sources and patch size as for k_patch_warp; out unused
+    const uint8_t* tmpl;     // template level 0, row pitch tp (a multiple of 64, >= tw + 4)
+    int32_t tp;
+    int32_t tw, th;          // the template's size: the gradient is read from all of it, not only from the rectangle
+    int32_t rx, ry;          // the rectangle's origin in the template (the rectangle lies inside it)
+    const uint8_t* luts;     // [njobs][256] or null
+    AlignAcc* acc;           // [njobs]
+};
+// k_patch_align, k_patch_warp's grid; the table form when luts is set.  Returns false, launching nothing, for a grid past
+// 2^31 - 1 or a rectangle beyond the caps.
+bool launch_patch_align(AlignArgs c, hipStream_t st);
 // ---- learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit): what learnPattern
 // derives from a template pyramid that already lies in the template slab, in one launch over all its levels.
 constexpr int kTmplPrepMaxLevels = 16;   // a 2^26-pixel template at min_reduce_area 1 has 13 levels above level 0

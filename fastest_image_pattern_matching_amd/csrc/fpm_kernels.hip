@@ -2960,6 +2960,133 @@ bool launch_patch_warp(PatchArgs a, hipStream_t st) {
     return true;
 }
 
+// k_patch_align (fpm_align_*): k_patch_compare's tile and sampling (patch_tile_stage /
+// patch_sample4), reduced to the eleven sums of one Gauss-Newton step of the pose against the template: with Tx, Ty the
+// template's central differences (twice the derivative), X, Y the pixel's doubled coordinates about the rectangle's
+// centre, Jt = X Ty - Y Tx and r = L[I] - T, the sums of Tx^2, Tx Ty, Ty^2, Tx Jt, Ty Jt, Jt^2, Tx r, Ty r, Jt r and r^2
+// over the used pixels, and their count.  A pixel is used when its template pixel has all four neighbours inside the
+// template; every other pixel, and every lane past the patch's right or bottom edge, runs through each barrier and
+// fold with Tx = Ty = r = 0: the value is masked, not only the store.
+//   LUT: L = the job's 256-byte table, staged in LDS (else L = identity)
+// Template reads: rows v - 1, v, v + 1 beneath the lane's 4 pixels as aligned dwords, funnel-shifted to bytes u .. u + 3
+// (rows above and below) and u - 1 .. u + 4 (the centre row: the dword before the group only where the group starts a
+// dword, and never before the row).  The row pitch is a multiple of 64 and at least tw + 4, so every dword lies inside
+// its row.  The neighbours come from the template, not from other lanes: tile borders need no exchange.
+// Reduction by wave-local moments: Jt^2 of one tile reaches 10^15, which no 32-bit fold carries, and 64-bit folds
+// cost two DPP moves and an add with carry per step and field.  Instead a wave writes X = Xb + 2 lu and Y = Yb + 2 lv
+// with lu = 0 .. 63 its tile column and lv = 0 .. 3 its row among the wave's four, so that Jt = (Xb Ty - Yb Tx) + 2 Jl with
+// Jl = lu Ty - lv Tx, |Jl| <= 66 * 255.  The wave folds the LOCAL moments in 32 bits with wave_fold -- over its 256
+// pixels |sum Tx Jl|, |sum Jl r| <= 256 * 255 * 16830 < 2^31 and the second moments <= 256 * 65025 < 2^24; sum Jl^2 <=
+// 256 * 16830^2 does not fit, so each lane splits its own four-pixel sum (< 2^31) into a low and a high half-word that
+// are folded apart, the count riding above the high one -- and the folds end in scalar registers (readlane), where the
+// wave-uniform Xb and Yb turn them into the eleven fields in 64-bit scalar arithmetic.  The four waves meet in LDS;
+// one u64 integer atomic per non-zero field and workgroup goes into the hit's zero-filled record (signed fields wrap in
+// two's complement), so the record does not depend on the order of the workgroups.
+__device__ __forceinline__ uint32_t tmpl_read4(const uint8_t* row, int x, int pitch) {
+    const int c0 = x & ~3;
+    const uint32_t lo = *(const uint32_t*)(row + c0);
+    const uint32_t hi = (x & 3) && c0 + 4 < pitch ? *(const uint32_t*)(row + c0 + 4) : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)x);
+}
+
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_patch_align(const AlignArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
+    __shared__ unsigned long long part[4][kAlignFields];
+    const PatchArgs& a = c.p;
+    const int tid = threadIdx.x;
+    if (LUT) {
+        // the job index as patch_tile_stage derives it; the helper's first barrier orders these writes before any read
+        const int job = xcd_remap(blockIdx.x, gridDim.x) / (a.tiles_x * a.tiles_y);
+        if (tid < 64) ((uint32_t*)lut)[tid] = ((const uint32_t*)(c.luts + (size_t)job * 256))[tid];
+    }
+    const PatchTile T = patch_tile_stage(a, tab, FT, tid);
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = T.x0 + gx, y = T.y0 + r;
+    const int left = a.pw - x;
+    const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
+    const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
+    const int tx = c.rx + x, ty = c.ry + y;
+    const bool row_used = nu > 0 && ty >= 1 && ty <= c.th - 2;   // rows ty - 1 and ty + 1 exist
+    uint32_t cw = 0, lw = 0, rw = 0, uw = 0, dw = 0;   // the template at u, u - 1, u + 1, and in the rows above and below
+    if (row_used) {
+        const uint8_t* trow = c.tmpl + (size_t)ty * c.tp;
+        const int c0 = tx & ~3, k = tx & 3;
+        const uint32_t lo = *(const uint32_t*)(trow + c0);
+        const uint32_t hi = c0 + 4 < c.tp ? *(const uint32_t*)(trow + c0 + 4) : 0u;
+        const uint32_t pv = k == 0 && c0 >= 4 ? *(const uint32_t*)(trow + c0 - 4) : 0u;
+        cw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)k);
+        lw = k == 0 ? __builtin_amdgcn_alignbyte(lo, pv, 3u) : __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k - 1));
+        rw = k == 3 ? hi : __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k + 1));
+        uw = tmpl_read4(trow - c.tp, tx, c.tp);
+        dw = tmpl_read4(trow + c.tp, tx, c.tp);
+    }
+    // the lane's local moments over its 4 pixels
+    const int lv = r & 3;
+    int n = 0, sxx = 0, sxy = 0, syy = 0, sxj = 0, syj = 0, sxr = 0, syr = 0, sjr = 0, srr = 0;
+    uint32_t sjj = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const bool used = row_used && u < nu && tx + u >= 1 && tx + u <= c.tw - 2;
+        const int i = (iw >> (8 * u)) & 255;
+        const int v = LUT ? (int)lut[i] : i;
+        const int gxv = used ? (int)((rw >> (8 * u)) & 255) - (int)((lw >> (8 * u)) & 255) : 0;
+        const int gyv = used ? (int)((dw >> (8 * u)) & 255) - (int)((uw >> (8 * u)) & 255) : 0;
+        const int rv = used ? v - (int)((cw >> (8 * u)) & 255) : 0;   // unused: nothing (L[0] may not be 0)
+        const int jl = (gx + u) * gyv - lv * gxv;
+        n += used ? 1 : 0;
+        sxx += gxv * gxv; sxy += gxv * gyv; syy += gyv * gyv;
+        sxj += gxv * jl; syj += gyv * jl; sjj += (uint32_t)(jl * jl);
+        sxr += gxv * rv; syr += gyv * rv; sjr += jl * rv; srr += rv * rv;
+    }
+    // wave totals in scalar registers (signed sums fold as their bit patterns: they fit 32 bits)
+    const int64_t Sxx = wave_fold<false>((uint32_t)sxx), Syy = wave_fold<false>((uint32_t)syy);
+    const int64_t Sxy = (int32_t)wave_fold<false>((uint32_t)sxy);
+    const int64_t SxJ = (int32_t)wave_fold<false>((uint32_t)sxj), SyJ = (int32_t)wave_fold<false>((uint32_t)syj);
+    const int64_t Sxr = (int32_t)wave_fold<false>((uint32_t)sxr), Syr = (int32_t)wave_fold<false>((uint32_t)syr);
+    const int64_t SJr = (int32_t)wave_fold<false>((uint32_t)sjr);
+    const int64_t Srr = wave_fold<false>((uint32_t)srr);
+    const uint32_t jlo = wave_fold<false>(sjj & 0xffffu);                          // <= 64 * 65535
+    const uint32_t jhn = wave_fold<false>((sjj >> 16) | ((uint32_t)n << 21));      // high halves < 2^21; n <= 256 above
+    const int64_t SJJ = ((int64_t)(jhn & 0x1fffffu) << 16) + jlo;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t Xb = 2 * T.x0 - (a.pw - 1), Yb = 2 * (T.y0 + 4 * wave) - (a.ph - 1);
+    int64_t f[kAlignFields];
+    f[kAlnN] = jhn >> 21;
+    f[kAlnHxx] = Sxx; f[kAlnHxy] = Sxy; f[kAlnHyy] = Syy;
+    f[kAlnHxt] = Xb * Sxy - Yb * Sxx + 2 * SxJ;
+    f[kAlnHyt] = Xb * Syy - Yb * Sxy + 2 * SyJ;
+    f[kAlnHtt] = Xb * Xb * Syy - 2 * Xb * Yb * Sxy + Yb * Yb * Sxx + 4 * Xb * SyJ - 4 * Yb * SxJ + 4 * SJJ;
+    f[kAlnGx] = Sxr; f[kAlnGy] = Syr;
+    f[kAlnGt] = Xb * Syr - Yb * Sxr + 2 * SJr;
+    f[kAlnSsd] = Srr;
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kAlignFields; ++k) part[wave][k] = (unsigned long long)f[k];
+    }
+    __syncthreads();
+    if (tid < kAlignFields) {
+        const unsigned long long s = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+        if (s) atomicAdd((unsigned long long*)&c.acc[T.job].f[tid], s);
+    }
+}
+
+bool launch_patch_align(AlignArgs c, hipStream_t st) {
+    PatchArgs& a = c.p;
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    if (a.pw > kAlignMaxSide || a.ph > kAlignMaxSide || (int64_t)a.pw * a.ph > kAlignMaxArea) return false;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX) return false;
+    const dim3 g((unsigned)grid), blk(256);
+    if (c.luts) hipLaunchKernelGGL((k_patch_align<true>), g, blk, 0, st, c);
+    else hipLaunchKernelGGL((k_patch_align<false>), g, blk, 0, st, c);
+    return true;
+}
+
 // ============================================================================================== variation model
 // k_model_accum (fpm_model_train_last / fpm_model_train_at): the per-pixel sum and sum of squares
 // of the patches of a job table, none of them written.  k_patch_warp's tile and 4 pixels per lane; a workgroup owns one

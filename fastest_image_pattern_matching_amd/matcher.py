@@ -364,6 +364,60 @@ def model_derive(n: int, total: int, total_sq: int, abs_threshold: int = 8, k: f
     return mean.value, lo.value, hi.value
 
 
+# -- pose alignment (fpm_align_*): least-squares polish of every hit's pose against the template ----------------------
+# one row per hit: fpm_align_sums / fpm_align_result, field for field
+ALIGN_SUMS_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.AlignSums._fields_], align=True)
+ALIGN_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.AlignResult._fields_], align=True)
+assert ALIGN_SUMS_DTYPE.itemsize == C.sizeof(L.AlignSums) and ALIGN_DTYPE.itemsize == C.sizeof(L.AlignResult)
+
+
+def align_rect(rect, tw: int, th: int) -> Tuple[int, int, int, int]:
+    """An alignment rectangle (x, y, w, h) for a ``tw`` x ``th`` template as four ints; None = the whole template.  A
+    comparison rectangle (inside the template) under two narrower caps: at most 2^20 pixels, sides of at most 4096
+    (include/fpm.h: they keep every sum below 2^62).  Raises ValueError otherwise.  Pure: no device."""
+    x, y, w, h = compare_rect(rect, tw, th)
+    if w > L.ALIGN_MAX_SIDE or h > L.ALIGN_MAX_SIDE:
+        raise ValueError(f"rectangle {(x, y, w, h)}: sides of at most {L.ALIGN_MAX_SIDE}")
+    if w * h > L.ALIGN_MAX_AREA:
+        raise ValueError(f"rectangle {(x, y, w, h)} holds more than 2^20 pixels")
+    return x, y, w, h
+
+
+def align_solve(sums):
+    """fpm_align_solve: ``(du, dv, dphi, singular)`` -- the Gauss-Newton step of one record of ALIGN_SUMS_DTYPE (or a
+    mapping / sequence of its eleven integers in order), by the engine's own code: du, dv in patch pixels, dphi in
+    radians; a singular step is (0, 0, 0, True).  Host only (no device)."""
+    names = [f[0] for f in L.AlignSums._fields_]
+    if isinstance(sums, dict) or (hasattr(sums, "dtype") and getattr(sums.dtype, "names", None)):
+        vals = [int(sums[k]) for k in names]
+    else:
+        vals = [int(v) for v in sums]
+    if len(vals) != len(names) or not all(-2 ** 63 <= v < 2 ** 63 for v in vals):
+        raise ValueError("fpm_align_solve: eleven int64 sums expected")
+    rec = L.AlignSums(*vals)
+    du, dv, dphi = C.c_double(), C.c_double(), C.c_double()
+    rc = L.load().fpm_align_solve(C.byref(rec), C.byref(du), C.byref(dv), C.byref(dphi))
+    if rc not in (0, 1):
+        raise ValueError(f"fpm_align_solve failed with {rc}")
+    return du.value, dv.value, dphi.value, bool(rc)
+
+
+def align_update(src_w: int, src_h: int, rect, lt, angle: float, du: float, dv: float, dphi: float):
+    """fpm_align_update: ``((lt_x, lt_y), angle)`` -- the pose after the step (du, dv, dphi) of a pose (ptLT ``lt`` as
+    f32, ``angle`` in degrees) on a ``src_w`` x ``src_h`` source for the rectangle ``rect`` (x, y, w, h): the pose whose
+    patch map is the current one composed with the rotation by dphi about the rectangle's centre and the shift (du,
+    dv).  ``lt`` comes back as float32 values.  Host only (no device)."""
+    x, y, w, h = (int(v) for v in rect)
+    r = L.PatchRect(x, y, w, h)
+    ox, oy, oa = C.c_float(), C.c_float(), C.c_double()
+    rc = L.load().fpm_align_update(int(src_w), int(src_h), C.byref(r), float(np.float32(lt[0])), float(np.float32(lt[1])),
+                                   float(angle), float(du), float(dv), float(dphi), C.byref(ox), C.byref(oy),
+                                   C.byref(oa))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_align_update failed with {rc}")
+    return (ox.value, oy.value), oa.value
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -1080,6 +1134,96 @@ class TemplateMatcher:
         ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
         if self._lib.fpm_model_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
             raise ValueError(f"fpm_model_profile({which}) failed")
+        return ms.value, n.value, b.value
+
+    # -- pose alignment: every hit polished by least squares against the template (fpm_align_*) ---------------------
+    def _align_rect(self, rect):
+        """(fpm_patch_rect or None, (x, y, w, h)) of an alignment: ``rect``, else the user-defined rectangle when one is
+        set and passes align_rect, else the whole template (NULL)."""
+        tw, th = self._template_size()
+        if rect is None and self._user_rect is not None:
+            try:
+                rect = align_rect(self._user_rect, tw, th)
+            except ValueError:
+                rect = None
+        r = align_rect(rect, tw, th)
+        return (None if rect is None else L.PatchRect(*r)), r
+
+    @staticmethod
+    def _align_args(iters, max_step):
+        if int(iters) != iters or not 1 <= int(iters) <= L.ALIGN_MAX_ITERS:
+            raise ValueError(f"iters {iters!r} must be a whole number 1 .. {L.ALIGN_MAX_ITERS}")
+        if not 0.0 < float(max_step) <= L.ALIGN_MAX_STEP:
+            raise ValueError(f"max_step {max_step!r} must be above 0 and at most {L.ALIGN_MAX_STEP} pixels")
+        return int(iters), float(max_step)
+
+    def align_sums_at(self, src_index, lts, angles, rect=None, normalize: bool = False) -> np.ndarray:
+        """The sums of one Gauss-Newton step of the pose at every pose supplied, on the staged sources
+        (fpm_align_sums_at): a structured array (ALIGN_SUMS_DTYPE) of exact integers -- n_used, the six entries of the
+        normal matrix, the three of the gradient, ssd (include/fpm.h).  One launch of k_patch_align; poses as
+        patches_at."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        r, _ = self._align_rect(rect)
+        out = np.zeros(len(idx), ALIGN_SUMS_DTYPE)
+        rc = self._lib.fpm_align_sums_at(self._ctx, C.byref(r) if r is not None else None,
+                                         idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
+                                         ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx),
+                                         L.COMPARE_NORMALIZE if normalize else 0,
+                                         out.ctypes.data_as(C.POINTER(L.AlignSums)))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "align_sums_at")
+        return out
+
+    def align_at(self, src_index, lts, angles, rect=None, iters: int = 3, max_step: float = 2.0,
+                 normalize: bool = False) -> np.ndarray:
+        """align_last from poses the caller supplies, on the staged sources (fpm_align_at); poses as patches_at.  Needs
+        staged sources, not a search; nothing in the matcher changes."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        iters, max_step = self._align_args(iters, max_step)
+        r, _ = self._align_rect(rect)
+        out = np.zeros(len(idx), ALIGN_DTYPE)
+        rc = self._lib.fpm_align_at(self._ctx, C.byref(r) if r is not None else None,
+                                    idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
+                                    ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx), iters, max_step,
+                                    L.COMPARE_NORMALIZE if normalize else 0, out.ctypes.data_as(C.POINTER(L.AlignResult)))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "align_at")
+        return out
+
+    def align_last(self, source: int = 0, rect=None, iters: int = 3, max_step: float = 2.0, normalize: bool = False,
+                   adopt: bool = False) -> np.ndarray:
+        """Every result of the last search polished by least squares against the learned template, where the pixels
+        are: ``iters`` Gauss-Newton steps of shift and rotation, ``iters + 1`` launches, no crop written
+        (fpm_align_last).  Returns a structured array (ALIGN_DTYPE), one row per result of ``source`` in result order
+        (``source=-1``: all sources): the aligned pose lt_x, lt_y (f32), angle (degrees), ssd_start and ssd (the sum of
+        squared differences at the start and at the returned pose: ssd <= ssd_start), n_used, evals, best_eval and flags
+        (L.ALIGN_SINGULAR, L.ALIGN_STEP_CLAMPED: the hit stopped early; L.ALIGN_KEPT_START: no step improved it).  A step
+        that would move a corner of the rectangle by more than ``max_step`` source pixels stops the hit.
+        ``normalize``: the pixels go through the hit's gain / offset table, built once at the start pose.
+        ``adopt=True``: the aligned poses replace the matcher's last poses -- last_patches, last_compare, last_inspect,
+        model_train_last and learn_hit sample at them until the next search; the results of the search are unchanged."""
+        iters, max_step = self._align_args(iters, max_step)
+        r, _ = self._align_rect(rect)
+        pr = C.byref(r) if r is not None else None
+        flags = (L.COMPARE_NORMALIZE if normalize else 0) | (L.ALIGN_ADOPT if adopt else 0)
+        n = C.c_int32()
+        rc = self._lib.fpm_align_last(self._ctx, pr, int(source), iters, max_step, flags, None, 0, C.byref(n))
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "align_last")
+        out = np.zeros(n.value, ALIGN_DTYPE)
+        if n.value:
+            rc = self._lib.fpm_align_last(self._ctx, pr, int(source), iters, max_step, flags,
+                                          out.ctypes.data_as(C.POINTER(L.AlignResult)), n.value, C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "align_last")
+        return out
+
+    def align_profile(self):
+        """``(ms, launches, bytes)`` of k_patch_align, collected under profile(True) and cleared by profile_reset
+        (fpm_align_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_align_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError("fpm_align_profile failed")
         return ms.value, n.value, b.value
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------

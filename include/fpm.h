@@ -427,6 +427,109 @@ int fpm_model_derive(int32_t n, int64_t sum, int64_t sum_sq, int32_t a, int32_t 
  * k_model_inspect (source pixels + lo and hi read + excess pixels written). */
 int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
 
+/* --- pose alignment: every hit polished by least squares against the template, on the device (no reference equivalent)
+ * The pose the entries above sample at is what the search left: the layer-0 integer peak, or the 3 x 3 x 3 quadratic fit
+ * of NCC scores, on an angle grid of atan(2 / max(w, h)).  A quarter-pixel residue moves an edge pixel by tens of gray
+ * levels.  These entries run Gauss-Newton iterations of the pose (shift and rotation) against the template where the
+ * pixels are; per iteration one launch of k_patch_align reduces every hit to eleven exact integers, the host solves a
+ * 3 x 3 system per hit in f64, and no crop is written.  ("Refine" names the pyramid descent here, fpm_op_refine; this
+ * is "align".)
+ * Rectangle.  (x, y, w, h) in template coordinates and inside the template, as a comparison rectangle, under two
+ * narrower caps: 1 <= w * h <= 2^20 and w, h <= 4096.  NULL = the whole template; a template beyond the caps with NULL
+ * is FPM_E_INVALID_ARG.  The caps bound every sum: |Tx|, |Ty|, |r| <= 255, |X| <= w - 1 and |Y| <= h - 1 give |Jt| < 255
+ * (w + h), and under both caps w + h <= 4096 + 256 = 4352, so the largest sum, h_tt = sum Jt^2, stays below n * 255^2 *
+ * (w + h)^2 <= 2^20 * 65025 * 4352^2 < 2^62; every other sum is smaller.  Src7's 762 x 521 template fits.
+ * Pixels.  I(u, v) is the pixel (u, v) of the patch fpm_last_patches gives for that rectangle and pose (same matrix,
+ * same fixed-point bilinear arithmetic, border 0, the inverted plane under bitwise_not); T(u, v) is template level 0
+ * at (x + u, y + v).  With FPM_COMPARE_NORMALIZE I is LUT[I], the hit's table built exactly as fpm_last_compare builds
+ * it (the sums launch of k_patch_compare, fpm_compare_derive's rule, the tables to the device) -- built ONCE, at the
+ * start pose, and reused by every iteration.
+ * Pixels whose footprint leaves the source are 0, as in a patch, and are NOT masked: a hit cut by the frame's edge is
+ * pulled towards the frame (its residual there is -T), so its aligned pose is biased.
+ * Gradients, exact integers: Tx = T(u + 1, v) - T(u - 1, v), Ty = T(u, v + 1) - T(u, v - 1) -- twice the derivative, in
+ * -255 .. 255 -- read from the whole template, not only from the rectangle.  A pixel is USED iff 1 <= x + u <= tw - 2 and
+ * 1 <= y + v <= th - 2.
+ * Per used pixel, with X = 2 u - (w - 1), Y = 2 v - (h - 1) (doubled coordinates about the rectangle's centre, integers):
+ *     Jt = X Ty - Y Tx,    r = I - T.
+ * Sums over the used pixels (fpm_align_sums, exact, int64):
+ *     n_used, h_xx = sum Tx^2, h_xy = sum Tx Ty, h_yy = sum Ty^2, h_xt = sum Tx Jt, h_yt = sum Ty Jt, h_tt = sum Jt^2,
+ *     g_x = sum Tx r, g_y = sum Ty r, g_t = sum Jt r, ssd = sum r^2.
+ * Solve (fpm_align_solve).  H q = -g with H = [[h_xx, h_xy, h_xt], [h_xy, h_yy, h_yt], [h_xt, h_yt, h_tt]], every sum
+ * converted to f64 first, by the symmetric adjugate in this order (no fused multiply-add):
+ *     c00 = h_yy h_tt - h_yt h_yt   c01 = h_xt h_yt - h_xy h_tt   c02 = h_xy h_yt - h_xt h_yy
+ *     c11 = h_xx h_tt - h_xt h_xt   c12 = h_xy h_xt - h_xx h_yt   c22 = h_xx h_yy - h_xy h_xy
+ *     det = (h_xx c00 + h_xy c01) + h_xt c02
+ *     q0 = -(((c00 g_x + c01 g_y) + c02 g_t) / det), q1 = -(((c01 g_x + c11 g_y) + c12 g_t) / det),
+ *     q2 = -(((c02 g_x + c12 g_y) + c22 g_t) / det)
+ *     du = 2 q0, dv = 2 q1 (patch pixels), dphi = 4 q2 (radians).
+ * The step is SINGULAR when n_used < 3, det <= 0 or det, du, dv or dphi is not finite; it is then (0, 0, 0).
+ * Update (fpm_align_update), all in f64 with glibc cos and sin.  A = the inverted patch matrix of the current pose
+ * (fpm_patch_matrix, inverted as cv::warpAffine inverts it), cx = (w - 1) / 2, cy = (h - 1) / 2.  The new pose is the
+ * one whose patch map is A o D, D = the rotation by dphi about the rectangle's centre followed by the shift (du, dv):
+ *     angle' = angle + dphi * 180 / pi
+ *     P = A (cx + du, cy + dv, 1)
+ *     lt' = P - L' (x + cx, y + cy),   L' = [[cos a', -sin a'], [sin a', cos a']],  a' = angle' * pi / 180.
+ * It is evaluated as a difference from the current pose, with A (cx, cy, 1) = lt + L (x + cx, y + cy) (L as L', of
+ * the current angle) taken as exact, so that a zero step returns the pose bit for bit:
+ *     lt' = (float) (lt + ((A00 du + A01 dv) + ((c - c') kx - (s - s') ky),  (A10 du + A11 dv) + ((s - s') kx + (c - c') ky)))
+ * with kx = x + cx, ky = y + cy, c = cos a, s = sin a, c' = cos a', s' = sin a'; the sum is rounded to f32 once.
+ * Iteration (fpm_align_at / fpm_align_last; iters 1 .. 8; 0 < max_step <= 1024 source pixels, 2.0 is a good value).
+ * Evaluation 0 is at the start pose.  After evaluation k < iters the host solves and updates every live hit.  A hit
+ * FREEZES when its step is singular (FPM_ALIGN_SINGULAR), or when the step would move a corner of the rectangle by more
+ * than max_step -- for a corner at (ex, ey) from the centre, with c = cos dphi, s = sin dphi,
+ *     mx = ((c ex - s ey) - ex) + du,  my = ((s ex + c ey) - ey) + dv,  mx mx + my my > max_step max_step
+ * -- or the new pose would leave the samplers' range of 2^20 pixels (both FPM_ALIGN_STEP_CLAMPED).  A frozen hit takes
+ * no further step; it stays in the later launches at its last pose.  Evaluation `iters` is at the last pose: iters + 1
+ * launches per call, one copy of the records to the host after each.  The pose returned is the evaluated pose with the
+ * lowest ssd, the earliest on ties (FPM_ALIGN_KEPT_START when that is evaluation 0): ssd <= ssd_start always.
+ * evals = the poses evaluated for the hit (steps taken + 1), best_eval = the index of the returned one.
+ * Launches.  k_patch_align, never part of a search or of a captured graph; one clearing of the records ahead of each.
+ * With FPM_COMPARE_NORMALIZE the sums launch of k_patch_compare and a copy of the sums to the host come first.
+ * Errors.  Rectangle, iters, max_step or flags out of range: FPM_E_INVALID_ARG, nothing launched.  A call that fails
+ * leaves the context untouched.  Additive entries: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_align_sums {
+    int64_t n_used, h_xx, h_xy, h_yy, h_xt, h_yt, h_tt, g_x, g_y, g_t, ssd;
+} fpm_align_sums;
+typedef struct fpm_align_result {
+    float lt_x, lt_y;          /* the aligned pose: ptLT as f32 */
+    double angle;              /* and its angle in degrees */
+    int64_t ssd_start, ssd;    /* sum r^2 at the start pose and at the returned one */
+    int64_t n_used;
+    int32_t evals, best_eval;
+    int32_t flags;             /* FPM_ALIGN_SINGULAR | FPM_ALIGN_STEP_CLAMPED | FPM_ALIGN_KEPT_START */
+    int32_t reserved;          /* 0 */
+} fpm_align_result;
+#define FPM_ALIGN_SINGULAR 1       /* result flags */
+#define FPM_ALIGN_STEP_CLAMPED 2
+#define FPM_ALIGN_KEPT_START 4
+#define FPM_ALIGN_ADOPT 2          /* call flag of fpm_align_last, beside FPM_COMPARE_NORMALIZE */
+
+/* One launch at caller-supplied poses on the staged sources: the kernel's records.  Poses and state rules as
+ * fpm_compare_at; flags: FPM_COMPARE_NORMALIZE or 0. */
+int fpm_align_sums_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                      const double* angles, int32_t n_poses, int32_t flags, fpm_align_sums* out);
+/* The iteration from caller-supplied poses; poses and state rules as fpm_compare_at; flags: FPM_COMPARE_NORMALIZE or 0. */
+int fpm_align_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                 const double* angles, int32_t n_poses, int32_t iters, double max_step, int32_t flags,
+                 fpm_align_result* out);
+/* The iteration from the poses of the last search's hits, in result order; source, cap, *n and every state rule as
+ * fpm_last_compare.  With FPM_ALIGN_ADOPT the aligned poses replace the context's last poses: fpm_last_patches*,
+ * fpm_last_compare, fpm_last_inspect, fpm_model_train_last, fpm_learn_hit and a later fpm_align_last sample at them
+ * until the next search.  fpm_last_results and fpm_last_candidates are never changed.  Without the flag nothing in the
+ * context changes. */
+int fpm_align_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t iters, double max_step,
+                   int32_t flags, fpm_align_result* out, int32_t cap, int32_t* n);
+/* host only, no context: the step of one record by the rule above.  Returns 0, or 1 for a singular step (then du = dv =
+ * dphi = 0), or FPM_E_INVALID_ARG for a null argument. */
+int fpm_align_solve(const fpm_align_sums* sums, double* du, double* dv, double* dphi);
+/* host only, no context: the pose after a step by the rule above; rect must not be NULL (only x, y, w, h >= 1 matter). */
+int fpm_align_update(int32_t src_w, int32_t src_h, const fpm_patch_rect* rect, float lt_x, float lt_y, double angle,
+                     double du, double dv, double dphi, float* lt2_x, float* lt2_y, double* angle2);
+/* Timing of k_patch_align, collected under fpm_profile_enable and cleared by fpm_profile_reset as fpm_model_profile's
+ * (no FPM_K_* index: FPM_K_COUNT is unchanged; the normalising sums launch counts under FPM_K_COMPARE).  bytes =
+ * source pixels read + template pixels read. */
+int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent

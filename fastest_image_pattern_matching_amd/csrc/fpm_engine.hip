@@ -437,6 +437,15 @@ static bool angle_list_ok(const fpm_params& prm, double step, bool mfc) {
     return n <= kMaxTopAngles;
 }
 
+// The list threshold of the matrix-core top layer and its prefilter's constants (fpm_kernels.hip, "Exactness of the
+// bound"): thr = the layer score; thrK carries the 1e-5 relative margin, E the absolute slack of the two f32 terms
+void top_mma_thresholds(TopMmaArgs& A, double thr, const TmplLevel& tt) {
+    const double tm = thr * (1.0 - 1e-5);
+    A.thrK = (float)(tm * tm * tt.norm * tt.norm * (double)A.area);
+    A.E = 1024.f;
+    A.thr = thr;
+}
+
 // The matrix-core top layer's plan (k_top_mma): whether it applies, its strip width and row runs
 // (work units), the B fragments of the top template level and the candidate-list buffers.  Applies where the template
 // level fits the kernel's two MFMA layouts, the layer score is > 0.01 (the greedy peak forms need thr > 0, and the lists
@@ -537,10 +546,8 @@ int plan_top_mma(fpm_ctx* ctx, Plan& P, const TmplLevel& tt) {
     A.nunits = (int)units.size();
     A.bfrag = P.d_tmu.as<uint8_t>(ubytes);
     A.prefilter = A.area <= 258 ? 1 : 0;
-    const double tm = thr * (1.0 - 1e-5);
-    A.thrK = (float)(tm * tm * tt.norm * tt.norm * (double)A.area);
-    A.E = 1024.f;
-    A.thr = thr; A.mean = tt.mean; A.norm = tt.norm; A.inv_area = tt.inv_area;
+    top_mma_thresholds(A, thr, tt);
+    A.mean = tt.mean; A.norm = tt.norm; A.inv_area = tt.inv_area;
     A.cand = P.d_ncand.as<int32_t>();
     A.cand_val = P.d_tcandv.as<float>();
     A.cand_cap = P.tcand_cap;
@@ -846,6 +853,67 @@ int check_sizes(fpm_ctx* ctx, int w, int h) {   // TemplateMatcher.cpp:99-114
 constexpr int kPrologueMaxSources = 2;            // step prologue of the small layers up to this batch size
 constexpr int64_t kPyr2MaxBytes = 16ll << 20;     // two-level pyramid launches up to this many input bytes
 
+// K1: source pyramid (all staged sources per launch).  pyr_zero: the first launch also zeroes the plan's counters
+// (d_livecnt, P.nzero words) ahead of the top layer's atomics.
+void enqueue_pyramid(fpm_ctx* ctx, bool pyr_zero) {
+    Plan& P = ctx->plan;
+    const int L = P.L, S = P.S;
+    hipStream_t st = ctx->stream;
+    uint8_t* dsrc = ctx->d_src.as<uint8_t>();
+    // Two levels per launch (k_pyr_down2) where the pair's input is small (<= kPyr2MaxBytes over the batch:
+    // launch-bound levels, e.g. every pair of a single Src7 search: 14.8 -> 11.3 us for levels 0-2), else one level per
+    // launch (k_pyr_down_s keeps more workgroups in flight: 43 Src7 levels 0-2 in 197 us vs 217-258 us,
+    // profiles/r04/mb32_r04g.txt).  FPM_PYR2=0 / 1 forces one form.
+    const char* pyr2_env = getenv("FPM_PYR2");
+    const int pyr2_mode = pyr2_env ? atoi(pyr2_env) : -1;
+    for (int l = 1; l <= L;) {
+        const SrcLevel& a = ctx->src[l - 1];
+        const SrcLevel& b = ctx->src[l];
+        int32_t* zero = l == 1 && pyr_zero ? P.d_livecnt.as<int32_t>() : nullptr;
+        const int nzero = l == 1 && pyr_zero ? P.nzero : 0;
+        const int64_t in_bytes = (int64_t)S * a.w * a.h;
+        const bool two = l + 1 <= L && (pyr2_mode >= 0 ? pyr2_mode != 0 : in_bytes <= kPyr2MaxBytes);
+        const SrcLevel& c = ctx->src[two ? l + 1 : l];
+        l += two ? 2 : 1;
+        if (two) {
+            ProfScope ps(ctx, FPM_K_PYR, (int64_t)S * ((int64_t)a.w * a.h + (int64_t)b.w * b.h + (int64_t)c.w * c.h));
+            launch_pyr_down2(dsrc + a.off, a.w, a.h, a.pitch, a.img_bytes, dsrc + b.off, b.w, b.h, b.pitch, b.img_bytes,
+                             dsrc + c.off, c.w, c.h, c.pitch, c.img_bytes, S, st, 0, zero, nzero);
+        } else {
+            ProfScope ps(ctx, FPM_K_PYR, (int64_t)S * ((int64_t)a.w * a.h + (int64_t)b.w * b.h));
+            launch_pyr_down(dsrc + a.off, a.w, a.h, a.pitch, a.img_bytes, dsrc + b.off, b.w, b.h, b.pitch, b.img_bytes, S,
+                            st, 0, zero, nzero);
+        }
+    }
+}
+
+// The split top layer's maps: k_warp (which zeroes the plan's counters) then k_ncc_tile, or k_ncc_map for the template
+// levels beyond its tile form.
+void enqueue_top_split_maps(fpm_ctx* ctx) {
+    Plan& P = ctx->plan;
+    const int L = P.L, S = P.S, J = S * P.nang;
+    hipStream_t st = ctx->stream;
+    const SrcLevel& top = ctx->src[L];
+    const TmplLevel& tt = ctx->tmpl[L];
+    {
+        const int64_t bytes = (int64_t)P.nang * top.w * top.h;
+        ProfScope ps(ctx, FPM_K_TOP_WARP, bytes * S);
+        launch_warp(P.d_jobs.as<WarpJob>(P.off_warp), J, P.max_canvas, st, P.d_livecnt.as<int32_t>(), P.nzero);
+    }
+    {
+        int64_t bytes = 0;
+        for (int a = 0; a < P.nang; ++a) bytes += 4LL * P.map_w[a] * P.map_h[a];
+        ProfScope ps(ctx, FPM_K_TOP_NCC, bytes * S);
+        if (ncc_tile_fits(tt.w, tt.h)) {
+            int mw = 0, mh = 0;
+            for (int a = 0; a < P.nang; ++a) { mw = std::max(mw, P.map_w[a]); mh = std::max(mh, P.map_h[a]); }
+            launch_ncc_tile(P.d_jobs.as<NccJob>(P.off_ncc), J, mw, mh, tt.w, tt.h, st);
+        } else {
+            launch_ncc_map(P.d_jobs.as<NccJob>(P.off_ncc), J, P.max_map, tt.w * tt.h, st);
+        }
+    }
+}
+
 int enqueue_search(fpm_ctx* ctx) {
     Plan& P = ctx->plan;
     const int L = P.L, S = P.S, J = S * P.nang;
@@ -898,31 +966,7 @@ int enqueue_search(fpm_ctx* ctx) {
     // mode 1 (refine == 0: states and live list written directly, no live-count atomics); launch_top_fused checks it
     // (L == stop == 1 also runs mode 1, behind the pyramid launch's zeroing)
     const bool pyr_zero = (top_init && L >= 1) || use_mma;   // (use_mma implies L >= 1: plan_top_mma)
-    // K1: source pyramid (all staged sources per launch).  Two levels per launch (k_pyr_down2) where the pair's input
-    // is small (<= kPyr2MaxBytes over the batch: launch-bound levels, e.g. every pair of a single Src7 search: 14.8 ->
-    // 11.3 us for levels 0-2), else one level per launch (k_pyr_down_s keeps more workgroups in flight: 43 Src7 levels
-    // 0-2 in 197 us vs 217-258 us, profiles/r04/mb32_r04g.txt).  FPM_PYR2=0 / 1 forces one form.
-    const char* pyr2_env = getenv("FPM_PYR2");
-    const int pyr2_mode = pyr2_env ? atoi(pyr2_env) : -1;
-    for (int l = 1; l <= L;) {
-        const SrcLevel& a = ctx->src[l - 1];
-        const SrcLevel& b = ctx->src[l];
-        int32_t* zero = l == 1 && pyr_zero ? P.d_livecnt.as<int32_t>() : nullptr;
-        const int nzero = l == 1 && pyr_zero ? P.nzero : 0;
-        const int64_t in_bytes = (int64_t)S * a.w * a.h;
-        const bool two = l + 1 <= L && (pyr2_mode >= 0 ? pyr2_mode != 0 : in_bytes <= kPyr2MaxBytes);
-        const SrcLevel& c = ctx->src[two ? l + 1 : l];
-        l += two ? 2 : 1;
-        if (two) {
-            ProfScope ps(ctx, FPM_K_PYR, (int64_t)S * ((int64_t)a.w * a.h + (int64_t)b.w * b.h + (int64_t)c.w * c.h));
-            launch_pyr_down2(dsrc + a.off, a.w, a.h, a.pitch, a.img_bytes, dsrc + b.off, b.w, b.h, b.pitch, b.img_bytes,
-                             dsrc + c.off, c.w, c.h, c.pitch, c.img_bytes, S, st, 0, zero, nzero);
-        } else {
-            ProfScope ps(ctx, FPM_K_PYR, (int64_t)S * ((int64_t)a.w * a.h + (int64_t)b.w * b.h));
-            launch_pyr_down(dsrc + a.off, a.w, a.h, a.pitch, a.img_bytes, dsrc + b.off, b.w, b.h, b.pitch, b.img_bytes, S,
-                            st, 0, zero, nzero);
-        }
-    }
+    enqueue_pyramid(ctx, pyr_zero);
     NmsArgs na{};
     na.jobs = P.d_jobs.as<NmsJob>(P.off_nms);
     na.peaks = P.d_peaks.as<Peak>();
@@ -981,23 +1025,7 @@ int enqueue_search(fpm_ctx* ctx) {
     }
     // profiling bytes: each kernel's share of §8(d)'s B_top = sum_angles (W_L H_L + 4 |R_a|): the rotation reads the
     // top level, the correlation writes the map (the rotated canvases are this design's scratch)
-    if (fused_lds == 0 && !use_mma) {
-        const int64_t bytes = (int64_t)P.nang * top.w * top.h;
-        ProfScope ps(ctx, FPM_K_TOP_WARP, bytes * S);
-        launch_warp(P.d_jobs.as<WarpJob>(P.off_warp), J, P.max_canvas, st, P.d_livecnt.as<int32_t>(), P.nzero);
-    }
-    if (fused_lds == 0 && !use_mma) {
-        int64_t bytes = 0;
-        for (int a = 0; a < P.nang; ++a) bytes += 4LL * P.map_w[a] * P.map_h[a];
-        ProfScope ps(ctx, FPM_K_TOP_NCC, bytes * S);
-        if (ncc_tile_fits(tt.w, tt.h)) {
-            int mw = 0, mh = 0;
-            for (int a = 0; a < P.nang; ++a) { mw = std::max(mw, P.map_w[a]); mh = std::max(mh, P.map_h[a]); }
-            launch_ncc_tile(P.d_jobs.as<NccJob>(P.off_ncc), J, mw, mh, tt.w, tt.h, st);
-        } else {
-            launch_ncc_map(P.d_jobs.as<NccJob>(P.off_ncc), J, P.max_map, tt.w * tt.h, st);
-        }
-    }
+    if (fused_lds == 0 && !use_mma) enqueue_top_split_maps(ctx);
     if (fused_lds == 0 && !use_mma) {
         ProfScope ps(ctx, FPM_K_TOP_NMS, 0);   // (reads the maps counted once in B_top)
         if (P.by_block) {   // (the counts and strip keys were zeroed by k_warp)
@@ -4090,6 +4118,107 @@ int fpm_op_peaks(fpm_ctx* ctx, const float* const* maps, const int32_t* mw, cons
             s[0] = k_true[i]; s[1] = hk[i]; s[2] = hk[i] < 0 ? 1 : 0;
             s[3] = by_block ? -1 : nms_plain_form(ni.blk_lds, cap, (long)mw[i] * mh[i]);
         }
+    }
+    return FPM_OK;
+}
+
+// The top-layer scoring of the staged batch by the plan's own tables and launchers (enqueue_pyramid, then
+// enqueue_top_split_maps or launch_top_mma on a copy of P.tma), and what it wrote: the maps, or k_top_mma's lists.
+static_assert(kTopFormExact16 == FPM_TOP_FORM_EXACT16 && kTopFormExact14 == FPM_TOP_FORM_EXACT14 &&
+                  kTopFormSmall == FPM_TOP_FORM_SMALL && kTopFormLarge == FPM_TOP_FORM_LARGE,
+              "stats[5] of fpm_op_top_maps is top_mma_form's value");
+int fpm_op_top_maps(fpm_ctx* ctx, int32_t form, double thr, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats,
+                    int32_t* list_cap, int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap,
+                    int32_t* list_count, int32_t* list_index, float* list_value, int64_t list_slots, int32_t* stats) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!ctx->learned) { ctx->err = "template not learned"; return FPM_E_NOT_LEARNED; }
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (ctx->S <= 0 || !ctx->staged || !ctx->src_valid) { ctx->err = "top maps: no staged sources"; return FPM_E_INVALID_ARG; }
+    const bool sizing = !geom && !maps && !list_count && !list_index && !list_value;
+    const bool want_maps = form == 0 || form == 1;
+    if (form < 0 || form > 2 || !std::isfinite(thr) || (thr > 0 && !(thr > 0.01)) || geom_cap < 0 || maps_cap < 0 ||
+        list_slots < 0 ||
+        (!sizing && (!geom || (want_maps ? !maps : (!list_count || !list_index || !list_value))))) {
+        ctx->err = "bad top maps arguments";
+        return FPM_E_INVALID_ARG;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct ProfOff {   // the launches below are not the search's: the profile counters stay as they were
+        fpm_ctx* c; bool was;
+        explicit ProfOff(fpm_ctx* x) : c(x), was(x->prof) { c->prof = false; }
+        ~ProfOff() { c->prof = was; }
+    } prof_off(ctx);
+    int rc = build_plan(ctx);
+    if (rc != FPM_OK) return rc;
+    Plan& P = ctx->plan;
+    const int L = P.L, S = P.S, nang = P.nang, J = S * nang;
+    std::vector<size_t> dense_off(nang);
+    size_t dense = 0;
+    for (int a = 0; a < nang; ++a) { dense_off[a] = dense; dense += (size_t)P.map_w[a] * P.map_h[a]; }
+    const int lcap = P.top_mma ? P.tcand_cap : 0;
+    if (n_sources) *n_sources = S;
+    if (n_angles) *n_angles = nang;
+    if (map_floats) *map_floats = (int64_t)dense;
+    if (list_cap) *list_cap = lcap;
+    TopMmaArgs ta = P.tma;
+    if (stats) {
+        std::fill(stats, stats + FPM_TOP_MAPS_STATS, 0);
+        stats[0] = P.top_mma ? 1 : 0;
+        stats[5] = -1;
+        stats[7] = P.by_block ? 1 : 0;
+        if (P.top_mma) {
+            ta.mode = 1;
+            stats[1] = lcap; stats[2] = ta.sw; stats[3] = ta.rt - ta.th; stats[4] = ta.nunits;
+            stats[5] = top_mma_form(ta); stats[6] = top_mma_grid(ta);
+        }
+    }
+    if (form != 0 && !P.top_mma) {
+        ctx->err = "top maps: the plan does not take the matrix-core form";
+        return FPM_E_SIZE;
+    }
+    if (sizing) return FPM_OK;
+    if (geom_cap < nang || (want_maps && (uint64_t)maps_cap < (uint64_t)dense * S) ||
+        (!want_maps && (uint64_t)list_slots < (uint64_t)lcap * J)) {
+        ctx->err = "top maps: output capacity below the sizing call's";
+        return FPM_E_CAPACITY;
+    }
+    for (int a = 0; a < nang; ++a) {
+        geom[4 * a + 0] = P.top[a].bw; geom[4 * a + 1] = P.top[a].bh;
+        geom[4 * a + 2] = P.map_w[a]; geom[4 * a + 3] = P.map_h[a];
+    }
+    if (J <= 0) return FPM_OK;
+    hipStream_t st = ctx->stream;
+    rc = apply_polarity(ctx);   // as start_staged, ahead of the pyramid
+    if (rc != FPM_OK) return rc;
+    enqueue_pyramid(ctx, form != 0);   // (the matrix-core form's list counts are among the counters it zeroes)
+    if (want_maps)   // a pixel no kernel writes reads back as a NaN pattern
+        HIP_TRY(hipMemsetAsync(P.d_map.p, 0xff, sizeof(float) * P.map_floats * S, st));
+    if (form == 0) {
+        enqueue_top_split_maps(ctx);
+    } else {
+        if (thr > 0) top_mma_thresholds(ta, thr, ctx->tmpl[L]);
+        HIP_TRY(hipMemsetAsync(ta.cand_cnt, 0, sizeof(int32_t) * J, st));   // no job taken, no list entry yet
+        if (form == 2) {
+            HIP_TRY(hipMemsetAsync(ta.cand, 0xff, sizeof(int32_t) * (size_t)lcap * J, st));
+            HIP_TRY(hipMemsetAsync(ta.cand_val, 0xff, sizeof(float) * (size_t)lcap * J, st));
+        }
+        ta.mode = form == 1 ? 1 : 0;
+        launch_top_mma(ta, st);
+    }
+    HIP_TRY(hipGetLastError());
+    if (want_maps) {
+        std::vector<float> hm(P.map_floats * S);
+        HIP_TRY(hipMemcpyAsync(hm.data(), P.d_map.p, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int s = 0; s < S; ++s)
+            for (int a = 0; a < nang; ++a)
+                std::copy_n(hm.data() + P.map_floats * s + P.map_off[a], (size_t)P.map_w[a] * P.map_h[a],
+                            maps + dense * s + dense_off[a]);
+    } else {
+        HIP_TRY(hipMemcpyAsync(list_count, ta.cand_cnt, sizeof(int32_t) * J, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(list_index, ta.cand, sizeof(int32_t) * (size_t)lcap * J, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(list_value, ta.cand_val, sizeof(float) * (size_t)lcap * J, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return FPM_OK;
 }

@@ -418,6 +418,10 @@ size_t top_mma_lds(const TopMmaArgs& a);
 void top_mma_layout(TopMmaArgs& a, int sw, int max_rows);
 bool top_mma_fits(int tw, int th);   // template shapes the kernel takes (R = 2 up to 17 wide, R = 1 up to 49)
 void launch_top_mma(const TopMmaArgs& a, hipStream_t st);
+// what launch_top_mma takes for `a`: the kernel instantiation (FPM_TOP_FORM_* of include/fpm.h) and the grid of a.mode
+enum { kTopFormExact16 = 0, kTopFormExact14 = 1, kTopFormSmall = 2, kTopFormLarge = 3 };
+int top_mma_form(const TopMmaArgs& a);
+int top_mma_grid(const TopMmaArgs& a);
 // k_nms_greedy over k_top_mma's lists (a.cand_val set): plain getNextMaxLoc key (by_block 0) or s_BlockMax key; with ci
 // (plain, cap <= kNmsInitCap) the candidate init of the jobs it takes.  Needs a.overlap >= 0, as every use of the greedy
 // form (its cell lists hold a rectangle of at most twice the template): plan_top_mma keeps other searches off this path

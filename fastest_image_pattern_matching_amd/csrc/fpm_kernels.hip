@@ -5860,17 +5860,27 @@ static void launch_top_form(const TopMmaArgs& a, int grid, size_t lds, hipStream
     }
 }
 
+// the instantiation launch_top_mma takes: exact-height forms for the two-row layout's common top templates (16 rows: a
+// square template at MinReduceArea 256, BASELINE configs[3]; 14: configs[2]), the masked small form for other heights
+// up to 16, <16, 64> for every other shape
+int top_mma_form(const TopMmaArgs& a) {
+    if (top_mma_small(a) && a.th == 16) return kTopFormExact16;
+    if (top_mma_small(a) && a.th == 14) return kTopFormExact14;
+    return top_mma_small(a) ? kTopFormSmall : kTopFormLarge;
+}
+// mode 1 touches only the jobs left by the greedy form (usually none): a small grid walks the unit list
+int top_mma_grid(const TopMmaArgs& a) { return a.mode == 1 ? std::min(a.nunits, 4 * device_cus()) : a.nunits; }
+
 void launch_top_mma(const TopMmaArgs& a, hipStream_t st) {
     if (a.nunits <= 0) return;
     const size_t lds = top_mma_lds(a);
-    // mode 1 touches only the jobs left by the greedy form (usually none): a small grid walks the unit list
-    const int grid = a.mode == 1 ? std::min(a.nunits, 4 * device_cus()) : a.nunits;
-    // exact-height forms for the two-row layout's common top templates (16 rows: a square template at MinReduceArea
-    // 256, BASELINE configs[3]; 14: configs[2]), the masked small form for other heights up to 16
-    if (top_mma_small(a) && a.th == 16) launch_top_form<8, 32, TM_CP2, 16>(a, grid, lds, st);
-    else if (top_mma_small(a) && a.th == 14) launch_top_form<7, 32, TM_CP2, 14>(a, grid, lds, st);
-    else if (top_mma_small(a)) launch_top_form<8, 32, TM_CP2>(a, grid, lds, st);
-    else launch_top_form<16, 64, TM_CP1>(a, grid, lds, st);
+    const int grid = top_mma_grid(a);
+    switch (top_mma_form(a)) {
+    case kTopFormExact16: launch_top_form<8, 32, TM_CP2, 16>(a, grid, lds, st); break;
+    case kTopFormExact14: launch_top_form<7, 32, TM_CP2, 14>(a, grid, lds, st); break;
+    case kTopFormSmall: launch_top_form<8, 32, TM_CP2>(a, grid, lds, st); break;
+    default: launch_top_form<16, 64, TM_CP1>(a, grid, lds, st); break;
+    }
 }
 
 void launch_top_greedy(const NmsArgs& a0, int njobs, int max_cells, hipStream_t st, const CandInitArgs* ci,

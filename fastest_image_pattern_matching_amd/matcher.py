@@ -1374,6 +1374,51 @@ class TemplateMatcher:
                      counts=cnt[:n].copy(), jobs=st[L.PEAKS_STATS_CALL:].reshape(-1, L.PEAKS_STATS_JOB)[:n].copy())
         return out, stats
 
+    def top_maps(self, form: int, thr: float = 0.0):
+        """fpm_op_top_maps: the top-layer scoring of the staged batch by the search's own plan and launchers.  form 0:
+        the split kernels' maps, 1: k_top_map's maps, 2: k_top_mma's candidate lists at `thr` (<= 0: the layer score).
+        Returns a dict: 'geom' (n_angles, 4) int32 rows (bw, bh, mw, mh); 'stats' dict as include/fpm.h lists them;
+        forms 0 and 1: 'maps'[source][angle] f32 (mh, mw) arrays; form 2: 'counts' (n_sources, n_angles) true counts,
+        'index' and 'value' (n_sources, n_angles, list_cap), the first min(count, list_cap) of each job filled.  Raises
+        ValueError carrying the status as `.rc` (FPM_E_SIZE: the plan does not take the matrix-core form)."""
+        IP, FP = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        ns, na, lc, mf = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        st = np.zeros(L.TOP_MAPS_STATS, np.int32)
+        self._push()
+
+        def call(geom, gcap, maps, mcap, cnt, idx, val, slots):
+            rc = self._check(self._lib.fpm_op_top_maps(
+                self._ctx, int(form), float(thr), C.byref(ns), C.byref(na), C.byref(mf), C.byref(lc), geom, gcap, maps,
+                mcap, cnt, idx, val, slots, st.ctypes.data_as(IP)), "top_maps")
+            if rc != L.FPM_OK:
+                e = ValueError(f"fpm_op_top_maps failed with {rc}: {self.last_error()}")
+                e.rc = rc
+                raise e
+
+        call(None, 0, None, 0, None, None, None, 0)
+        S, nang, cap, dense = ns.value, na.value, lc.value, mf.value
+        geom = np.zeros((max(nang, 1), 4), np.int32)
+        out = {}
+        if form in (0, 1):
+            flat = np.zeros(max(S * dense, 1), np.float32)
+            call(geom.ctypes.data_as(IP), nang, flat.ctypes.data_as(FP), S * dense, None, None, None, 0)
+            offs = np.concatenate([[0], np.cumsum(geom[:nang, 2].astype(np.int64) * geom[:nang, 3])])
+            out["maps"] = [[flat[s * dense + offs[a]:s * dense + offs[a + 1]].reshape(geom[a, 3], geom[a, 2])
+                            for a in range(nang)] for s in range(S)]
+        else:
+            cnt = np.zeros(max(S * nang, 1), np.int32)
+            idx = np.zeros(max(S * nang * cap, 1), np.int32)
+            val = np.zeros(max(S * nang * cap, 1), np.float32)
+            call(geom.ctypes.data_as(IP), nang, None, 0, cnt.ctypes.data_as(IP), idx.ctypes.data_as(IP),
+                 val.ctypes.data_as(FP), S * nang * cap)
+            out["counts"] = cnt[:S * nang].reshape(S, nang)
+            out["index"] = idx[:S * nang * cap].reshape(S, nang, cap)
+            out["value"] = val[:S * nang * cap].reshape(S, nang, cap)
+        out["geom"] = geom[:nang]
+        out["stats"] = dict(top_mma=int(st[0]), list_cap=int(st[1]), sw=int(st[2]), run=int(st[3]), nunits=int(st[4]),
+                            form=int(st[5]), map_grid=int(st[6]), by_block=int(st[7]))
+        return out
+
     def overlap_filter(self, corners, scores, max_overlap: float, device: bool = True):
         """filterWithRotatedRect (TemplateMatcher.cpp:1133-1194) on rectangles given as rows (ltx, lty, rtx, rty, rbx,
         rby) with their scores, in the given order: (indices of the survivors, stats) -- stats as fpm_op_overlap_filter

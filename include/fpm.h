@@ -672,6 +672,48 @@ int fpm_op_peaks(fpm_ctx* ctx, const float* const* maps, const int32_t* mw, cons
                  int32_t tw, int32_t th, int32_t cap, int32_t by_block, int32_t mfc, double thr, double overlap,
                  int32_t form, int32_t list_cap, uint32_t list_seed, fpm_peak* peaks, int32_t* counts,
                  int32_t* stats);
+/* The search's own top-layer scoring over every (source, angle) job of the staged batch, and what it computed: the
+ * score maps before any peak is taken, or the matrix-core form's candidate lists.  Needs a learned template
+ * (FPM_E_NOT_LEARNED) and staged sources (fpm_stage_sources / fpm_stage_sources_device).  The call builds, or reuses,
+ * the plan fpm_match_staged would use with the context's parameters, runs the search's pyramid launches and then only
+ * the top-layer scoring, with the plan's own job tables, work units, B fragments and launchers (launch_top_mma, the
+ * split launchers): no geometry or layout is restated.
+ *   form 0  the split chain as the search selects it (k_warp -> k_ncc_tile / k_ncc_map): full maps
+ *   form 1  k_top_map (the matrix-core form's mode 1) over every job, the list counts zeroed first so that no job is
+ *           skipped: full maps
+ *   form 2  k_top_mma (mode 0), the list counts zeroed first: per job the true count of outputs with (double)score >=
+ *           thr (it may exceed the capacity) and the first min(count, capacity) (map index y * mw + x, score) pairs, in
+ *           no particular order
+ * Forms 1 and 2 return FPM_E_SIZE, with nothing launched, where the plan did not admit the matrix-core form (the
+ * template level's shape, the parameters or FPM_TOP_MMA=0 keep the search on the other kernels).
+ * thr <= 0: the plan's layer score of the top layer.  thr > 0.01: that value instead, for forms 1 and 2 (the list
+ * threshold and the prefilter's constant follow it by the plan's own expression).  0 < thr <= 0.01 and a non-finite
+ * thr are FPM_E_INVALID_ARG.
+ * Sizes.  n_sources, n_angles, map_floats (the dense maps of one source: the sum of mw * mh over the angles) and
+ * list_cap (the list capacity in effect) are written by every successful call (each may be NULL).  A call with geom,
+ * maps and the three list outputs all NULL is the sizing call: it plans, launches nothing and writes the sizes and
+ * stats.
+ * Outputs.  geom: [n_angles][4] = bw, bh (the rotated canvas), mw, mh (the map; 0, 0 for an angle the search skips,
+ * whose jobs have no map and an empty list); geom_cap = the angles it holds.  maps (forms 0 and 1): [source][angle]
+ * dense f32, mw * mh each, n_sources * map_floats in all; maps_cap = the floats it holds.  list_count: [source][angle];
+ * list_index, list_value: [source][angle][list_cap]; list_slots = the entries each of the two holds (form 2; list_count
+ * holds n_sources * n_angles).  A capacity below the need: FPM_E_CAPACITY, nothing launched.  stats (may be NULL):
+ * FPM_TOP_MAPS_STATS entries: [0] the plan admitted the matrix-core form, [1] list capacity, [2] strip width sw, [3]
+ * rows per run (the tallest unit), [4] work units, [5] the kernel instantiation launch_top_mma takes (FPM_TOP_FORM_*),
+ * [6] the grid of the mode-1 launch, [7] block mode (s_BlockMax peaks); [1] .. [6] are 0 (and [5] -1) without the
+ * matrix-core form.
+ * State.  FPM_E_INVALID_ARG while a search is in flight, without staged sources, for a form outside 0 .. 2 and for a
+ * missing output of the form.  The learned template, the staged sources, the parameters, the last results and
+ * candidates, the model and the profile counters stay as they were; a following fpm_match_staged returns what it
+ * returns without the call.  Additive entry: FPM_ABI_VERSION is unchanged. */
+#define FPM_TOP_MAPS_STATS 8
+#define FPM_TOP_FORM_EXACT16 0   /* <8, 32>, template height 16 as a constant  */
+#define FPM_TOP_FORM_EXACT14 1   /* <7, 32>, template height 14 as a constant  */
+#define FPM_TOP_FORM_SMALL 2     /* <8, 32>, rows past the height masked       */
+#define FPM_TOP_FORM_LARGE 3     /* <16, 64>                                   */
+int fpm_op_top_maps(fpm_ctx* ctx, int32_t form, double thr, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats,
+                    int32_t* list_cap, int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap,
+                    int32_t* list_count, int32_t* list_index, float* list_value, int64_t list_slots, int32_t* stats);
 /* Learned-template introspection: number of pyramid levels, per-level size and statistics
  * (s_TemplData, DataStructures.h:16-55). */
 int fpm_template_info(const fpm_ctx* ctx, int32_t* levels, int32_t* border_color);

@@ -471,6 +471,10 @@ struct SearchStats {
     // rows of kTraceCols doubles = origin, layer, n3, imax, then (angle, score, mx, my, runner-up score of the
     // map) for j = 0..2, then the ROIs' ptLT in the layer's coordinates (the `lt * 2` getRotatedROI is called with)
     std::vector<double> trace;
+    // the top layer's score maps before the peak loop paints them (only when Matcher::keep_maps is set; a
+    // diagnostic): one per scored angle, with the angle's index in the angle list
+    struct TopMap { int angle_index, bw, bh; MatF map; };
+    std::vector<TopMap> top_maps;
 };
 static const int kTraceCols = 21;
 
@@ -604,6 +608,7 @@ public:
     double last_seconds = 0.0;
     SearchStats stats;
     bool trace = false;
+    bool keep_maps = false;
     int ccorr_mode = 0;   // TM_CCORR arithmetic: 0 = exact integer sum rounded once (parity), 1 = f32 DFT (above)
 
     Matcher() { fpm_params_default(&prm); }
@@ -1039,6 +1044,7 @@ public:
             Mat8 rot = warp_affine(spyr[L], m, bw, bh, T.border);
             MatF res;
             match_template(rot, L, false, res);
+            if (keep_maps) stats.top_maps.push_back({i, bw, bh, res});
             int px, py;
             double v, vmax;
             if (by_block) {
@@ -1301,6 +1307,19 @@ int orc_trace(void* h, double* out, int cap_rows) {
         std::memcpy(out + (size_t)i * orc::kTraceCols, &m->stats.trace[(size_t)i * orc::kTraceCols],
                     sizeof(double) * orc::kTraceCols);
     return n;
+}
+
+// top-layer score maps of the next matches (diagnostic), see SearchStats::top_maps: orc_top_map_count() maps, each
+// (res.w, res.h) f32 with its angle index and the rotated canvas's (bw, bh); out may be null to read the geometry
+void orc_set_keep_maps(void* h, int on) { ((orc::Matcher*)h)->keep_maps = on != 0; }
+int orc_top_map_count(void* h) { return (int)((orc::Matcher*)h)->stats.top_maps.size(); }
+int orc_top_map(void* h, int k, int* geom, float* out) {
+    auto* m = (orc::Matcher*)h;
+    if (k < 0 || k >= (int)m->stats.top_maps.size()) return FPM_E_INVALID_ARG;
+    const auto& t = m->stats.top_maps[k];
+    geom[0] = t.angle_index; geom[1] = t.bw; geom[2] = t.bh; geom[3] = t.map.w; geom[4] = t.map.h;
+    if (out) std::memcpy(out, t.map.px.data(), t.map.px.size() * sizeof(float));
+    return FPM_OK;
 }
 
 // The top layer's peak sequence on a given f32 map (TemplateMatcher.cpp:179-210; MFC MatchToolDlg.cpp:860-888):

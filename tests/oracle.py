@@ -45,6 +45,9 @@ def load(path: str = ORACLE_LIB):
     lib.orc_top_candidates.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     lib.orc_set_trace.argtypes = [C.c_void_p, C.c_int]
     lib.orc_trace.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+    lib.orc_set_keep_maps.argtypes = [C.c_void_p, C.c_int]
+    lib.orc_top_map_count.argtypes = [C.c_void_p]
+    lib.orc_top_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     lib.orc_template_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.orc_template_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -254,6 +257,22 @@ class OracleMatcher:
         for f, k in (("angle", 4), ("score", 5), ("x", 6), ("y", 7), ("second", 8)):
             out[f] = buf[:, k:19:5]
         out["lt"] = buf[:, 19:21]
+        return out
+
+    def set_keep_maps(self, on: bool = True):
+        self._lib.orc_set_keep_maps(self._h, 1 if on else 0)
+        return self
+
+    def top_maps(self):
+        """Top-layer score maps of the last match (after set_keep_maps), unpainted, one per scored angle in angle
+        order: [(angle_index, bw, bh, f32 map (bh - th + 1, bw - tw + 1))]."""
+        out = []
+        for k in range(self._lib.orc_top_map_count(self._h)):
+            g = (C.c_int * 5)()
+            assert self._lib.orc_top_map(self._h, k, g, None) == 0
+            m = np.zeros((g[4], g[3]), np.float32)
+            assert self._lib.orc_top_map(self._h, k, g, m.ctypes.data_as(C.POINTER(C.c_float))) == 0
+            out.append((g[0], g[1], g[2], m))
         return out
 
     def refine_roi(self, level_img: np.ndarray, layer: int, lt, angle: float, fold):

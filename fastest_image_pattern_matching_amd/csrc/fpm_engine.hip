@@ -914,6 +914,54 @@ void enqueue_top_split_maps(fpm_ctx* ctx) {
     }
 }
 
+// k_top_fused's dynamic LDS for the plan (its largest canvas and map), or 0 where the fused form cannot run: block
+// mode, a template level beyond k_ncc_tile's form, no job, or more LDS than the kernel's static arrays leave of the
+// default 64 KB launch limit (tests/test_gpu_parity.py::test_top_fused_lds_threshold runs canvases either side of it).
+// need (optional): the LDS the largest job asks for, whatever the limit
+size_t plan_top_fused_lds(const fpm_ctx* ctx, size_t* need = nullptr) {
+    const Plan& P = ctx->plan;
+    const TmplLevel& tt = ctx->tmpl[P.L];
+    if (need) *need = 0;
+    if (P.by_block || !ncc_tile_fits(tt.w, tt.h) || P.S * P.nang <= 0) return 0;
+    size_t lds = 0;
+    for (int a = 0; a < P.nang; ++a) lds = std::max(lds, top_fused_lds(P.top[a].bw, P.top[a].bh, tt.w, tt.h));
+    if (need) *need = lds;
+    return lds > top_fused_lds_limit() ? 0 : lds;
+}
+
+// The top layer's form as the search selects it: *fused_lds > 0 = k_top_fused with that much dynamic LDS (small
+// canvases with the plain peak path and enough (source, angle) jobs to fill the chip; FPM_TOP_FUSED=0 keeps the
+// three-kernel form, =1 forces the fused one whatever the job count), *use_mma = the matrix-core form (where the plan
+// admits it, except where the fused kernel applies; FPM_TOP_MMA=1 takes it there too), else the split chain.  Both
+// switches are read when the search is recorded (once per plan)
+void plan_top_choice(const fpm_ctx* ctx, size_t* fused_lds, bool* use_mma) {
+    const Plan& P = ctx->plan;
+    const char* top_env = getenv("FPM_TOP_FUSED");
+    const int top_mode = top_env ? atoi(top_env) : -1;
+    *fused_lds = 0;
+    if (top_mode != 0 && (P.S * P.nang >= kTopFusedMinJobs || top_mode == 1)) *fused_lds = plan_top_fused_lds(ctx);
+    const char* mma_env = getenv("FPM_TOP_MMA");
+    *use_mma = P.top_mma && (*fused_lds == 0 || (mma_env && atoi(mma_env) == 1));
+    if (*use_mma) *fused_lds = 0;
+}
+
+// The top-layer peak pass's arguments as the plan gives them (the launchers' own fields are set by the callers)
+NmsArgs plan_nms_args(const fpm_ctx* ctx) {
+    const Plan& P = ctx->plan;
+    const TmplLevel& tt = ctx->tmpl[P.L];
+    NmsArgs na{};
+    na.jobs = P.d_jobs.as<NmsJob>(P.off_nms);
+    na.peaks = P.d_peaks.as<Peak>();
+    na.counts = P.d_counts.as<int32_t>();
+    na.tw = tt.w; na.th = tt.h; na.cap = P.cap; na.by_block = P.by_block ? 1 : 0;
+    na.mfc = ctx->prm.semantics == FPM_SEMANTICS_MFC ? 1 : 0;
+    na.thr = P.layer_score[P.L]; na.overlap = ctx->prm.max_overlap;
+    na.lds_blocks = 0;
+    na.cand = nullptr; na.cand_cnt = nullptr; na.cand_cap = 0; na.cand_lds = 0; na.stamps = nullptr;
+    na.skey = nullptr; na.sdone = nullptr;
+    return na;
+}
+
 int enqueue_search(fpm_ctx* ctx) {
     Plan& P = ctx->plan;
     const int L = P.L, S = P.S, J = S * P.nang;
@@ -921,29 +969,17 @@ int enqueue_search(fpm_ctx* ctx) {
     hipStream_t st = ctx->stream;
     uint8_t* dsrc = ctx->d_src.as<uint8_t>();
     const SrcLevel& top = ctx->src[L];
-    const TmplLevel& tt = ctx->tmpl[L];
     P.step_layers = 0;   // (set again by the launches recorded below)
     P.top_lists = false;
     // small canvases with the plain peak path: the whole top layer as one kernel (k_top_fused), canvas and map in
     // LDS, when there are enough (source, angle) jobs to fill the chip: one workgroup runs a job's warp, map and
     // peak loop serially (33 us for a single Src7 source's 41 jobs against 24 us for the three split kernels; 75.5
     // against 106.4 us at 1763 jobs, profiles/r02_z/lat_r02_z.txt).  FPM_TOP_FUSED=0 keeps the three-kernel form,
-    // FPM_TOP_FUSED=1 forces the fused one whatever the job count (tests, profiling comparisons)
+    // FPM_TOP_FUSED=1 forces the fused one whatever the job count (tests, profiling comparisons); else the matrix-core
+    // top layer (k_top_mma + greedy peaks from its lists) where the plan admits it: plan_top_choice
     size_t fused_lds = 0;
-    const char* top_env = getenv("FPM_TOP_FUSED");   // read when the search is recorded (once per plan)
-    const int top_mode = top_env ? atoi(top_env) : -1;
-    if (!P.by_block && ncc_tile_fits(tt.w, tt.h) && J > 0 && (J >= kTopFusedMinJobs || top_mode == 1)) {
-        for (int a = 0; a < P.nang; ++a)
-            fused_lds = std::max(fused_lds, top_fused_lds(P.top[a].bw, P.top[a].bh, tt.w, tt.h));
-        // the dynamic LDS plus the kernel's static arrays (peaks, reduction slots, as compiled) within the default 64 KB
-        // launch limit (tests/test_gpu_parity.py::test_top_fused_lds_threshold runs canvases either side of it)
-        if (top_mode == 0 || fused_lds > top_fused_lds_limit()) fused_lds = 0;
-    }
-    // the matrix-core top layer (k_top_mma + greedy peaks from its lists) where the plan admits it, except where the
-    // fused small-canvas kernel applies; FPM_TOP_MMA=1 takes it there too (read when the search is recorded)
-    const char* mma_env = getenv("FPM_TOP_MMA");
-    const bool use_mma = P.top_mma && (fused_lds == 0 || (mma_env && atoi(mma_env) == 1));
-    if (use_mma) fused_lds = 0;
+    bool use_mma = false;
+    plan_top_choice(ctx, &fused_lds, &use_mma);
     int32_t* live[2] = {P.d_live.as<int32_t>(), P.d_live.as<int32_t>() + P.C};
     int32_t* livecnt = P.d_livecnt.as<int32_t>();
     CandInitArgs ca;   // the top peaks -> candidate states and the first live list (k_cand_init, or fused in k_nms)
@@ -967,23 +1003,14 @@ int enqueue_search(fpm_ctx* ctx) {
     // (L == stop == 1 also runs mode 1, behind the pyramid launch's zeroing)
     const bool pyr_zero = (top_init && L >= 1) || use_mma;   // (use_mma implies L >= 1: plan_top_mma)
     enqueue_pyramid(ctx, pyr_zero);
-    NmsArgs na{};
-    na.jobs = P.d_jobs.as<NmsJob>(P.off_nms);
-    na.peaks = P.d_peaks.as<Peak>();
-    na.counts = P.d_counts.as<int32_t>();
-    na.tw = tt.w; na.th = tt.h; na.cap = P.cap; na.by_block = P.by_block ? 1 : 0;
-    na.mfc = ctx->prm.semantics == FPM_SEMANTICS_MFC ? 1 : 0;
-    na.thr = P.layer_score[L]; na.overlap = ctx->prm.max_overlap;
-    na.lds_blocks = 0;
-    na.cand = nullptr; na.cand_cnt = nullptr; na.cand_cap = 0; na.cand_lds = 0; na.stamps = nullptr;
-    na.skey = nullptr; na.sdone = nullptr;
+    NmsArgs na = plan_nms_args(ctx);
     if (fused_lds > 0) {
         int64_t bytes = (int64_t)P.nang * top.w * top.h;
         for (int a = 0; a < P.nang; ++a) bytes += 4LL * P.map_w[a] * P.map_h[a];
         ProfScope ps(ctx, FPM_K_TOP_NCC, bytes * S);
         launch_top_fused(P.d_jobs.as<WarpJob>(P.off_warp), P.d_jobs.as<NccJob>(P.off_ncc), na, J, fused_lds,
                          pyr_zero ? nullptr : P.d_livecnt.as<int32_t>(), pyr_zero ? 0 : P.nzero, st,
-                         top_init ? &ca : nullptr, P.d_jobs.as<int32_t>(P.off_order));
+                         top_init ? &ca : nullptr, P.d_jobs.as<int32_t>(P.off_order), false);
         cand_fused = top_init;
     }
     if (use_mma) {
@@ -4220,6 +4247,123 @@ int fpm_op_top_maps(fpm_ctx* ctx, int32_t form, double thr, int32_t* n_sources, 
         HIP_TRY(hipMemcpyAsync(list_value, ta.cand_val, sizeof(float) * (size_t)lcap * J, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return FPM_OK;
+}
+
+// The fused top layer (k_top_fused) over the staged batch whatever the job count, by the plan's own job tables, job
+// order and peak arguments (plan_nms_args): once as the product instantiation, once as the map-writing one.  Neither
+// launch initialises candidates (ci = nullptr); the peaks and counts go to the operator's scratch, the maps to the
+// plan's map scratch (NccJob::out), which a search of this form never reads.
+int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats, int32_t* cap,
+                     int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap, fpm_peak* peaks, int32_t* counts,
+                     fpm_peak* dump_peaks, int32_t* dump_counts, int64_t peak_slots, int32_t* stats) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (!ctx->learned) { ctx->err = "template not learned"; return FPM_E_NOT_LEARNED; }
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (ctx->S <= 0 || !ctx->staged || !ctx->src_valid) { ctx->err = "top fused: no staged sources"; return FPM_E_INVALID_ARG; }
+    const bool sizing = !geom && !maps && !peaks && !counts && !dump_peaks && !dump_counts;
+    if (geom_cap < 0 || maps_cap < 0 || peak_slots < 0 ||
+        (!sizing && (!geom || !maps || !peaks || !counts || !dump_peaks || !dump_counts))) {
+        ctx->err = "bad top fused arguments";
+        return FPM_E_INVALID_ARG;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct ProfOff {   // the launches below are not the search's: the profile counters stay as they were
+        fpm_ctx* c; bool was;
+        explicit ProfOff(fpm_ctx* x) : c(x), was(x->prof) { c->prof = false; }
+        ~ProfOff() { c->prof = was; }
+    } prof_off(ctx);
+    int rc = build_plan(ctx);
+    if (rc != FPM_OK) return rc;
+    Plan& P = ctx->plan;
+    const int S = P.S, nang = P.nang, J = S * nang;
+    std::vector<size_t> dense_off(nang);
+    size_t dense = 0;
+    for (int a = 0; a < nang; ++a) { dense_off[a] = dense; dense += (size_t)P.map_w[a] * P.map_h[a]; }
+    if (n_sources) *n_sources = S;
+    if (n_angles) *n_angles = nang;
+    if (map_floats) *map_floats = (int64_t)dense;
+    if (cap) *cap = P.cap;
+    size_t need = 0;
+    const size_t lds = plan_top_fused_lds(ctx, &need);
+    if (stats) {
+        size_t chosen = 0;
+        bool use_mma = false;
+        plan_top_choice(ctx, &chosen, &use_mma);
+        std::fill(stats, stats + FPM_TOP_FUSED_STATS, 0);
+        stats[0] = (int32_t)need;
+        stats[1] = (int32_t)top_fused_static_lds(false);
+        stats[2] = (int32_t)top_fused_lds_limit();
+        stats[3] = top_fused_grid(J);
+        stats[4] = J;
+        stats[5] = P.cap;
+        stats[6] = chosen > 0 ? 1 : 0;
+        stats[7] = (int32_t)top_fused_static_lds(true);
+    }
+    if (lds == 0 && J > 0) {
+        ctx->err = "top fused: the plan cannot take the fused form (block mode, the template level or the LDS limit)";
+        return FPM_E_SIZE;
+    }
+    if (sizing) return FPM_OK;
+    const size_t slots = (size_t)J * P.cap;
+    if (geom_cap < nang || (uint64_t)maps_cap < (uint64_t)dense * S || (uint64_t)peak_slots < (uint64_t)slots) {
+        ctx->err = "top fused: output capacity below the sizing call's";
+        return FPM_E_CAPACITY;
+    }
+    for (int a = 0; a < nang; ++a) {
+        geom[4 * a + 0] = P.top[a].bw; geom[4 * a + 1] = P.top[a].bh;
+        geom[4 * a + 2] = P.map_w[a]; geom[4 * a + 3] = P.map_h[a];
+    }
+    if (J <= 0) return FPM_OK;
+    hipStream_t st = ctx->stream;
+    // scratch: per launch [J][cap] peaks and [J] counts, uploaded from the caller's arrays so that a slot no kernel
+    // writes comes back as the caller left it
+    const size_t o_peaks[2] = {0, round_up(sizeof(Peak) * slots, (size_t)256)};
+    const size_t o_counts[2] = {2 * o_peaks[1], 2 * o_peaks[1] + round_up(sizeof(int32_t) * J, (size_t)256)};
+    HIP_TRY(ctx->d_op_b.ensure(o_counts[1] + sizeof(int32_t) * J));
+    fpm_peak* hp_out[2] = {peaks, dump_peaks};
+    int32_t* hc_out[2] = {counts, dump_counts};
+    std::vector<Peak> hp[2];
+    for (int v = 0; v < 2; ++v) {
+        hp[v].resize(slots);
+        for (size_t k = 0; k < slots; ++k) {
+            Peak& q = hp[v][k];
+            q.x = hp_out[v][k].x; q.y = hp_out[v][k].y; q.score = hp_out[v][k].score; q.pad = 0;
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_peaks[v]), hp[v].data(), sizeof(Peak) * slots, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_op_b.as<char>(o_counts[v]), hc_out[v], sizeof(int32_t) * J, hipMemcpyHostToDevice, st));
+    }
+    rc = apply_polarity(ctx);   // as start_staged, ahead of the pyramid
+    if (rc != FPM_OK) return rc;
+    // a pixel the map-writing launch leaves out reads back as a NaN pattern
+    HIP_TRY(hipMemsetAsync(P.d_map.p, 0xff, sizeof(float) * P.map_floats * S, st));
+    // as the search without the fused candidate init: the pyramid launches zero nothing, block 0 of the top kernel does
+    enqueue_pyramid(ctx, false);
+    for (int v = 0; v < 2; ++v) {
+        NmsArgs na = plan_nms_args(ctx);
+        na.peaks = ctx->d_op_b.as<Peak>(o_peaks[v]);
+        na.counts = ctx->d_op_b.as<int32_t>(o_counts[v]);
+        launch_top_fused(P.d_jobs.as<WarpJob>(P.off_warp), P.d_jobs.as<NccJob>(P.off_ncc), na, J, lds,
+                         P.d_livecnt.as<int32_t>(), P.nzero, st, nullptr, P.d_jobs.as<int32_t>(P.off_order), v == 1);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<float> hm(P.map_floats * S);
+    HIP_TRY(hipMemcpyAsync(hm.data(), P.d_map.p, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
+    for (int v = 0; v < 2; ++v) {
+        HIP_TRY(hipMemcpyAsync(hp[v].data(), ctx->d_op_b.as<char>(o_peaks[v]), sizeof(Peak) * slots, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hc_out[v], ctx->d_op_b.as<char>(o_counts[v]), sizeof(int32_t) * J, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s)
+        for (int a = 0; a < nang; ++a)
+            std::copy_n(hm.data() + P.map_floats * s + P.map_off[a], (size_t)P.map_w[a] * P.map_h[a],
+                        maps + dense * s + dense_off[a]);
+    for (int v = 0; v < 2; ++v)
+        for (size_t k = 0; k < slots; ++k) {
+            fpm_peak& p = hp_out[v][k];
+            const Peak& q = hp[v][k];
+            p.x = q.x; p.y = q.y; p.score = q.score;
+        }
     return FPM_OK;
 }
 

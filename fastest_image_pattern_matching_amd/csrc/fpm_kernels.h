@@ -381,9 +381,13 @@ constexpr int kTopFusedMinJobs = 256;   // fewer jobs than CUs: the three split 
 // (zero / nzero are then 0: block 0's clearing would race with the other blocks' atomics)
 // order (optional): the job each workgroup takes, costliest angles first (fewer workgroups than resident slots are
 // left for the last round)
+// dump: the map-writing instantiation (fpm_op_top_fused): every job's LDS map, unpainted, also goes to NccJob::out; the
+// search passes false.  top_fused_static_lds: the kernel's static LDS as compiled (0 if the query fails)
 void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& a, int njobs_n, size_t lds,
-                      int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci = nullptr,
-                      const int32_t* order = nullptr);
+                      int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci, const int32_t* order,
+                      bool dump);
+size_t top_fused_static_lds(bool dump);
+int top_fused_grid(int njobs_n);   // the workgroups launch_top_fused starts for njobs_n jobs (FPM_GRID_TOP)
 // ---- the top layer on the matrix cores (k_top_mma): warp + TM_CCORR + CCOEFF_Denominator for every (source, angle)
 // job without materialising the rotated canvas or the map.  Work unit = (job, strip of output columns, run of output
 // rows); the host builds the unit list (top_mma_plan).

@@ -2116,7 +2116,10 @@ void launch_cand_init(const CandInitArgs& a, hipStream_t st) {
 // 106.4 for k_warp + k_ncc_tile + k_nms; round-3 ablations (a profiling build, since removed from the product) put
 // 21 us in the taps, 19 in the correlation, 3 in the peak loop.
 constexpr int kTopThreads = 256;   // k_top_fused workgroup (measured: 512 threads per job no faster)
-// one (source, angle) job of k_top_fused (returns when the job is done; the caller separates jobs by a barrier)
+// one (source, angle) job of k_top_fused (returns when the job is done; the caller separates jobs by a barrier).
+// DUMP = false is the product kernel; DUMP = true (fpm_op_top_fused only) also copies the finished LDS map, before any
+// peak is painted into it, to the job's dense map in HBM (NccJob::out) -- everything else is the same source
+template <bool DUMP>
 __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict__ wjobs,
                                               const NccJob* __restrict__ njobs, const NmsArgs& a,
                                               const CandInitArgs& ci, int ci_mode, uint32_t* tf_lds, float* sv,
@@ -2208,6 +2211,8 @@ __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict
         }
     }
     __syncthreads();
+    if constexpr (DUMP)   // (read-only on Mp: the first rectangle is painted behind wg_argmax's barriers)
+        for (int k = tid; k < n; k += kTopThreads) j.out[k] = Mp[k];
     // K5 (plain getNextMaxLoc, TemplateMatcher.cpp:197-212 / :1196-1206) on the LDS map
     Peak* out = a.peaks + (size_t)job * a.cap;
     const double ov = a.overlap;
@@ -2256,6 +2261,7 @@ __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict
 }
 
 // jobs k = blockIdx.x, + gridDim.x, ... in `order` (the grid may be smaller than the job count: FPM_GRID_TOP)
+template <bool DUMP>
 __global__ __launch_bounds__(kTopThreads) void k_top_fused(const WarpJob* __restrict__ wjobs,
                                                            const NccJob* __restrict__ njobs,
                                                            NmsArgs a, int32_t* zero, int nzero,
@@ -2270,7 +2276,7 @@ __global__ __launch_bounds__(kTopThreads) void k_top_fused(const WarpJob* __rest
         for (int i = threadIdx.x; i < nzero; i += kTopThreads) zero[i] = 0;
     for (int k = blockIdx.x; k < njobs_n; k += gridDim.x) {
         if (k != (int)blockIdx.x) __syncthreads();   // the previous job is done with the LDS
-        top_fused_job(order ? order[k] : k, wjobs, njobs, a, ci, ci_mode, tf_lds, sv, si, spk, &sbase);
+        top_fused_job<DUMP>(order ? order[k] : k, wjobs, njobs, a, ci, ci_mode, tf_lds, sv, si, spk, &sbase);
     }
 }
 
@@ -2282,6 +2288,7 @@ size_t top_fused_lds(int bw, int bh, int tw, int th) {
 
 // The dynamic LDS a k_top_fused job may use without raising the kernel's 64 KB default launch limit: 64 KB minus
 // the kernel's static LDS (peak list, reduction slots), read from the code object once per device
+// (the product instantiation's; launch_top_fused checks once that the map-writing one carries the same static LDS)
 size_t top_fused_lds_limit() {
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -2292,15 +2299,40 @@ size_t top_fused_lds_limit() {
     if (it != lim.end()) return it->second;
     hipFuncAttributes fa{};
     size_t stat = 8192;   // conservative if the query fails
-    if (hipFuncGetAttributes(&fa, (const void*)k_top_fused) == hipSuccess) stat = fa.sharedSizeBytes;
+    if (hipFuncGetAttributes(&fa, (const void*)k_top_fused<false>) == hipSuccess) stat = fa.sharedSizeBytes;
     const size_t l = stat < 65536 ? 65536 - stat : 0;
     lim[dev] = l;
     return l;
 }
 
+size_t top_fused_static_lds(bool dump) {
+    hipFuncAttributes fa{};
+    const void* f = dump ? (const void*)k_top_fused<true> : (const void*)k_top_fused<false>;
+    return hipFuncGetAttributes(&fa, f) == hipSuccess ? fa.sharedSizeBytes : 0;
+}
+
+// FPM_GRID_TOP: workgroup cap (a scheduling knob: the jobs loop; read when a search is recorded), 0 / unset: one
+// workgroup per job
+int top_fused_grid(int njobs_n) {
+    const char* gte = getenv("FPM_GRID_TOP");
+    const int grid_cap = gte && atoi(gte) > 0 ? atoi(gte) : 0;
+    return grid_cap > 0 && njobs_n > grid_cap ? grid_cap : njobs_n;
+}
+
 void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& a, int njobs_n, size_t lds,
-                      int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci, const int32_t* order) {
+                      int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci, const int32_t* order,
+                      bool dump) {
     if (njobs_n <= 0) return;
+    if (dump) {   // both instantiations declare the same arrays, so one LDS limit (top_fused_lds_limit) serves both
+        static std::once_flag once;
+        std::call_once(once, [] {
+            const size_t sp = top_fused_static_lds(false), sd = top_fused_static_lds(true);
+            if (sp == 0 || sp != sd) {
+                std::fprintf(stderr, "fpm: k_top_fused<true> and <false> differ in static LDS (%zu, %zu)\n", sd, sp);
+                std::abort();
+            }
+        });
+    }
     CandInitArgs cz{};
     const bool fuse = ci && a.cap <= kNmsInitCap;
     const int mode = !fuse ? 0 : (ci->refine == 0 ? 1 : (ci->refine == 2 ? 3 : 2));
@@ -2311,13 +2343,13 @@ void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& 
                      mode);
         std::abort();
     }
-    // FPM_GRID_TOP: workgroup cap (a scheduling knob: the jobs loop; read when a search is recorded), 0 / unset: one
-    // workgroup per job
-    const char* gte = getenv("FPM_GRID_TOP");
-    const int grid_cap = gte && atoi(gte) > 0 ? atoi(gte) : 0;
-    const int grid = grid_cap > 0 && njobs_n > grid_cap ? grid_cap : njobs_n;
-    hipLaunchKernelGGL(k_top_fused, dim3(grid), dim3(kTopThreads), lds, st, wjobs, njobs, a, zero, nzero,
-                       fuse ? *ci : cz, mode, order, njobs_n);
+    const int grid = top_fused_grid(njobs_n);
+    if (dump)
+        hipLaunchKernelGGL(k_top_fused<true>, dim3(grid), dim3(kTopThreads), lds, st, wjobs, njobs, a, zero, nzero,
+                           fuse ? *ci : cz, mode, order, njobs_n);
+    else
+        hipLaunchKernelGGL(k_top_fused<false>, dim3(grid), dim3(kTopThreads), lds, st, wjobs, njobs, a, zero, nzero,
+                           fuse ? *ci : cz, mode, order, njobs_n);
 }
 
 // ============================================================================================== K6+K7+K8

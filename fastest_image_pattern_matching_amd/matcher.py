@@ -1419,6 +1419,52 @@ class TemplateMatcher:
                             form=int(st[5]), map_grid=int(st[6]), by_block=int(st[7]))
         return out
 
+    TOP_FUSED_FILL = (-7, -7, -7.0)   # what top_fused leaves in a peak slot no kernel wrote (counts: -7)
+
+    def top_fused(self):
+        """fpm_op_top_fused: k_top_fused over the staged batch by the search's own plan, as the product kernel and as
+        its map-writing instantiation.  Returns a dict: 'geom' (n_angles, 4) int32 rows (bw, bh, mw, mh); 'maps'
+        [source][angle] f32 (mh, mw) arrays, unpainted; 'peaks' (n_sources, n_angles, cap) PEAK_DTYPE and 'counts'
+        (n_sources, n_angles) of the product launch, 'dump_peaks' / 'dump_counts' of the map-writing one -- every slot
+        from counts on holds TOP_FUSED_FILL; 'stats' dict as include/fpm.h lists them.  Raises ValueError carrying the
+        status as `.rc` and, for FPM_E_SIZE (the fused form cannot run), the stats as `.stats`."""
+        IP, FP, PP = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(L.Peak)
+        ns, na, cp, mf = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        st = np.zeros(L.TOP_FUSED_STATS, np.int32)
+        self._push()
+
+        def stats():
+            return dict(lds=int(st[0]), static_lds=int(st[1]), lds_limit=int(st[2]), grid=int(st[3]), jobs=int(st[4]),
+                        cap=int(st[5]), search_takes_it=int(st[6]), dump_static_lds=int(st[7]))
+
+        def call(geom, gcap, maps, mcap, pk, cnt, dpk, dcnt, slots):
+            rc = self._check(self._lib.fpm_op_top_fused(
+                self._ctx, C.byref(ns), C.byref(na), C.byref(mf), C.byref(cp), geom, gcap, maps, mcap, pk, cnt, dpk, dcnt,
+                slots, st.ctypes.data_as(IP)), "top_fused")
+            if rc != L.FPM_OK:
+                e = ValueError(f"fpm_op_top_fused failed with {rc}: {self.last_error()}")
+                e.rc = rc
+                e.stats = stats()
+                raise e
+
+        call(None, 0, None, 0, None, None, None, None, 0)
+        S, nang, cap, dense = ns.value, na.value, cp.value, mf.value
+        geom = np.zeros((max(nang, 1), 4), np.int32)
+        flat = np.zeros(max(S * dense, 1), np.float32)
+        pk = [np.zeros(max(S * nang * cap, 1), PEAK_DTYPE) for _ in range(2)]
+        cnt = [np.full(max(S * nang, 1), self.TOP_FUSED_FILL[0], np.int32) for _ in range(2)]
+        for p in pk:
+            p["x"], p["y"], p["score"] = self.TOP_FUSED_FILL
+        call(geom.ctypes.data_as(IP), nang, flat.ctypes.data_as(FP), S * dense, pk[0].ctypes.data_as(PP),
+             cnt[0].ctypes.data_as(IP), pk[1].ctypes.data_as(PP), cnt[1].ctypes.data_as(IP), S * nang * cap)
+        offs = np.concatenate([[0], np.cumsum(geom[:nang, 2].astype(np.int64) * geom[:nang, 3])])
+        return dict(geom=geom[:nang], stats=stats(),
+                    maps=[[flat[s * dense + offs[a]:s * dense + offs[a + 1]].reshape(geom[a, 3], geom[a, 2])
+                           for a in range(nang)] for s in range(S)],
+                    peaks=pk[0][:S * nang * cap].reshape(S, nang, cap), counts=cnt[0][:S * nang].reshape(S, nang),
+                    dump_peaks=pk[1][:S * nang * cap].reshape(S, nang, cap),
+                    dump_counts=cnt[1][:S * nang].reshape(S, nang))
+
     def overlap_filter(self, corners, scores, max_overlap: float, device: bool = True):
         """filterWithRotatedRect (TemplateMatcher.cpp:1133-1194) on rectangles given as rows (ltx, lty, rtx, rty, rbx,
         rby) with their scores, in the given order: (indices of the survivors, stats) -- stats as fpm_op_overlap_filter

@@ -714,6 +714,38 @@ int fpm_op_peaks(fpm_ctx* ctx, const float* const* maps, const int32_t* mw, cons
 int fpm_op_top_maps(fpm_ctx* ctx, int32_t form, double thr, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats,
                     int32_t* list_cap, int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap,
                     int32_t* list_count, int32_t* list_index, float* list_value, int64_t list_slots, int32_t* stats);
+/* The fused top layer (k_top_fused: the canvas warp, the NCC and the plain getNextMaxLoc loop of one (source, angle) job
+ * in one workgroup's LDS) over every job of the staged batch, and what it computed: the peaks of the product kernel,
+ * and the score maps before any peak is painted, which only a second, map-writing instantiation of the same source
+ * (template parameter DUMP) stores.  Needs a learned template (FPM_E_NOT_LEARNED) and staged sources.  The call builds,
+ * or reuses, the plan fpm_match_staged would use with the context's parameters, runs the search's pyramid launches and
+ * then launch_top_fused twice on the plan's own job tables and job order, whatever the job count (the search itself
+ * takes this form from 256 jobs on, or with FPM_TOP_FUSED=1): first the product instantiation, then the map-writing
+ * one, neither with the candidate initialisation.  The threshold is the plan's layer score of the top layer, the
+ * overlap the context's max_overlap, the capacity the plan's (max_pos + MATCH_CANDIDATE_NUM): nothing is restated.
+ * FPM_E_SIZE, with nothing launched, where the fused form cannot run: block mode (s_BlockMax peaks), a template level
+ * beyond k_ncc_tile's form (128 x 64), or a job whose canvas and map need more LDS than stats[2].
+ * Sizes.  n_sources, n_angles, map_floats (as fpm_op_top_maps) and cap (peak slots per job) are written by every call
+ * that planned (each may be NULL), stats too.  A call with geom, maps and the four peak outputs all NULL is the sizing
+ * call: it plans, launches nothing and writes the sizes and stats.
+ * Outputs.  geom, geom_cap, maps, maps_cap: as fpm_op_top_maps (the maps are the map-writing launch's; 0 x 0 and no
+ * map for an angle the search skips).  peaks: [source][angle][cap], counts: [source][angle], of the product launch;
+ * dump_peaks, dump_counts: the same of the map-writing launch.  All four are in/out: their contents are copied to
+ * the device before the launches and back after them, so a slot no kernel wrote (every peak slot from counts on)
+ * returns as the caller left it.  peak_slots = the entries each of peaks and dump_peaks holds (>= n_sources * n_angles
+ * * cap).  A capacity below the need: FPM_E_CAPACITY, nothing launched.  stats (may be NULL): FPM_TOP_FUSED_STATS
+ * entries: [0] the dynamic LDS of the launches in bytes (the largest job's need, also where it is refused), [1] the
+ * product kernel's static LDS, [2] the dynamic LDS limit (64 KB - [1]), [3] the grid (FPM_GRID_TOP caps it; the jobs
+ * loop), [4] jobs, [5] cap, [6] the search itself takes the fused form for this plan, [7] the map-writing kernel's
+ * static LDS (equal to [1]; checked once per process).
+ * State.  As fpm_op_top_maps: FPM_E_INVALID_ARG while a search is in flight, without staged sources and for a missing
+ * output; the template, the sources, the parameters, the last results and candidates, the model and the profile
+ * counters stay as they were; a following fpm_match_staged returns what it returns without the call.  Additive entry:
+ * FPM_ABI_VERSION is unchanged. */
+#define FPM_TOP_FUSED_STATS 8
+int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats, int32_t* cap,
+                     int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap, fpm_peak* peaks, int32_t* counts,
+                     fpm_peak* dump_peaks, int32_t* dump_counts, int64_t peak_slots, int32_t* stats);
 /* Learned-template introspection: number of pyramid levels, per-level size and statistics
  * (s_TemplData, DataStructures.h:16-55). */
 int fpm_template_info(const fpm_ctx* ctx, int32_t* levels, int32_t* border_color);

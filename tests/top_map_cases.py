@@ -1,4 +1,5 @@
-"""Scenes, shapes and oracle maps shared by tests/test_oracle_top_maps.py and tests/test_gpu_top_maps.py.
+"""Scenes, shapes and oracle maps shared by tests/test_oracle_top_maps.py, tests/test_gpu_top_maps.py,
+tests/test_oracle_top_fused.py and tests/test_gpu_top_fused.py.
 
 A case is a (scene, top template shape) pair; its oracle run (OracleMatcher.set_keep_maps: the top-layer score map of
 every scored angle, unpainted) is computed once per process and handed out read-only.
@@ -21,12 +22,14 @@ SHAPES = {
     (49, 16): (98, 32, 1024),   # widest one-row layout; no prefilter; <16, 64>
     (17, 32): (34, 64, 1024),   # tallest two-row layout; 47 ring rows in <16, 64>
     (60, 60): (120, 120, 4096),   # beyond both layouts: the split kernels only
+    (3, 30): (6, 60, 256),      # narrower than one 4-pixel word (k_top_fused's template masks)
 }
 SCORE = 0.6   # layer score of the top layer: 0.54
 
 
-def params(top, max_pos=3):
-    return dict(max_pos=max_pos, tolerance_angle=180.0, score=SCORE, min_reduce_area=SHAPES[top][2])
+def params(top, max_pos=3, score=SCORE, max_overlap=0.0):
+    return dict(max_pos=max_pos, tolerance_angle=180.0, score=score, max_overlap=max_overlap,
+                min_reduce_area=SHAPES[top][2])
 
 
 def noise_scene(top, seed=0, w=470, h=310):
@@ -54,19 +57,40 @@ def saturated_scene(top, w=470, h=310):
     return s, t
 
 
+def constant_template_scene(top, seed=0, w=470, h=310):
+    """The noise scene's source under a template of one value: every level is ResultEqual1."""
+    s, t = noise_scene(top, seed, w, h)
+    return s, np.full_like(t, 93)
+
+
+def constant_source_scene(top, w=470, h=310):
+    """A source of one value under the noise template: every window is flat."""
+    _, t = noise_scene(top, 0, w, h)
+    return np.full((h, w), 141, np.uint8), t
+
+
 @functools.lru_cache(maxsize=None)
-def case(kind, top, seed=0, w=470, h=310, max_pos=3):
+def case(kind, top, seed=0, w=470, h=310, max_pos=3, score=SCORE, max_overlap=0.0):
     """(source, template, params, oracle maps [(angle_index, bw, bh, map)], n_angles, OracleMatcher after its search);
-    everything read-only."""
-    s, t = saturated_scene(top, w, h) if kind == "saturated" else noise_scene(top, seed, w, h)
-    prm = params(top, max_pos)
+    everything read-only.  kind: "saturated", "constant_template", "constant_source", anything else the noise scene; a
+    narrow source (a top level narrower than the top template for some angles) is a matter of w and h."""
+    if kind == "saturated":
+        s, t = saturated_scene(top, w, h)
+    elif kind == "constant_template":
+        s, t = constant_template_scene(top, seed, w, h)
+    elif kind == "constant_source":
+        s, t = constant_source_scene(top, w, h)
+    else:
+        s, t = noise_scene(top, seed, w, h)
+    prm = params(top, max_pos, score, max_overlap)
     o = oracle.OracleMatcher().set(**prm)
     assert o.learnPattern(t)
     o.set_keep_maps()
     o.match(s)
     maps = o.top_maps()
     levels, _ = o.template_levels()
-    assert len(levels) == 2 and levels[1][0].shape == (top[1], top[0]) and not levels[1][4], (top, len(levels))
+    assert len(levels) == 2 and levels[1][0].shape == (top[1], top[0]), (top, len(levels))
+    assert levels[1][4] == (kind == "constant_template"), (kind, top)
     for _, _, _, m in maps:
         m.setflags(write=False)
     s.setflags(write=False)

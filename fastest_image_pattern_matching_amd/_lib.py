@@ -62,6 +62,9 @@ ALIGN_ADOPT = 2
 ALIGN_SINGULAR, ALIGN_STEP_CLAMPED, ALIGN_KEPT_START = 1, 2, 4
 ALIGN_MAX_AREA, ALIGN_MAX_SIDE, ALIGN_MAX_ITERS, ALIGN_MAX_STEP = 1 << 20, 4096, 8, 1024.0
 ALIGN_KERNEL_SYMBOL = "k_patch_align"
+# fpm_blobs_host: the summary's flag and the capacity rules
+BLOBS_TRUNCATED = 1
+BLOBS_MAX_CAP, BLOBS_MAX_SLOTS = 65536, 1 << 22
 
 
 class Params(C.Structure):
@@ -138,6 +141,20 @@ class AlignResult(C.Structure):
     _fields_ = [("lt_x", C.c_float), ("lt_y", C.c_float), ("angle", C.c_double), ("ssd_start", C.c_int64),
                 ("ssd", C.c_int64), ("n_used", C.c_int64), ("evals", C.c_int32), ("best_eval", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Blob(C.Structure):
+    """fpm_blob -- one connected component of an excess image (fpm_blobs_host)."""
+
+    _fields_ = [(n, C.c_int32) for n in ("hit", "seed", "area", "x0", "y0", "x1", "y1", "max_value")] + \
+               [(n, C.c_int64) for n in ("sum_value", "sum_x", "sum_y")]
+
+
+class BlobSummary(C.Structure):
+    """fpm_blob_summary -- one image's counts (fpm_blobs_host)."""
+
+    _fields_ = [("fg_pixels", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_components", "n_blobs", "n_returned", "largest_area", "flags", "reserved")]
 
 
 class RoiRecord(C.Structure):
@@ -270,6 +287,8 @@ SIGNATURES = {
                                    C.c_double, C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_double)]),
     "fpm_align_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_blobs_host": (C.c_int, [_U8P, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
+                                 C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -582,4 +582,100 @@ void subpix_estimation(const HostMatch* v, double* dx, double* dy, double* dangl
     *dangle = (t[6] * rhs[0] + t[7] * rhs[1] + t[8] * rhs[2]) * kR2D;
 }
 
+// ---- defect blobs (include/fpm.h, "defect blobs") ----
+const char* blobs_bad_args(int64_t n, int32_t level, int32_t connectivity, int32_t min_area, int32_t cap_per_hit) {
+    if (level < 0 || level > 254) return "level must be 0 .. 254";
+    if (connectivity != 4 && connectivity != 8) return "connectivity must be 4 or 8";
+    if (min_area < 1) return "min_area must be at least 1";
+    if (cap_per_hit < 1 || cap_per_hit > FPM_BLOBS_MAX_CAP) return "cap_per_hit must be 1 .. 65536";
+    if (n * cap_per_hit > FPM_BLOBS_MAX_SLOTS) return "more than 2^22 record slots (n x cap_per_hit)";
+    return nullptr;
+}
+
+void blobs_tail(fpm_blob* recs, int64_t m, int64_t missing, int64_t fg_pixels, int32_t n_components, int32_t largest_area,
+                int32_t min_area, int32_t cap, fpm_blob* out, fpm_blob_summary* summary) {
+    int64_t kept = 0;
+    for (int64_t i = 0; i < m; ++i)
+        if (recs[i].area >= min_area) recs[kept++] = recs[i];
+    std::sort(recs, recs + kept, [](const fpm_blob& a, const fpm_blob& b) { return a.seed < b.seed; });
+    const int64_t n_blobs = kept + missing, n_ret = std::min<int64_t>(kept, cap);
+    if (out != recs) std::copy(recs, recs + n_ret, out);
+    std::fill(out + n_ret, out + cap, fpm_blob{});
+    summary->fg_pixels = fg_pixels;
+    summary->n_components = n_components;
+    summary->n_blobs = (int32_t)n_blobs;
+    summary->n_returned = (int32_t)n_ret;
+    summary->largest_area = largest_area;
+    summary->flags = n_blobs > cap ? FPM_BLOBS_TRUNCATED : 0;
+    summary->reserved = 0;
+}
+
 }  // namespace fpm
+
+// Two-pass union-find over one image at a time: pass 1 links every foreground pixel to its left and upper neighbours
+// (the smaller index becomes the parent, so a root is its component's seed), pass 2 resolves every pixel to its root,
+// writes the label and adds the pixel to the root's record.
+int fpm_blobs_host(const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
+                   int32_t connectivity, int32_t min_area, fpm_blob_summary* summary, fpm_blob* out,
+                   int32_t cap_per_hit, int32_t* labels) {
+    if (!images || !summary || !out || n < 1 || n > 65535 || w < 1 || h < 1 || (int64_t)w * h > ((int64_t)1 << 22) ||
+        stride < (size_t)w || fpm::blobs_bad_args(n, level, connectivity, min_area, cap_per_hit))
+        return FPM_E_INVALID_ARG;
+    const int32_t npx = w * h;
+    const bool c8 = connectivity == 8;
+    std::vector<int32_t> parent((size_t)npx), slot((size_t)npx);
+    std::vector<fpm_blob> recs;
+    auto find = [&](int32_t x) {
+        while (parent[x] != x) x = parent[x] = parent[parent[x]];   // path halving; parent[x] < x off a root
+        return x;
+    };
+    auto unite = [&](int32_t a, int32_t b) {
+        a = find(a); b = find(b);
+        if (a < b) parent[b] = a;
+        else if (b < a) parent[a] = b;
+    };
+    for (int32_t i = 0; i < n; ++i) {
+        const uint8_t* img = images + (size_t)i * stride * h;
+        auto fg = [&](int32_t u, int32_t v) { return (int)img[(size_t)v * stride + u] > level; };
+        for (int32_t v = 0; v < h; ++v)
+            for (int32_t u = 0; u < w; ++u) {
+                const int32_t p = v * w + u;
+                parent[p] = fg(u, v) ? p : -1;
+                if (parent[p] < 0) continue;
+                if (u > 0 && parent[p - 1] >= 0) unite(p, p - 1);
+                if (v > 0) {
+                    if (parent[p - w] >= 0) unite(p, p - w);
+                    if (c8 && u > 0 && parent[p - w - 1] >= 0) unite(p, p - w - 1);
+                    if (c8 && u < w - 1 && parent[p - w + 1] >= 0) unite(p, p - w + 1);
+                }
+            }
+        recs.clear();
+        int64_t fg_pixels = 0;
+        int32_t largest = 0;
+        for (int32_t v = 0; v < h; ++v)
+            for (int32_t u = 0; u < w; ++u) {
+                const int32_t p = v * w + u;
+                int32_t* lab = labels ? labels + (size_t)i * npx + p : nullptr;
+                if (parent[p] < 0) { if (lab) *lab = 0; continue; }
+                const int32_t r = find(p);   // r <= p: a root is met first, in row-major order, as its own pixel
+                parent[p] = r;
+                if (r == p) {
+                    slot[p] = (int32_t)recs.size();
+                    recs.push_back(fpm_blob{i, p, 0, u, v, u, v, 0, 0, 0, 0});
+                }
+                fpm_blob& b = recs[(size_t)slot[r]];
+                const int32_t e = img[(size_t)v * stride + u];
+                b.area++;
+                b.x0 = std::min(b.x0, u); b.y0 = std::min(b.y0, v);
+                b.x1 = std::max(b.x1, u); b.y1 = std::max(b.y1, v);
+                b.max_value = std::max(b.max_value, e);
+                b.sum_value += e; b.sum_x += u; b.sum_y += v;
+                fg_pixels++;
+                if (lab) *lab = r + 1;
+            }
+        for (const fpm_blob& b : recs) largest = std::max(largest, b.area);
+        fpm::blobs_tail(recs.data(), (int64_t)recs.size(), 0, fg_pixels, (int32_t)recs.size(), largest, min_area,
+                        cap_per_hit, out + (size_t)i * cap_per_hit, summary + i);
+    }
+    return FPM_OK;
+}

@@ -3,6 +3,7 @@
 #include <functional>
 #include <vector>
 
+#include "../../include/fpm.h"
 #include "fpm_geom.h"
 
 namespace fpm {
@@ -42,5 +43,14 @@ int host_thread_count();   // threads host_parallel uses: FPM_HOST_THREADS, else
 // wake the pool's workers now and keep them spinning for `us` microseconds, so that a host tail expected after a device
 // wait starts without the wake-up latency of sleeping threads
 void host_pool_warm(int us);
+// The tail of a blob entry (include/fpm.h, "defect blobs"), for one image: of the m candidate records in recs keep those
+// with area >= min_area, sort them by seed, hand the first min(kept, cap) to out (out may be recs itself) with zeroed
+// records behind them up to cap, and fill the summary.  missing = qualifying components that have no record in recs
+// (0 for fpm_blobs_host, which passes every component; an entry with bounded record slots passes its overshoot); they
+// count in n_blobs.  One function, so that every entry ends in the same filter, order, truncation and flags.
+void blobs_tail(fpm_blob* recs, int64_t m, int64_t missing, int64_t fg_pixels, int32_t n_components, int32_t largest_area,
+                int32_t min_area, int32_t cap, fpm_blob* out, fpm_blob_summary* summary);
+// the argument rules the blob entries share; nullptr = fine, else what is wrong
+const char* blobs_bad_args(int64_t n, int32_t level, int32_t connectivity, int32_t min_area, int32_t cap_per_hit);
 
 }  // namespace fpm

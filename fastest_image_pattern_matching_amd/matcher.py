@@ -364,6 +364,56 @@ def model_derive(n: int, total: int, total_sq: int, abs_threshold: int = 8, k: f
     return mean.value, lo.value, hi.value
 
 
+# -- defect blobs (fpm_blobs_host) --------------------------------------------------------------------------------------
+# one row per component / per hit: fpm_blob and fpm_blob_summary, field for field
+BLOB_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Blob._fields_], align=True)
+BLOB_SUMMARY_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.BlobSummary._fields_], align=True)
+assert BLOB_DTYPE.itemsize == C.sizeof(L.Blob) == 56 and BLOB_SUMMARY_DTYPE.itemsize == C.sizeof(L.BlobSummary) == 32
+
+
+def _blob_images(images):
+    """(n, h, w) uint8, C-contiguous, from one (h, w) image or a stack of them."""
+    a = np.ascontiguousarray(images, np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.size == 0:
+        raise ValueError("images: a (h, w) or (n, h, w) uint8 array with at least one pixel expected")
+    return a
+
+
+def _blob_buffers(n, h, w, cap, labels):
+    if not 1 <= int(cap) <= L.BLOBS_MAX_CAP or n * int(cap) > L.BLOBS_MAX_SLOTS:
+        raise ValueError(f"cap {cap!r}: 1 .. 65536 with n x cap <= 2^22 expected")
+    summary = np.zeros(n, BLOB_SUMMARY_DTYPE)
+    recs = np.zeros((n, int(cap)), BLOB_DTYPE)
+    lab = np.zeros((n, h, w), np.int32) if labels else None
+    plab = lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None
+    return summary, recs, lab, plab
+
+
+def _blob_result(summary, recs, lab, labels):
+    blobs = [recs[i, :summary["n_returned"][i]].copy() for i in range(len(summary))]
+    return (summary, blobs, lab) if labels else (summary, blobs)
+
+
+def blobs_host(images, level: int = 0, min_area: int = 4, connectivity: int = 8, cap: int = 64, labels: bool = False):
+    """fpm_blobs_host: the connected components of the pixels above ``level`` in each of the uint8 ``images`` ((h, w)
+    or (n, h, w)) -- the excess images last_inspect(image=True) returns, for one -- on the host (no device), by the
+    contract in include/fpm.h: ``(summary, blobs)`` with ``summary`` a BLOB_SUMMARY_DTYPE array, one row per image,
+    and ``blobs`` one BLOB_DTYPE array per image, the components of at least ``min_area`` pixels in ascending seed
+    (the smallest row-major index of the component), at most ``cap`` of them (the first by seed).  ``labels=True``: a
+    third item, int32 (n, h, w), seed + 1 per foreground pixel and 0 elsewhere."""
+    a = _blob_images(images)
+    n, h, w = a.shape
+    summary, recs, lab, plab = _blob_buffers(n, h, w, cap, labels)
+    rc = L.load().fpm_blobs_host(L.u8ptr(a), n, w, h, w, int(level), int(connectivity), int(min_area),
+                                 summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                 recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), plab)
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_blobs_host failed with {rc}")
+    return _blob_result(summary, recs, lab, labels)
+
+
 # -- pose alignment (fpm_align_*): least-squares polish of every hit's pose against the template ----------------------
 # one row per hit: fpm_align_sums / fpm_align_result, field for field
 ALIGN_SUMS_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.AlignSums._fields_], align=True)

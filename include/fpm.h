@@ -530,6 +530,60 @@ int fpm_align_update(int32_t src_w, int32_t src_h, const fpm_patch_rect* rect, f
  * source pixels read + template pixels read. */
 int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
 
+/* --- defect blobs: connected components of an excess image (no reference equivalent) ----------------------------------
+ * fpm_last_inspect gives per hit two counts, a sum and ONE box around every pixel that left its interval: forty isolated
+ * one-pixel excesses and one 40-pixel scratch are the same record, two defects in opposite corners one box the size of
+ * the part.  The step after it segments the excess image into connected regions, drops those below a minimum area and
+ * reports each with its area, box, centroid sums and strength.  This block states that contract and gives its host
+ * entry, fpm_blobs_host, which takes the images fpm_last_inspect / fpm_inspect_at write (or any u8 images).  Entries
+ * that label where the excess images lie, on the device, are not part of the library yet.
+ * Foreground.  The input is a w x h image of u8 values e(u, v) and a level t = 0 .. 254; pixel (u, v) is foreground iff
+ * e(u, v) > t.
+ * Connectivity.  4 (edge neighbours) or 8 (edge and corner neighbours); a component is a maximal connected set of
+ * foreground pixels.
+ * Name.  A component's seed is the smallest row-major index v * w + u of its pixels (w * h <= 2^22: an int32).  It is
+ * unique per component and independent of any schedule.  In the label image a pixel carries seed + 1, background 0.
+ * Record: fpm_blob, 56 bytes, no padding, exact integers.  Per-image summary: fpm_blob_summary, 32 bytes, no padding.
+ * Filter, order, capacity.  min_area >= 1; cap_per_hit = 1 .. 65536 with n * cap_per_hit <= 2^22.  A component
+ * QUALIFIES when area >= min_area.  Records come image by image in call order, those of image i from
+ * out[i * cap_per_hit] on, in ascending seed; the records behind the image's n_returned are zero-filled.  When n_blobs
+ * <= cap_per_hit the output is fully determined.  When it is larger the call is still FPM_OK, the image carries
+ * FPM_BLOBS_TRUNCATED, n_blobs is the true count, and cap_per_hit records come back, each the exact record of a distinct
+ * qualifying component, in ascending seed: fpm_blobs_host returns the first cap_per_hit by seed (an entry that draws
+ * its record slots in parallel may return any cap_per_hit of them).  Components below min_area use no capacity.
+ * Label image (labels, may be NULL): dense int32 [n][h][w], seed + 1 of the pixel's component for every foreground
+ * pixel, filtered or not, 0 elsewhere.
+ * Errors.  connectivity other than 4 or 8, level outside 0 .. 254, min_area < 1, cap_per_hit outside its range, a null
+ * image, summary or record pointer, n outside 1 .. 65535, w or h < 1, w * h > 2^22, stride < w: FPM_E_INVALID_ARG,
+ * nothing written.  Additive entry: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_blob {
+    int32_t hit;                 /* index of the image / hit within the call                         */
+    int32_t seed;                /* smallest row-major index v * w + u of the component               */
+    int32_t area;                /* pixels                                                           */
+    int32_t x0, y0, x1, y1;      /* inclusive box, image (rectangle) coordinates                     */
+    int32_t max_value;           /* max e over the component                                         */
+    int64_t sum_value;           /* sum e                                                            */
+    int64_t sum_x, sum_y;        /* sum u, sum v: the centroid is (sum_x / area, sum_y / area)       */
+} fpm_blob;
+typedef struct fpm_blob_summary {
+    int64_t fg_pixels;           /* foreground pixels                                                */
+    int32_t n_components;        /* all components, before the area filter                           */
+    int32_t n_blobs;             /* components with area >= min_area (the true count, may exceed cap) */
+    int32_t n_returned;          /* min(n_blobs, cap_per_hit)                                        */
+    int32_t largest_area;        /* over all components, 0 when there is none                        */
+    int32_t flags;               /* FPM_BLOBS_TRUNCATED when n_blobs > cap_per_hit                    */
+    int32_t reserved;            /* 0 */
+} fpm_blob_summary;
+#define FPM_BLOBS_TRUNCATED 1
+#define FPM_BLOBS_MAX_CAP 65536          /* cap_per_hit */
+#define FPM_BLOBS_MAX_SLOTS (1 << 22)    /* n * cap_per_hit */
+
+/* host only, no context: n u8 images of one size (image i at images + i * stride * h, rows stride >= w apart), labelled
+ * by a two-pass union-find, then filtered, sorted by seed and cut to cap_per_hit. */
+int fpm_blobs_host(const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
+                   int32_t connectivity, int32_t min_area, fpm_blob_summary* summary, fpm_blob* out,
+                   int32_t cap_per_hit, int32_t* labels);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent

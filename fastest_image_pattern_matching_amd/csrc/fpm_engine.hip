@@ -121,7 +121,7 @@ struct Plan {
     // device buffers owned by the plan
     DevBuf d_ncand;                            // s_BlockMax candidate lists (k_nms_blocks -> k_nms_fast)
     DevBuf d_canvas, d_map, d_bmax, d_bloc, d_jobs, d_nodes, d_top, d_topn, d_peaks, d_counts, d_state,
-        d_live, d_livecnt, d_rec, d_rowsum, d_wsum, d_wsq, d_tab, d_roi, d_tdesc, d_state2, d_rec2;
+        d_live, d_livecnt, d_rec, d_rowsum, d_wtot, d_wtotq, d_wedge, d_tab, d_roi, d_tdesc, d_state2, d_rec2;
     int tabw = 0, tabh = 0, roi_pitch = 0, tdesc_stride = 1;
     size_t roi_stride = 0;
     int slot_cap = 0;                          // ROIs per refinement round (bounded scratch)
@@ -131,7 +131,7 @@ struct Plan {
     char* h_dev = nullptr;   // device-side address of h_out (k_pack writes it over PCIe)
     void release() {
         for (DevBuf* b : {&d_tmu, &d_tcandv, &d_ncand, &d_canvas, &d_map, &d_bmax, &d_bloc, &d_jobs, &d_nodes, &d_top, &d_topn, &d_peaks,
-                          &d_counts, &d_state, &d_live, &d_livecnt, &d_rec, &d_rowsum, &d_wsum, &d_wsq, &d_tab, &d_roi, &d_tdesc, &d_state2, &d_rec2})
+                          &d_counts, &d_state, &d_live, &d_livecnt, &d_rec, &d_rowsum, &d_wtot, &d_wtotq, &d_wedge, &d_tab, &d_roi, &d_tdesc, &d_state2, &d_rec2})
             b->release();
         h_out.release();
         valid = false;
@@ -184,8 +184,8 @@ struct fpm_ctx {
     uint64_t plan_gen = ~0ull;
     // op scratch
     DevBuf d_op_a, d_op_b, d_op_job;
-    // fpm_op_refine's per-ROI scratch (the plan's d_tab .. d_wsq belong to the recorded search)
-    DevBuf d_rf_tab, d_rf_tdesc, d_rf_roi, d_rf_rowsum, d_rf_wsum, d_rf_wsq;
+    // fpm_op_refine's per-ROI scratch (the plan's d_tab .. d_wedge belong to the recorded search)
+    DevBuf d_rf_tab, d_rf_tdesc, d_rf_roi, d_rf_rowsum, d_rf_wtot, d_rf_wtotq, d_rf_wedge;
     // filterWithRotatedRect on the device (overlap_filter_device): rectangles + counters; staging and mapped outputs
     DevBuf d_ov;
     PinBuf h_ov_in, h_ov_out;
@@ -370,14 +370,15 @@ SrcLevel level_layout(int w, int h) {
 // reads whole 16-row groups, up to 15 rows past a box (k_roi_warp3), i.e. past the last image's spare row
 size_t level_slab_slack(int pitch0) { return 16 * (size_t)pitch0 + 256; }
 
-// Per-ROI refinement scratch (tables, tile descriptors, sampled ROI, row sums, window partials) sized for the largest
+// Per-ROI refinement scratch (tables, tile descriptors, sampled ROI, row sums, the window sums' band totals
+// and edge rows) sized for the largest
 // of the template levels lv[0 .. nlv).
 struct RoiScratchDims {
     int tabw = 1, tabh = 1, roi_pitch = 1, tdesc_stride = 1;
-    size_t roi_stride = 0, max_rows = 1, max_chunks = 1;
+    size_t roi_stride = 0, max_rows = 1, max_bands = 1;
     size_t per_roi() const {
         return sizeof(int32_t) * 2 * (tabw + tabh) + sizeof(int4) * tdesc_stride + roi_stride + max_rows * 49 * 4 +
-               max_chunks * 49 * 12;
+               max_bands * 7 * 12 + kRoiEdgeWords * 4;
     }
 };
 RoiScratchDims roi_scratch_dims(const TmplLevel* lv, int nlv) {
@@ -385,9 +386,8 @@ RoiScratchDims roi_scratch_dims(const TmplLevel* lv, int nlv) {
     int max_w = 1;
     for (int l = 0; l < nlv; ++l) {
         d.tdesc_stride = std::max(d.tdesc_stride, roi_tiles_for(lv[l].w, lv[l].h));
-        const int rc = roi_pick_rc(lv[l].w, lv[l].h);
         d.max_rows = std::max(d.max_rows, (size_t)lv[l].h);
-        d.max_chunks = std::max(d.max_chunks, (size_t)(lv[l].h + rc - 1) / rc);
+        d.max_bands = std::max(d.max_bands, (size_t)roi_bands(lv[l].h));
         max_w = std::max(max_w, lv[l].w);
         d.roi_stride = std::max(d.roi_stride, roi_tiles_bytes(lv[l].w, lv[l].h));
     }
@@ -397,13 +397,14 @@ RoiScratchDims roi_scratch_dims(const TmplLevel* lv, int nlv) {
     return d;
 }
 hipError_t roi_scratch_ensure(const RoiScratchDims& d, size_t slots, DevBuf& tab, DevBuf& tdesc, DevBuf& roi,
-                              DevBuf& rowsum, DevBuf& wsum, DevBuf& wsq) {
+                              DevBuf& rowsum, DevBuf& wtot, DevBuf& wtotq, DevBuf& wedge) {
     hipError_t e = tab.ensure(slots * 2 * (d.tabw + d.tabh) * sizeof(int32_t));
     if (e == hipSuccess) e = tdesc.ensure(slots * d.tdesc_stride * sizeof(int4));
     if (e == hipSuccess) e = roi.ensure(slots * d.roi_stride);
     if (e == hipSuccess) e = rowsum.ensure(slots * round_up(d.max_rows * 49, (size_t)4) * 4);
-    if (e == hipSuccess) e = wsum.ensure(slots * d.max_chunks * 49 * 4);
-    if (e == hipSuccess) e = wsq.ensure(slots * d.max_chunks * 49 * 8);
+    if (e == hipSuccess) e = wtot.ensure(slots * d.max_bands * 7 * 4);
+    if (e == hipSuccess) e = wtotq.ensure(slots * d.max_bands * 7 * 8);
+    if (e == hipSuccess) e = wedge.ensure(slots * kRoiEdgeWords * 4);
     return e;
 }
 
@@ -700,7 +701,7 @@ int build_plan(fpm_ctx* ctx) {
     // the prologue-stepped run of small layers (below) alternates state and records between two buffers each
     HIP_TRY(P.d_state2.ensure(sizeof(CandState) * (size_t)P.C));
     HIP_TRY(P.d_rec2.ensure(sizeof(RoiRecord) * (size_t)P.C * P.n3));
-    {   // refinement scratch per ROI (tables, sampled ROI, row sums, window partials); bounded, rounds cover the rest
+    {   // refinement scratch per ROI (tables, sampled ROI, row sums, window band totals and edge rows); bounded, rounds cover the rest
         const RoiScratchDims rd = roi_scratch_dims(ctx->tmpl.data(), L);
         P.tdesc_stride = rd.tdesc_stride;
         P.roi_pitch = rd.roi_pitch;
@@ -725,12 +726,12 @@ int build_plan(fpm_ctx* ctx) {
         P.slot_cap = (int)std::max<size_t>((size_t)P.n3, std::min(want, budget / per_roi) / P.n3 * P.n3);
         for (;;) {
             const hipError_t e = roi_scratch_ensure(rd, (size_t)P.slot_cap, P.d_tab, P.d_tdesc, P.d_roi, P.d_rowsum,
-                                                    P.d_wsum, P.d_wsq);
+                                                    P.d_wtot, P.d_wtotq, P.d_wedge);
             if (e == hipSuccess) break;
             (void)hipGetLastError();   // clear the sticky allocation error
             if (e != hipErrorOutOfMemory || P.slot_cap <= P.n3) HIP_TRY(e);
             P.d_tab.release(); P.d_tdesc.release(); P.d_roi.release();
-            P.d_rowsum.release(); P.d_wsum.release(); P.d_wsq.release();
+            P.d_rowsum.release(); P.d_wtot.release(); P.d_wtotq.release(); P.d_wedge.release();
             P.slot_cap = std::max(P.n3, P.slot_cap / 2 / P.n3 * P.n3);
         }
     }
@@ -1110,8 +1111,6 @@ int enqueue_search(fpm_ctx* ctx) {
         ra.tmpl8 = ctx->d_tmpl8.as<int8_t>() + tl.off8; ra.tp8 = tl.p8; ra.nk = (tl.w + 63) / 64;
         ra.tsum = ctx->d_tsum.as<int32_t>() + tl.tsum_off;
         ra.n3 = P.n3;
-        ra.rc = roi_pick_rc(tl.w, tl.h);
-        ra.nchunk = (tl.h + ra.rc - 1) / ra.rc;
         ra.fold = ctx->prm.use_simd ? 1 : 0;
         ra.equal1 = tl.equal1 ? 1 : 0;
         ra.per_source = P.nang * P.cap;
@@ -1125,8 +1124,9 @@ int enqueue_search(fpm_ctx* ctx) {
         ra.tdesc = P.d_tdesc.as<int4>(); ra.tdesc_stride = P.tdesc_stride;
         ra.roi = P.d_roi.as<uint8_t>(); ra.roi_pitch = roi_pitch_for(tl.w); ra.roi_stride = P.roi_stride;
         ra.rowsum = P.d_rowsum.as<uint32_t>();
-        ra.wsum = P.d_wsum.as<uint32_t>();
-        ra.wsq = P.d_wsq.as<uint64_t>();
+        ra.wtot = P.d_wtot.as<uint32_t>();
+        ra.wtotq = P.d_wtotq.as<uint64_t>();
+        ra.wedge = P.d_wedge.as<uint32_t>();
         ra.rec = P.d_rec.as<RoiRecord>();
         ra.step = l > stop ? 1 : 0;   // candidate step fused into k_roi_eval (the stop layer is decided on the host)
         ra.mark_reached0 = l - 1 == stop ? 1 : 0;
@@ -1729,7 +1729,7 @@ int complete_staged(fpm_ctx* ctx, std::vector<std::vector<fpm_result>>& results,
                 ctx->kp[FPM_K_ROI_SMALL].bytes += rois * (foot + tmpl + 49 * 4);
                 continue;
             }
-            // the sampled ROI, row sums and window partials are this design's scratch, not §8(d) traffic: the
+            // the sampled ROI, row sums and window band totals are this design's scratch, not §8(d) traffic: the
             // sampling kernel is charged the footprint read, the correlation the template, the evaluation the scores
             ctx->kp[FPM_K_ROI_WARP].bytes += rois * foot;
             ctx->kp[FPM_K_ROI_CORR].bytes += rois * tmpl;
@@ -2830,7 +2830,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->plan.release();
     ctx->d_tmpl.release(); ctx->d_tmpl8.release(); ctx->d_tsum.release(); ctx->d_src.release();
     ctx->d_op_a.release(); ctx->d_op_b.release(); ctx->d_op_job.release();
-    for (DevBuf* b : {&ctx->d_rf_tab, &ctx->d_rf_tdesc, &ctx->d_rf_roi, &ctx->d_rf_rowsum, &ctx->d_rf_wsum, &ctx->d_rf_wsq})
+    for (DevBuf* b : {&ctx->d_rf_tab, &ctx->d_rf_tdesc, &ctx->d_rf_roi, &ctx->d_rf_rowsum, &ctx->d_rf_wtot, &ctx->d_rf_wtotq, &ctx->d_rf_wedge})
         b->release();
     ctx->d_ov.release(); ctx->h_ov_in.release(); ctx->h_ov_out.release();
     ctx->d_imgtab.release(); ctx->h_imgtab.release();
@@ -3917,7 +3917,7 @@ int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int
     const RoiScratchDims rd = roi_scratch_dims(&tl, 1);
     if (!small)
         HIP_TRY(roi_scratch_ensure(rd, (size_t)slot_cap, ctx->d_rf_tab, ctx->d_rf_tdesc, ctx->d_rf_roi, ctx->d_rf_rowsum,
-                                   ctx->d_rf_wsum, ctx->d_rf_wsq));
+                                   ctx->d_rf_wtot, ctx->d_rf_wtotq, ctx->d_rf_wedge));
     RoiArgs ra{};
     ra.level = ctx->d_op_a.as<uint8_t>(); ra.level_stride = lv.img_bytes;
     ra.W = lv.w; ra.H = lv.h; ra.P = lv.pitch;
@@ -3925,8 +3925,6 @@ int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int
     ra.tmpl8 = ctx->d_tmpl8.as<int8_t>() + tl.off8; ra.tp8 = tl.p8; ra.nk = (tl.w + 63) / 64;
     ra.tsum = ctx->d_tsum.as<int32_t>() + tl.tsum_off;
     ra.n3 = n3;
-    ra.rc = roi_pick_rc(tl.w, tl.h);
-    ra.nchunk = (tl.h + ra.rc - 1) / ra.rc;
     ra.fold = fold ? 1 : 0;
     ra.equal1 = tl.equal1 ? 1 : 0;
     ra.per_source = n;
@@ -3939,8 +3937,9 @@ int fpm_op_refine(fpm_ctx* ctx, const uint8_t* const* levels, int32_t count, int
     ra.tdesc = ctx->d_rf_tdesc.as<int4>(); ra.tdesc_stride = rd.tdesc_stride;
     ra.roi = ctx->d_rf_roi.as<uint8_t>(); ra.roi_pitch = roi_pitch_for(tl.w); ra.roi_stride = rd.roi_stride;
     ra.rowsum = ctx->d_rf_rowsum.as<uint32_t>();
-    ra.wsum = ctx->d_rf_wsum.as<uint32_t>();
-    ra.wsq = ctx->d_rf_wsq.as<uint64_t>();
+    ra.wtot = ctx->d_rf_wtot.as<uint32_t>();
+    ra.wtotq = ctx->d_rf_wtotq.as<uint64_t>();
+    ra.wedge = ctx->d_rf_wedge.as<uint32_t>();
     ra.rec = ctx->d_op_b.as<RoiRecord>(o_rec);
     ra.step = 0;   // records only: no candidate step, no prev_rec prologue, no next-layer tables
     const bool want_px = roi_pixels && !small && !tl.equal1;

@@ -106,8 +106,6 @@ struct RoiArgs {
     int32_t nk;              // ceil(tw / 64): MFMA k-steps per row
     const int32_t* tsum;     // per template row: sum of T (u8)
     int32_t n3;              // refinement angles per candidate (1 or 3)
-    int32_t rc;              // template rows per correlation chunk
-    int32_t nchunk;          // ceil(th / rc)
     int32_t fold;            // use_simd
     int32_t equal1;
     int32_t per_source;      // candidates per source (nang * cap)
@@ -127,8 +125,13 @@ struct RoiArgs {
     size_t roi_stride;
     int32_t nparts;          // the fused experiment only (scripts/roi_fused.hip): runs of bands per ROI
     uint32_t* rowsum;        // [slot][th][49] exact int32 per-row dot products
-    uint32_t* wsum;          // [slot][nchunk][49] window-sum partials of I
-    uint64_t* wsq;           // [slot][nchunk][49] window-sum partials of I^2
+    // the window sums of the normalisation, S(dy, dx) = sum_{t < th} W[t + dy][dx] (W[r][dx]: the sum of I, or of I^2,
+    // over the window [dx, dx + tw) of ROI row r), leave k_roi_corr as band totals and edge rows and are rebuilt by
+    // k_roi_eval:  S(dy, dx) = sum_bands wtot[band][dx] - sum_{r < dy} W[r][dx] + sum_{r < dy} W[th + r][dx]
+    // (integers throughout; holds for every th >= 1, also th < 6 where the head and tail rows overlap)
+    uint32_t* wtot;          // [slot][nband][7] sum of W over the band's own template rows 32 band .. 32 band + rb - 1 (I)
+    uint64_t* wtotq;         // [slot][nband][7] the same of I^2; nband = ceil(th / 32)
+    uint32_t* wedge;         // [slot][2][12][7] W of ROI rows 0 .. 5 (band 0) and th .. th + 5 (the last band): I, then I^2
     RoiRecord* rec;          // [cand * n3 + j]
     // candidate step fused into k_roi_eval (TemplateMatcher.cpp:329-366) when step != 0
     int32_t step;            // 1: best of n3, early break, back-mapping, append to live_out
@@ -455,12 +458,13 @@ constexpr int kOverlapMaxCand = 512;   // overlapping partners of one rectangle 
 // lists / offcnt may be mapped host memory (plain stores only); meta must be device memory.
 void launch_overlap_pairs(const OvRect* r, const float4* box, int n, double max_overlap, int32_t* lists, int list_cap,
                           int32_t* offcnt, int32_t* meta, hipStream_t st);
-int roi_pick_rc(int tw, int th);
 int roi_pitch_for(int tw);
 int roi_tab_rows(int th);   // rows of a ROI's X0 / Y0 tables: th + 6 rounded up to a 32-row tile
 size_t roi_tiles_bytes(int tw, int th);
 int roi_tiles_for(int tw, int th);   // 32x32 warp tiles of a (tw+6) x (th+6) ROI
-size_t roi_corr_lds(int roi_pitch, int tw, int rc);
+size_t roi_corr_lds(int roi_pitch);
+constexpr int kRoiEdgeWords = 2 * 12 * 7;   // RoiArgs::wedge per slot
+int roi_bands(int th);                       // k_roi_corr's bands of template rows (RoiArgs::wtot / wtotq per slot: x 7)
 constexpr int kMmaRows = 16;   // template rows per MFMA correlation chunk (M of v_mfma_i32_16x16x64_i8)
 
 }  // namespace fpm

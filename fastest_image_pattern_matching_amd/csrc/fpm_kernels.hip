@@ -2364,7 +2364,6 @@ void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& 
 // (A single fused kernel per layer was measured slower: at its LDS/VGPR footprint the latency-bound sampling
 // loses the occupancy it needs; see DESIGN.md.)
 // ---- geometry of the refinement scratch ----------------------------------------------------------------------
-constexpr int ROI_RC = kMmaRows;     // template rows per correlation chunk
 constexpr int ROI_T = 32;            // warp tile: 32 x 32 ROI pixels per wave task
 constexpr int ROI_FT = 4096;         // per-wave LDS footprint buffer (bytes) >= worst-case rotated tile bbox
 // k_roi_warp's footprint row pitch in LDS: one fixed odd number of dwords (row-strided byte gathers spread over the
@@ -2382,8 +2381,6 @@ constexpr int kTapShift = kTabFrac - kInterBits;        // 11
 // samplers write it flipped (one bit-op per 4 pixels), so k_roi_corr stages rows into LDS as they are
 constexpr uint32_t kRoiFlip = 0x80808080u;
 
-int roi_pick_rc(int /*tw*/, int th) { return th < ROI_RC ? th : ROI_RC; }
-
 // ROI row pitch: >= RW + 16 (look-ahead of the 16-byte B reads at shift <= 6) and >= 64*ceil(tw/64) + 22 (the
 // MFMA k range), pitch/16 odd (spreads the LDS banks of row-strided 16-byte reads)
 __host__ __device__ inline int roi_pitch_calc(int tw) {
@@ -2393,6 +2390,7 @@ __host__ __device__ inline int roi_pitch_calc(int tw) {
     return q * 16;
 }
 int roi_pitch_for(int tw) { return roi_pitch_calc(tw); }
+int roi_bands(int th) { return (th + 2 * kMmaRows - 1) / (2 * kMmaRows); }   // kBandRows
 int roi_tab_rows(int th) { return (th + 6 + ROI_T - 1) / ROI_T * ROI_T; }
 // Position of ROI row y in a ROI's X0 / Y0 tables: inside each 32-row tile block, rows y, y + 8, y + 16, y + 24 are
 // adjacent (k_roi_warp's lane of rows lr + 8i reads its four row origins as one 16-byte load)
@@ -2408,9 +2406,9 @@ __host__ __device__ inline int tmpl_lds_pitch(int tp8) {
     return q * 16;
 }
 
-// (the 2 * src_rows words are dead layout: they held the rows' totals of the removed RS 0 form and are kept, like the
-// tw / rc parameters, so that the launched LDS size stays what it was; a change that may alter the LDS size drops them)
-size_t roi_corr_lds(int roi_pitch, int /*tw*/, int /*rc*/) {
+// (the 2 * src_rows words after the rows once held the rows' totals of the removed RS 0 form; 48 of them now hold the
+// band totals of the two N tiles, k_roi_corr's bt1 / bt2, so the launched LDS size stays what it was)
+size_t roi_corr_lds(int roi_pitch) {
     constexpr int src_rows = 2 * kMmaRows + 6;
     return (size_t)src_rows * roi_pitch +
            sizeof(uint32_t) * (2 * src_rows + 2 * 7 * src_rows + 2 * kMmaRows + 2 * kMmaRows * 49) + 64;
@@ -3991,7 +3989,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 // 16-byte loads of the i8 template.  u8 operands enter the signed MFMA as x ^ 0x80 = x - 128; the exact value
 // is restored with integer corrections  sum T*I = sum T'I' + 128*(W[s][dx] + TS[t]) - 16384*tw  (W = window row
 // sum of I, TS = template row sum; mod 2^32, true value < 2^31).  The item also produces the rows' exact window
-// sums of I and I^2 and the per-16-row-chunk window-sum partials used by the normalisation.
+// sums of I and I^2 and, of them, the band totals and edge rows from which k_roi_eval rebuilds the normalisation's
+// window sums.
 typedef int fpm_v4i __attribute__((ext_vector_type(4)));
 constexpr int kBandRows = 2 * kMmaRows;       // template rows per work item
 constexpr int kBandSrc = kBandRows + 6;       // source rows per work item
@@ -4187,14 +4186,30 @@ __device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, i
     q2 = p2 - m2;
 }
 
+// Sum over the 16 lanes of a DPP row (lanes 16 i .. 16 i + 15), left in every one of them: xor 1, xor 2 (quad_perm), then
+// row_half_mirror and row_mirror, which pair each lane with one of the other quad / the other half whose sum is uniform.
+__device__ __forceinline__ uint32_t row16_sum(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, false);   // row_half_mirror
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, false);   // row_mirror
+    return v;
+}
+// ... of 16 values below 2^32 as a 64-bit sum: the low and high half-words summed apart (each sum < 2^20)
+__device__ __forceinline__ uint64_t row16_sum_wide(uint32_t v) {
+    const uint32_t lo = row16_sum(v & 0xffffu), hi = row16_sum(v >> 16);
+    return (uint64_t)lo + ((uint64_t)hi << 16);
+}
+
 // MODE (profiling ablations in scripts/roi_microbench.hip; the product uses 0): 2 = no MFMA loop, 3 = no staging
-// (slot-major form only), 5 = no row-result stores, 6 = no window partials, 7 = no row sums (4, no window-edge phase,
-// went with the RS 0 form, the only one with such a phase)
+// (slot-major form only), 5 = no row-result stores, 6 = no band totals / edge rows of the window sums (until the band
+// totals replaced them: no per-chunk window partials), 7 = no row sums (4, no window-edge phase, went with the RS 0
+// form, the only one with such a phase)
 // The A operand is read from the global i8 slab (no template rows in LDS); WPE: register cap (waves per SIMD);
 // NK > 0: register-A form (A fragments of nk <= NK k-steps held per wave, band-major item runs)
 // PFR (register-A form): prefetch the next item's rows (false: load this item's rows at its start, fewer VGPRs)
 // RS: 1 (the slot-major form) = row statistics in one phase (a quad of lanes per row: its I / I^2 totals reduced by DPP,
-// then the edge pixels of each window subtracted by the same lanes; the window partials split over lane pairs),
+// then the edge pixels of each window subtracted by the same lanes),
 // 3 (the product up to 8 k-steps) = the full-row sums on the matrix cores (tile_row_sums: the owner wave of each N tile,
 // waves 0 / 1 / 3, reads its tile's dx = 0 B fragments as 16-byte LDS reads and issues 2 MFMAs per k-step, then
 // subtracts the window edges of its 16 rows itself: the same two barriers as 1, without its strided walk of 48 dwords
@@ -4209,6 +4224,12 @@ __device__ __forceinline__ void window_edges(uint64_t lo, uint64_t hi, int dx, i
 // product: the item's matrix work is not held behind the co-resident waves' staging and statistics VALU; Src7 kernel
 // pass 196.5 -> 185.7 us per k_roi_corr launch averaged over the layers, profiles/r06_prio/), 2 = the GEMM alone,
 // 0 = none
+// Window sums (RoiArgs::wtot / wtotq / wedge): the lanes that compute a row's W[row][dx] (every RS) also store it as an
+// edge row where the row is one of the ROI's first 6 (band 0) or the 6 past its last template row (the last band), and
+// add it, masked to the band's own rows < rb, into the band total of their N tile (rows 16 i .. 16 i + 15 sit in one
+// wave: tiles 0 and 1 in waves 0 and 1); the two tiles' totals meet in LDS (bt1 / bt2) and 7 lanes of wave 2 store
+// their sum after the epilogue.  14 numbers per item instead of the 196 per-chunk partials of a phase of its own
+// (profiles/window_band_totals/).
 #ifndef FPM_CORR_PRIO
 #define FPM_CORR_PRIO 1
 #endif
@@ -4223,7 +4244,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const int tw = a.tw, th = a.th, RW = tw + 6;
     const int SBp = a.roi_pitch;
     uint8_t* const SB = smem;                                  // kBandSrc rows x SBp, bytes ^ 0x80
-    // (2 kBandSrc words after the rows stay free: roi_corr_lds's layout, once the rows' totals)
+    // the 2 kBandSrc words after the rows: the band totals of N tiles 0 and 1, [tile][8] (I: u32, then I^2: u64)
+    uint64_t* bt2 = (uint64_t*)(SB + (size_t)kBandSrc * SBp);
+    uint32_t* bt1 = (uint32_t*)(bt2 + 16);
+    static_assert(16 * 2 + 16 <= 2 * kBandSrc, "bt2 / bt1 fit the words between the rows and wi");
     uint32_t* wi = (uint32_t*)(SB + (size_t)kBandSrc * SBp) + 2 * kBandSrc;   // [row][dx] window sums of I
     uint32_t* wq = wi + kBandSrc * 7;                          // [row][dx] window sums of I^2
     uint32_t* lts = wq + kBandSrc * 7;                         // the band's template-row sums (16-byte aligned)
@@ -4406,17 +4430,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             const uint64_t lo = (uint64_t)(l0 ^ 0x80808080u) | ((uint64_t)(l1 ^ 0x80808080u) << 32);
             const uint64_t hi = (uint64_t)e0 | ((uint64_t)e1 << 32);
             const int nf = min(6, 64 * a.nk - tw);
+            const uint32_t eo = (uint32_t)slot * (uint32_t)kRoiEdgeWords;   // the slot's edge rows (32-bit offsets recomputed per item)
+            uint32_t t1[2] = {0u, 0u}, t2[2] = {0u, 0u};   // this row's share of the band totals
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int dx = g3 + 4 * h;
                 if (dx < 7 && row < nsrc) {
                     uint32_t q1, q2;
                     window_edges(lo, hi, dx, nf, q1, q2);
-                    wi[row * 7 + dx] = s1 - q1;
-                    wq[row * 7 + dx] = s2 - q2;
+                    const uint32_t v1 = s1 - q1, v2 = s2 - q2;
+                    wi[row * 7 + dx] = v1;
+                    wq[row * 7 + dx] = v2;
+                    if (MODE != 6) {
+                        if (row < rb) { t1[h] = v1; t2[h] = v2; }
+                        if (band == 0 && row < 6) {                  // ROI rows 0 .. 5
+                            const uint32_t o = eo + (uint32_t)(row * 7 + dx);
+                            a.wedge[o] = v1;
+                            a.wedge[o + 84u] = v2;
+                        }
+                        if (band == nband - 1 && row >= rb) {        // ROI rows th .. th + 5 (row < nsrc = rb + 6)
+                            const uint32_t o = eo + (uint32_t)((6 + row - rb) * 7 + dx);
+                            a.wedge[o] = v1;
+                            a.wedge[o + 84u] = v2;
+                        }
+                    }
+                }
+            }
+            if (MODE != 6 && nt < 2) {   // wave-uniform: waves 0 and 1, whose 16 rows n3 of each dx share a DPP row
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t r1 = row16_sum(t1[h]);
+                    const uint64_t r2 = row16_sum_wide(t2[h]);
+                    if (n3 == 0 && g3 + 4 * h < 7) {
+                        bt1[8 * nt + g3 + 4 * h] = r1;
+                        bt2[8 * nt + g3 + 4 * h] = r2;
+                    }
                 }
             }
         }
+        uint32_t u1[2] = {0u, 0u}, u2[2] = {0u, 0u};   // (RS 1) the lane's row's share of the band totals
         if (RS == 1 && MODE != 7 && tid < 4 * nsrc) {
             // row r's statistics by the quad of lanes 4r .. 4r + 3 (whole quads: DPP within the quad): exact full-row
             // sums of I and I^2 over the row's words (pixels past RW are zero), then each lane subtracts the window's
@@ -4469,46 +4521,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                     q2 = __builtin_amdgcn_udot4(a1, a1, q2, false);
                     q2 = __builtin_amdgcn_udot4(b0, b0, q2, false);
                     q2 = __builtin_amdgcn_udot4(b1, b1, q2, false);
-                    wi[r * 7 + dx] = s1 - q1;
-                    wq[r * 7 + dx] = s2 - q2;
+                    const uint32_t v1 = s1 - q1, v2 = s2 - q2;
+                    wi[r * 7 + dx] = v1;
+                    wq[r * 7 + dx] = v2;
+                    if (MODE != 6) {
+                        if (r < rb) { u1[h] = v1; u2[h] = v2; }
+                        const uint32_t eo = (uint32_t)slot * (uint32_t)kRoiEdgeWords;
+                        if (band == 0 && r < 6) {                    // ROI rows 0 .. 5
+                            const uint32_t o = eo + (uint32_t)(r * 7 + dx);
+                            a.wedge[o] = v1;
+                            a.wedge[o + 84u] = v2;
+                        }
+                        if (band == nband - 1 && r >= rb) {          // ROI rows th .. th + 5 (r < nsrc = rb + 6)
+                            const uint32_t o = eo + (uint32_t)((6 + r - rb) * 7 + dx);
+                            a.wedge[o] = v1;
+                            a.wedge[o + 84u] = v2;
+                        }
+                    }
+                }
+            }
+        }
+        if (RS == 1 && MODE != 7 && MODE != 6 && wv < 2) {
+            // the band totals of N tiles 0 and 1: wave wv holds rows 16 wv .. 16 wv + 15, a row per quad, so the lanes of
+            // one dx are 4 apart (every lane of the wave takes part: the lanes past the band's rows add zeros)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint32_t r1 = u1[h], lo = u2[h] & 0xffffu, hi = u2[h] >> 16;
+#pragma unroll
+                for (int m = 4; m <= 32; m <<= 1) {
+                    r1 += (uint32_t)__shfl_xor((int)r1, m, 64);
+                    lo += (uint32_t)__shfl_xor((int)lo, m, 64);
+                    hi += (uint32_t)__shfl_xor((int)hi, m, 64);
+                }
+                if (lane < 4 && lane + 4 * h < 7) {
+                    bt1[8 * wv + lane + 4 * h] = r1;
+                    bt2[8 * wv + lane + 4 * h] = (uint64_t)lo + ((uint64_t)hi << 16);
                 }
             }
         }
         __syncthreads();
-        // per-16-row-chunk partials of the window sums, 8 rows per lane (lane pairs, combined by DPP within the quad;
-        // the 8 rows' LDS reads all in flight)
-        auto partials = [&]() {
-            if (MODE == 6 || tid >= 4 * 49) return;
-            const int pr = tid >> 1, half = tid & 1;
-            const int h = pr / 49, k = pr - h * 49;
-            const int chunk = (T0 >> 4) + h;
-            const int tlo = kMmaRows * h, thi = min(tlo + kMmaRows, rb);
-            const bool ok = chunk < a.nchunk && tlo < thi;   // the same for both lanes of the pair
-            const int pdy = k / 7, ddx = k - pdy * 7;
-            const int t0 = tlo + 8 * half, n8 = ok ? min(8, thi - t0) : 0;
-            uint32_t s1 = 0, x[8], y[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = (t0 + u + pdy) * 7 + ddx;
-                x[u] = u < n8 ? wi[i] : 0u;
-                y[u] = u < n8 ? wq[i] : 0u;
-            }
-            uint64_t s2 = 0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s1 += x[u]; s2 += y[u]; }
-            s1 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xF, 0xF, false);
-            const uint32_t lo = (uint32_t)s2, hi = (uint32_t)(s2 >> 32);
-            s2 += (uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)lo, 0xB1, 0xF, 0xF, false) |
-                  ((uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)hi, 0xB1, 0xF, 0xF, false) << 32);
-            if (ok && half == 0) {
-                // 32-bit index recomputed per item (opaque k): a loop-invariant 64-bit address kept across the item
-                // loop was spilled, and its reload's vmcnt(0) waited for every row-result store of the item
-                uint32_t kk = (uint32_t)k;
-                asm volatile("" : "+v"(kk));
-                const uint32_t wo = ((uint32_t)slot * (uint32_t)a.nchunk + (uint32_t)chunk) * 49u + kk;
-                a.wsum[wo] = s1;
-                a.wsq[wo] = s2;
-            }
+        // the band's 7 + 7 totals of the window sums: N tile 0's plus, where the band has more than 16 rows, N tile 1's
+        // (bt1 / bt2, written before the barrier above and not again until two barriers on); 7 lanes of wave 2
+        auto band_totals = [&]() {
+            if (MODE == 6 || MODE == 7 || tid < 128 || tid >= 128 + 7) return;
+            // 32-bit index recomputed per item (opaque dx): a loop-invariant 64-bit address kept across the item
+            // loop was spilled, and its reload's vmcnt(0) waited for every row-result store of the item
+            uint32_t dx = (uint32_t)(tid - 128);
+            asm volatile("" : "+v"(dx));
+            const bool two = rb > kMmaRows;
+            const uint32_t s1 = bt1[dx] + (two ? bt1[8 + dx] : 0u);
+            const uint64_t s2 = bt2[dx] + (two ? bt2[8 + dx] : 0ull);
+            const uint32_t wo = ((uint32_t)slot * (uint32_t)nband + (uint32_t)band) * 7u + dx;
+            a.wtot[wo] = s1;
+            a.wtotq[wo] = s2;
         };
         const bool active = kMmaRows * mt < rb && kMmaRows * nt < nsrc;   // wave-uniform
         if (FPM_CORR_PRIO == 1) __builtin_amdgcn_s_setprio(1);   // the GEMM and its epilogue
@@ -4558,7 +4623,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
         if (FPM_CORR_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        partials();
+        band_totals();
         if (SE) { pv_slot = slot; pv_T0 = T0; pv_rb = rb; }
     }
     if (SE && pv_slot >= 0) {   // the last item's row results
@@ -5123,21 +5188,26 @@ __device__ void eval_roi(const RoiArgs& a, int slot, int lane, uint8_t* blk, flo
     }
     const size_t total4 = ((size_t)th * 49 + 3) >> 2;   // uint4 per ROI series (slot stride 4 * total4)
     const uint4* rs = (const uint4*)(a.rowsum + (size_t)slot * total4 * 4);
-    uint64_t s1 = 0, s2 = 0;
-    if (lane < 49) {   // window sums over the chunk partials
-        const uint32_t* ws = a.wsum + (size_t)slot * a.nchunk * 49 + lane;
-        const uint64_t* wq = a.wsq + (size_t)slot * a.nchunk * 49 + lane;
-        int c = 0;
-        for (; c + 8 <= a.nchunk; c += 8) {
-            uint32_t x[8];
-            uint64_t y[8];
+    // The window sums' inputs (RoiArgs::wtot / wtotq / wedge), all loads independent and issued here, used once the first series block is
+    // requested:
+    // lane l < 63 takes the flat band totals l + 63 u (63 = 9 x 7: a lane keeps its dx = l % 7), four of them in flight
+    // (36 bands, th <= 1152; more follow), lane l < 42 the four edge values of (row l / 7, dx l % 7).
+    const int nt7 = 7 * ((th + kBandRows - 1) / kBandRows);
+    const uint32_t* wt = a.wtot + (size_t)slot * nt7;
+    const uint64_t* wtq = a.wtotq + (size_t)slot * nt7;
+    uint32_t bx[4];
+    uint64_t by[4];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { x[u] = ws[(size_t)(c + u) * 49]; y[u] = wq[(size_t)(c + u) * 49]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s1 += x[u]; s2 += y[u]; }
-        }
-        for (; c < a.nchunk; ++c) { s1 += ws[(size_t)c * 49]; s2 += wq[(size_t)c * 49]; }
+    for (int u = 0; u < 4; ++u) {
+        const int i = lane + 63 * u;
+        const bool ok = lane < 63 && i < nt7;
+        bx[u] = ok ? wt[i] : 0u;
+        by[u] = ok ? wtq[i] : 0ull;
     }
+    const uint32_t* we = a.wedge + (size_t)slot * kRoiEdgeWords;
+    const bool el = lane < 42;
+    const uint32_t eh1 = el ? we[lane] : 0u, et1 = el ? we[42 + lane] : 0u;          // I: rows r, th + r
+    const uint32_t eh2 = el ? we[84 + lane] : 0u, et2 = el ? we[126 + lane] : 0u;    // I^2
     // the series streams through two wave-private LDS buffers by LDS-DMA: block b + 1 (exactly kEvalDma
     // 16-byte loads per lane, padded with dummy loads so a counted vmcnt is exact) is in flight while block b folds
     constexpr int BQ = kEvalRows * 49 / 4;   // uint4 per block
@@ -5158,6 +5228,26 @@ __device__ void eval_roi(const RoiArgs& a, int slot, int lane, uint8_t* blk, flo
     float accF = 0.f;
     uint64_t accI = 0;
     issue_block(0, blk);
+    // (consumed with block 0 in flight: only the 49 sums stay live across the fold)
+    // S(dy, dx) = sum_bands tot[band][dx] + sum_{r < dy} (W[th + r][dx] - W[r][dx]): lane k = 7 dy + dx gathers the 9
+    // lanes' partial totals of its dx and the row differences r < dy (each below 2^31 in magnitude) from lanes 7 r + dx
+    uint64_t p1 = (uint64_t)bx[0] + bx[1] + bx[2] + bx[3], p2 = by[0] + by[1] + by[2] + by[3];
+    for (int i = lane + 4 * 63; lane < 63 && i < nt7; i += 63) { p1 += wt[i]; p2 += wtq[i]; }
+    const int kdy = lane < 49 ? lane / 7 : 0, kdx = lane < 49 ? lane - 7 * kdy : 0;
+    const int d1 = (int)(et1 - eh1), d2 = (int)(et2 - eh2);
+    uint64_t s1 = 0, s2 = 0;
+    // (three steps' cross-lane reads in flight, not all of them: unrolled whole they cost 47 VGPRs and a wave of occupancy)
+#pragma unroll 3
+    for (int m = 0; m < 9; ++m) {
+        const int src = kdx + 7 * m;
+        s1 += (uint64_t)(uint32_t)__shfl((int)(uint32_t)p1, src, 64) | ((uint64_t)(uint32_t)__shfl((int)(p1 >> 32), src, 64) << 32);
+        s2 += (uint64_t)(uint32_t)__shfl((int)(uint32_t)p2, src, 64) | ((uint64_t)(uint32_t)__shfl((int)(p2 >> 32), src, 64) << 32);
+    }
+#pragma unroll 3
+    for (int r = 0; r < 6; ++r) {
+        const int v1 = __shfl(d1, kdx + 7 * r, 64), v2 = __shfl(d2, kdx + 7 * r, 64);
+        if (r < kdy) { s1 += (uint64_t)(int64_t)v1; s2 += (uint64_t)(int64_t)v2; }
+    }
     for (int b = 0; b < nblk; ++b) {
         const uint32_t* cb = (const uint32_t*)(blk + (b & 1) * kEvalBuf);
         if (b + 1 < nblk) {
@@ -5349,7 +5439,7 @@ static void launch_corr_regs(const RoiArgs& a, long items, size_t lds, hipStream
 }
 void launch_roi_corr(const RoiArgs& a, hipStream_t st) {
     if (a.slot_cap <= 0 || a.equal1) return;
-    const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
+    const size_t lds = roi_corr_lds(a.roi_pitch);
     // register-A form where its staged rows fit one 64-lane pass and A fits 16 k-steps (templates <= 1024 wide);
     // the slot-major form below serves wider templates
     if ((a.roi_pitch >> 4) <= 64 && a.nk <= 16 && lds <= 65536) {

@@ -2,7 +2,7 @@
 // product chain it replaces (k_roi_tables -> k_roi_warp -> k_roi_corr) on the microbenchmark's Src7 problem
 // (random 4024x3036 levels, 762x521 template, 11 candidates x 3 angles per source; MB_* env overrides as in
 // roi_microbench.hip, e.g. the layer-1 shape MB_W=2012 MB_H=1518 MB_P=2048 MB_TW=381 MB_TH=261).  Checks that the
-// row dot products and window-sum partials (k_roi_eval's inputs) and the records k_roi_eval makes of them are
+// row dot products and window-sum band totals (k_roi_eval's inputs) and the records k_roi_eval makes of them are
 // identical, then times both.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off scripts/fused_bench.hip -o build/fused_bench
 #include "../fastest_image_pattern_matching_amd/csrc/fpm_kernels.hip"
@@ -68,14 +68,16 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dts, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
         a.tmpl8 = d8; a.tp8 = p8; a.nk = (TW + 63) / 64; a.tsum = dts;
     }
-    a.n3 = n3; a.rc = roi_pick_rc(TW, TH); a.nchunk = (TH + a.rc - 1) / a.rc;
+    a.n3 = n3;
     a.fold = 1; a.equal1 = 0; a.per_source = ncand; a.slot_base = 0; a.slot_cap = C * n3;
     a.mean = 100; a.norm = 5000; a.inv_area = 1.0 / (TW * TH);
     a.live = d_live; a.live_count = d_cnt; a.state = d_st; a.nodes = d_nodes;
-    const size_t rs_n = (size_t)C * n3 * ((TH * 49 + 3) & ~3), ws_n = (size_t)C * n3 * a.nchunk * 49;
+    const size_t rs_n = (size_t)C * n3 * ((TH * 49 + 3) & ~3), ws_n = (size_t)C * n3 * roi_bands(TH) * 7,
+                 we_n = (size_t)C * n3 * kRoiEdgeWords;
     CK(hipMalloc(&a.rowsum, rs_n * 4));
-    CK(hipMalloc(&a.wsum, ws_n * 4));
-    CK(hipMalloc(&a.wsq, ws_n * 8));
+    CK(hipMalloc(&a.wtot, ws_n * 4));
+    CK(hipMalloc(&a.wtotq, ws_n * 8));
+    CK(hipMalloc(&a.wedge, we_n * 4));
     CK(hipMalloc(&a.rec, sizeof(RoiRecord) * C * n3));
     a.tabw = roi_pitch_for(TW); a.tabh = roi_tab_rows(TH);
     a.roi_pitch = roi_pitch_for(TW); a.roi_stride = roi_tiles_bytes(TW, TH);
@@ -102,22 +104,22 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> r_wq(ws_n), g_wq(ws_n);
     std::vector<RoiRecord> r_rec(C * n3), g_rec(C * n3);
     auto clear = [&] {
-        CK(hipMemset(a.rowsum, 0xcd, rs_n * 4)); CK(hipMemset(a.wsum, 0xcd, ws_n * 4));
-        CK(hipMemset(a.wsq, 0xcd, ws_n * 8)); CK(hipMemset(a.rec, 0xcd, sizeof(RoiRecord) * C * n3));
+        CK(hipMemset(a.rowsum, 0xcd, rs_n * 4)); CK(hipMemset(a.wtot, 0, ws_n * 4));
+        CK(hipMemset(a.wtotq, 0, ws_n * 8)); CK(hipMemset(a.wedge, 0xcd, we_n * 4)); CK(hipMemset(a.rec, 0xcd, sizeof(RoiRecord) * C * n3));
     };
     clear();
     launch_roi_tables(a, 0); launch_roi_warp(a, 0); launch_roi_corr(a, 0); launch_roi_eval(a, 0);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(r_rs.data(), a.rowsum, rs_n * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(r_ws.data(), a.wsum, ws_n * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(r_wq.data(), a.wsq, ws_n * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(r_ws.data(), a.wtot, ws_n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(r_wq.data(), a.wtotq, ws_n * 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(r_rec.data(), a.rec, sizeof(RoiRecord) * C * n3, hipMemcpyDeviceToHost));
     clear();
     launch_roi_fused(a, 0); launch_roi_eval(a, 0);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(g_rs.data(), a.rowsum, rs_n * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(g_ws.data(), a.wsum, ws_n * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(g_wq.data(), a.wsq, ws_n * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(g_ws.data(), a.wtot, ws_n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(g_wq.data(), a.wtotq, ws_n * 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(g_rec.data(), a.rec, sizeof(RoiRecord) * C * n3, hipMemcpyDeviceToHost));
     size_t bad_rs = 0, bad_ws = 0, bad_wq = 0, bad_rec = 0, first = (size_t)-1;
     const size_t per = (TH * 49 + 3) & ~3;
@@ -125,7 +127,7 @@ int main(int argc, char** argv) {
         if (i % per < (size_t)TH * 49 && r_rs[i] != g_rs[i]) { ++bad_rs; if (first == (size_t)-1) first = i; }
     for (size_t i = 0; i < ws_n; ++i) { bad_ws += r_ws[i] != g_ws[i]; bad_wq += r_wq[i] != g_wq[i]; }
     bad_rec = memcmp(r_rec.data(), g_rec.data(), sizeof(RoiRecord) * C * n3) != 0;
-    printf("check: rowsum %zu / wsum %zu / wsq %zu differ, records %s\n", bad_rs, bad_ws, bad_wq, bad_rec ? "DIFFER" : "identical");
+    printf("check: rowsum %zu / band totals %zu / %zu differ, records %s\n", bad_rs, bad_ws, bad_wq, bad_rec ? "DIFFER" : "identical");
     if (first != (size_t)-1) {
         const size_t sl = first / per, e = first % per;
         printf("  first rowsum mismatch: slot %zu row %zu k %zu: ref %u got %u\n", sl, e / 49, e % 49, r_rs[first], g_rs[first]);

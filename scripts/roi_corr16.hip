@@ -11,6 +11,7 @@ namespace fpm {
 // Outputs are k_roi_corr's exactly: the row dot products [t][49] (exact u32, through LDS as 16-byte runs during the
 // next item, SE), and the window-sum partial of the item's chunk (one 16-row chunk per item).
 constexpr int kB16Rows = kMmaRows, kB16Src = kB16Rows + 6;
+__device__ inline int roi_bands_dev(int th) { return (th + 2 * kB16Rows - 1) / (2 * kB16Rows); }   // roi_bands
 __host__ __device__ inline size_t roi_corr16_lds(int roi_pitch) {
     return (size_t)kB16Src * roi_pitch + sizeof(uint32_t) * (2 * 7 * kB16Src + kB16Rows + kB16Rows * 49) + 64;
 }
@@ -162,32 +163,26 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 }
             }
         }
-        // the item's chunk partial of the window sums (positions k by lane pairs, 8 rows each, combined by DPP)
-        if (tid < 2 * 49) {
-            const int k = tid >> 1, half = tid & 1;
-            const int chunk = T0 >> 4;
-            const int pdy = k / 7, ddx = k - pdy * 7;
-            const int t0 = 8 * half, n8 = min(8, rb - t0);
-            uint32_t s1 = 0, x[8], y[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = (t0 + u + pdy) * 7 + ddx;
-                x[u] = u < n8 ? wi[i] : 0u;
-                y[u] = u < n8 ? wq[i] : 0u;
-            }
+        // the item's share of the window sums (RoiArgs::wtot / wtotq / wedge): its 16 rows' totals, added into the 32-row
+        // band's by atomics (the two items of a band run in different workgroups; the harness zeroes the totals before
+        // the launch), and the ROI's edge rows from the first and the last item
+        if (tid < 7) {
+            uint32_t s1 = 0;
             uint64_t s2 = 0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s1 += x[u]; s2 += y[u]; }
-            s1 += (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xF, 0xF, false);
-            const uint32_t lo = (uint32_t)s2, hi = (uint32_t)(s2 >> 32);
-            s2 += (uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)lo, 0xB1, 0xF, 0xF, false) |
-                  ((uint64_t)(uint32_t)__builtin_amdgcn_mov_dpp((int)hi, 0xB1, 0xF, 0xF, false) << 32);
-            if (half == 0 && chunk < a.nchunk) {
-                uint32_t kk = (uint32_t)k;
-                asm volatile("" : "+v"(kk));
-                const uint32_t wo = ((uint32_t)slot * (uint32_t)a.nchunk + (uint32_t)chunk) * 49u + kk;
-                a.wsum[wo] = s1;
-                a.wsq[wo] = s2;
+            for (int t = 0; t < rb; ++t) { s1 += wi[t * 7 + tid]; s2 += wq[t * 7 + tid]; }
+            const uint32_t wo = ((uint32_t)slot * (uint32_t)roi_bands_dev(th) + (uint32_t)(band >> 1)) * 7u + (uint32_t)tid;
+            atomicAdd(a.wtot + wo, s1);
+            atomicAdd((unsigned long long*)a.wtotq + wo, (unsigned long long)s2);
+        } else if (tid < 49) {
+            const int e = tid - 7, er = e / 7, dx = e - er * 7;
+            uint32_t* we = a.wedge + (uint32_t)slot * (uint32_t)kRoiEdgeWords;
+            if (band == 0) {
+                we[er * 7 + dx] = wi[er * 7 + dx];
+                we[84 + er * 7 + dx] = wq[er * 7 + dx];
+            }
+            if (band == nband - 1) {
+                we[(6 + er) * 7 + dx] = wi[(rb + er) * 7 + dx];
+                we[84 + (6 + er) * 7 + dx] = wq[(rb + er) * 7 + dx];
             }
         }
         pv_slot = slot; pv_T0 = T0; pv_rb = rb;

@@ -9,7 +9,7 @@ namespace fpm {
 //   warp tables computed in LDS instead of read from HBM), their exact row sums of I and I^2 reduced on the fly;
 //   the 6 rows a band shares with the next stay in the ring (ring slot = ROI row mod kBandSrc);
 //   then K7's banded GEMM on the matrix cores (A fragments of the band in registers, loaded during the sampling)
-//   and its epilogue: the exact per-row dot products and the per-16-row window-sum partials, exactly k_roi_corr's
+//   and its epilogue: the exact per-row dot products and the window sums' band totals and edge rows, exactly k_roi_corr's
 //   outputs, so K8 (k_roi_eval) folds them unchanged.
 // Only the first band of a run samples its 6 leading rows again (runs of ~3.5 bands: ~4.5 % extra sampling), the
 // ~0.4 MB sampled ROI of a layer-0 Src7 candidate is neither written to nor re-read from HBM, and the per-ROI warp
@@ -236,21 +236,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                     }
                 }
             }
-            if (tid < 2 * 49) {   // per-16-row-chunk partials of the window sums (k_roi_corr)
-                const int h = tid / 49, k = tid - h * 49;
-                const int chunk = (T0 >> 4) + h;
-                const int tlo = kMmaRows * h, thi = min(tlo + kMmaRows, rb);
-                if (chunk < a.nchunk && tlo < thi) {
-                    const int pdy = k / 7, ddx = k - pdy * 7;
-                    uint32_t s1 = 0;
-                    uint64_t s2 = 0;
-                    for (int t = tlo; t < thi; ++t) {
-                        const int r = ring(T0 + t + pdy) * 7 + ddx;
-                        s1 += wi[r];
-                        s2 += wq[r];
-                    }
-                    a.wsum[((size_t)slot * a.nchunk + chunk) * 49 + k] = s1;
-                    a.wsq[((size_t)slot * a.nchunk + chunk) * 49 + k] = s2;
+            if (tid < 7) {   // the band's totals of the window sums over its own rows (RoiArgs::wtot / wtotq)
+                uint32_t s1 = 0;
+                uint64_t s2 = 0;
+                for (int t = 0; t < rb; ++t) {
+                    const int r = ring(T0 + t) * 7 + tid;
+                    s1 += wi[r];
+                    s2 += wq[r];
+                }
+                a.wtot[((size_t)slot * nband + b) * 7 + tid] = s1;
+                a.wtotq[((size_t)slot * nband + b) * 7 + tid] = s2;
+            } else if (tid < 49) {   // edge rows (RoiArgs::wedge): ROI rows 0 .. 5 from band 0, th .. th + 5 from the last
+                const int e = tid - 7, er = e / 7, dx = e - er * 7;
+                uint32_t* we = a.wedge + (size_t)slot * kRoiEdgeWords;
+                if (b == 0) {
+                    we[er * 7 + dx] = wi[ring(er) * 7 + dx];
+                    we[84 + er * 7 + dx] = wq[ring(er) * 7 + dx];
+                }
+                if (b == nband - 1) {
+                    we[(6 + er) * 7 + dx] = wi[ring(th + er) * 7 + dx];
+                    we[84 + (6 + er) * 7 + dx] = wq[ring(th + er) * 7 + dx];
                 }
             }
         }

@@ -1,7 +1,7 @@
 // roi_microbench.hip — profiling harness (not part of the product): times the product refinement kernels
 // (k_roi_tables / k_roi_warp / k_roi_corr / k_roi_eval) and k_pyr_down on a fixed Src7 layer-0-sized problem
 // (4024x3036 level, 762x521 template, 264 ROIs = 8 sources x 11 candidates x 3), checks k_roi_corr's row dot
-// products and window partials of a few ROIs against a host computation, and measures stream ceilings.
+// products and window band totals and edge rows of a few ROIs against a host computation, and measures stream ceilings.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off scripts/roi_microbench.hip -o build/roi_mb
 #include "../fastest_image_pattern_matching_amd/csrc/fpm_kernels.hip"
 
@@ -241,15 +241,17 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dts, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
         a.tmpl8 = d8; a.tp8 = p8; a.nk = (TW + 63) / 64; a.tsum = dts;
     }
-    a.n3 = n3; a.rc = argc > 2 ? atoi(argv[2]) : roi_pick_rc(TW, TH); a.nchunk = (TH + a.rc - 1) / a.rc;
+    a.n3 = n3;
+    const int nband = roi_bands(TH);
     a.fold = 1; a.equal1 = 0; a.per_source = ncand; a.slot_base = 0; a.slot_cap = C * n3;
     a.mean = 100; a.norm = 5000; a.inv_area = 1.0 / (TW * TH);
     a.live = d_live; a.live_count = d_cnt; a.state = d_st; a.nodes = d_nodes;
     CK(hipMalloc(&a.rowsum, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4));
-    CK(hipMalloc(&a.wsum, (size_t)C * n3 * a.nchunk * 49 * 4));
-    CK(hipMalloc(&a.wsq, (size_t)C * n3 * a.nchunk * 49 * 8));
+    CK(hipMalloc(&a.wtot, (size_t)C * n3 * nband * 7 * 4));
+    CK(hipMalloc(&a.wtotq, (size_t)C * n3 * nband * 7 * 8));
+    CK(hipMalloc(&a.wedge, (size_t)C * n3 * kRoiEdgeWords * 4));
     CK(hipMalloc(&a.rec, sizeof(RoiRecord) * C * n3));
-        printf("rois %d rc %d chunks %d corr lds %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc));
+        printf("rois %d bands %d corr lds %zu\n", C * n3, nband, roi_corr_lds(roi_pitch_for(TW)));
     // ---- product kernels (tables -> warp -> corr -> eval) --------------------------------------------------
     a.tabw = roi_pitch_for(TW); a.tabh = roi_tab_rows(TH);
     a.roi_pitch = roi_pitch_for(TW); a.roi_stride = roi_tiles_bytes(TW, TH);
@@ -344,7 +346,7 @@ int main(int argc, char** argv) {
     launch_roi_warp(a, 0);   // the product's ROIs (the warp variants above may have left other bytes)
     timeit([&] { launch_roi_corr(a, 0); }, "prod corr");
     if (TW > 512 && TW <= 768) {   // register-A form (12 k-steps, the Src7 layer-0 product) and its phase ablations
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
+        const size_t lds = roi_corr_lds(a.roi_pitch);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
         const int grid = (int)std::min<long>(items, 768);
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA full");
@@ -355,7 +357,7 @@ int main(int argc, char** argv) {
         // round 5: the product form's phases (MODE ablations of k_roi_corr<., 4, 12, false, 1, true, true>)
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no mfma+epi");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no stores");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no partials");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no band totals");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 4, 12, false, 1, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w no rowsums");
         // the row statistics on the matrix cores (RS 3, RS 4) against the RS 1 form, alternated
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 3, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS3");
@@ -365,12 +367,12 @@ int main(int argc, char** argv) {
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 12, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA SE DMA 4w RS4 (again)");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<2, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no mfma+epi");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<5, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no stores");
-        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no partials");
+        timeit([&] { hipLaunchKernelGGL((k_roi_corr<6, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no band totals");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 3, 12, false>), dim3(grid), dim3(256), lds, 0, a); }, "corrA no rowsums");
         if (envi("MB_CORR_ONLY", 0)) { launch_roi_corr(a, 0); }
     }
     if (TW > 256 && TW <= 512) {   // 8 k-steps (the Src7 layer-1 product): 3 vs 4 waves per SIMD
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
+        const size_t lds = roi_corr_lds(a.roi_pitch);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 8, false>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 3 waves");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3, 8, false, 1, true>), dim3((int)std::min<long>(items, 768)), dim3(256), lds, 0, a); }, "corrA8 SE 3 waves");
@@ -385,7 +387,7 @@ int main(int argc, char** argv) {
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 8, false, 4, true, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA8 SE DMA 4w RS4 (again)");
     }
     if (TW <= 256) {   // 4 k-steps (the Src7 layer-2 product): register staging, 4 waves per SIMD
-        const size_t lds = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
+        const size_t lds = roi_corr_lds(a.roi_pitch);
         const long items = (long)a.slot_cap * ((TH + 31) / 32);
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<7, 4, 4, false, 1, true>), dim3((int)std::min<long>(items, 1024)), dim3(256), lds, 0, a); }, "corrA4 SE 4w no rowsums");
@@ -398,7 +400,7 @@ int main(int argc, char** argv) {
     }
     timeit([&] { launch_roi_eval(a, 0); }, "prod eval");
     {
-        const size_t lds1 = roi_corr_lds(a.roi_pitch, a.tw, a.rc);
+        const size_t lds1 = roi_corr_lds(a.roi_pitch);
         const int grid = std::min(C * n3 * ((TH + 31) / 32), 16384);
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 1>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA free");
         timeit([&] { hipLaunchKernelGGL((k_roi_corr<0, 3>), dim3(grid), dim3(256), lds1, 0, a); }, "corr globA w3");
@@ -434,12 +436,13 @@ int main(int argc, char** argv) {
             std::vector<uint8_t> roi_t(a.roi_stride);
             const int txn = (TW + 6 + 31) / 32;
             auto roi_at = [&](int r, int c) { return (uint8_t)(roi_t[((size_t)((r >> 5) * txn + (c >> 5)) << 10) + (r & 31) * 32 + (c & 31)] ^ 0x80); };   // stored flipped
-            std::vector<uint32_t> rs((size_t)TH * 49), ws((size_t)a.nchunk * 49);
-            std::vector<uint64_t> wq((size_t)a.nchunk * 49);
+            std::vector<uint32_t> rs((size_t)TH * 49), ws((size_t)nband * 7), we(kRoiEdgeWords);
+            std::vector<uint64_t> wq((size_t)nband * 7);
             CK(hipMemcpy(roi_t.data(), a.roi + (size_t)slot * a.roi_stride, a.roi_stride, hipMemcpyDeviceToHost));
             CK(hipMemcpy(rs.data(), a.rowsum + (size_t)slot * ((TH * 49 + 3) & ~3), rs.size() * 4, hipMemcpyDeviceToHost));
-            CK(hipMemcpy(ws.data(), a.wsum + (size_t)slot * a.nchunk * 49, ws.size() * 4, hipMemcpyDeviceToHost));
-            CK(hipMemcpy(wq.data(), a.wsq + (size_t)slot * a.nchunk * 49, wq.size() * 8, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(ws.data(), a.wtot + (size_t)slot * nband * 7, ws.size() * 4, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(wq.data(), a.wtotq + (size_t)slot * nband * 7, wq.size() * 8, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(we.data(), a.wedge + (size_t)slot * kRoiEdgeWords, we.size() * 4, hipMemcpyDeviceToHost));
             for (int t = 0; t < TH; ++t)
                 for (int dy = 0; dy < 7; ++dy)
                     for (int dx = 0; dx < 7; ++dx) {
@@ -447,13 +450,21 @@ int main(int argc, char** argv) {
                         for (int c = 0; c < TW; ++c) ref += (uint32_t)tm[(size_t)t * TP + c] * roi_at(t + dy, c + dx);
                         if (ref != rs[(size_t)t * 49 + dy * 7 + dx]) ++bad;
                     }
-            for (int ch = 0; ch < a.nchunk; ++ch)
-                for (int k = 0; k < 49; ++k) {
-                    const int dy = k / 7, dx = k % 7;
+            // band totals (the band's own template rows) and edge rows (ROI rows 0 .. 5 and TH .. TH + 5) of the window sums
+            auto wrow = [&](int r, int dx, uint32_t& s1, uint64_t& s2) {
+                for (int c = 0; c < TW; ++c) { const uint32_t v = roi_at(r, c + dx); s1 += v; s2 += v * v; }
+            };
+            for (int bd = 0; bd < nband; ++bd)
+                for (int dx = 0; dx < 7; ++dx) {
                     uint32_t s1 = 0; uint64_t s2 = 0;
-                    for (int t = ch * a.rc; t < std::min(TH, (ch + 1) * a.rc); ++t)
-                        for (int c = 0; c < TW; ++c) { const uint32_t v = roi_at(t + dy, c + dx); s1 += v; s2 += v * v; }
-                    if (s1 != ws[(size_t)ch * 49 + k] || s2 != wq[(size_t)ch * 49 + k]) ++bad;
+                    for (int t = 32 * bd; t < std::min(TH, 32 * (bd + 1)); ++t) wrow(t, dx, s1, s2);
+                    if (s1 != ws[(size_t)bd * 7 + dx] || s2 != wq[(size_t)bd * 7 + dx]) ++bad;
+                }
+            for (int e = 0; e < 12; ++e)
+                for (int dx = 0; dx < 7; ++dx) {
+                    uint32_t s1 = 0; uint64_t s2 = 0;
+                    wrow(e < 6 ? e : TH + e - 6, dx, s1, s2);
+                    if (s1 != we[e * 7 + dx] || (uint32_t)s2 != we[84 + e * 7 + dx]) ++bad;
                 }
             (void)RW;
         }
@@ -476,7 +487,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(d8, t8.data(), t8.size(), hipMemcpyHostToDevice));
         CK(hipMemcpy(dts, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
         b.tmpl8 = d8; b.tp8 = p8; b.nk = 2; b.tsum = dts;
-        b.nchunk = (TH3 + 15) / 16; b.rc = 16; b.per_source = nc3;
+        b.per_source = nc3;
         std::vector<CandState> st3(C3);
         std::vector<int> live3(C3);
         for (int i = 0; i < C3; ++i) {

@@ -326,15 +326,17 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dts, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
         a.tmpl8 = d8; a.tp8 = p8; a.nk = (TW + 63) / 64; a.tsum = dts;
     }
-    a.n3 = n3; a.rc = argc > 2 ? atoi(argv[2]) : roi_pick_rc(TW, TH); a.nchunk = (TH + a.rc - 1) / a.rc;
+    a.n3 = n3;
+    const int nband = roi_bands(TH);
     a.fold = 1; a.equal1 = 0; a.per_source = ncand; a.slot_base = 0; a.slot_cap = C * n3;
     a.mean = 100; a.norm = 5000; a.inv_area = 1.0 / (TW * TH);
     a.live = d_live; a.live_count = d_cnt; a.state = d_st; a.nodes = d_nodes;
     CK(hipMalloc(&a.rowsum, (size_t)C * n3 * ((TH * 49 + 3) & ~3) * 4));
-    CK(hipMalloc(&a.wsum, (size_t)C * n3 * a.nchunk * 49 * 4));
-    CK(hipMalloc(&a.wsq, (size_t)C * n3 * a.nchunk * 49 * 8));
+    CK(hipMalloc(&a.wtot, (size_t)C * n3 * nband * 7 * 4));
+    CK(hipMalloc(&a.wtotq, (size_t)C * n3 * nband * 7 * 8));
+    CK(hipMalloc(&a.wedge, (size_t)C * n3 * kRoiEdgeWords * 4));
     CK(hipMalloc(&a.rec, sizeof(RoiRecord) * C * n3));
-        printf("rois %d rc %d chunks %d corr lds %zu\n", C * n3, a.rc, a.nchunk, roi_corr_lds(roi_pitch_for(TW), TW, a.rc));
+        printf("rois %d bands %d corr lds %zu\n", C * n3, nband, roi_corr_lds(roi_pitch_for(TW)));
     // ---- product kernels (tables -> warp -> corr -> eval) --------------------------------------------------
     a.tabw = roi_pitch_for(TW); a.tabh = roi_tab_rows(TH);
     a.roi_pitch = roi_pitch_for(TW); a.roi_stride = roi_tiles_bytes(TW, TH);

@@ -65,6 +65,9 @@ ALIGN_KERNEL_SYMBOL = "k_patch_align"
 # fpm_blobs_host: the summary's flag and the capacity rules
 BLOBS_TRUNCATED = 1
 BLOBS_MAX_CAP, BLOBS_MAX_SLOTS = 65536, 1 << 22
+# fpm_blobs_profile's `which`: the labelling kernels have no FPM_K_* index
+BLOB_TILE, BLOB_MERGE, BLOB_FLATTEN, BLOB_SLOTS, BLOB_FEATURES = 0, 1, 2, 3, 4
+BLOB_KERNEL_SYMBOLS = ["k_blob_tile", "k_blob_merge", "k_blob_flatten", "k_blob_slots", "k_blob_features"]
 
 
 class Params(C.Structure):
@@ -289,6 +292,14 @@ SIGNATURES = {
     "fpm_align_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_blobs_host": (C.c_int, [_U8P, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_last_blobs": (C.c_int, [_P] + [C.c_int32] * 7 + [C.POINTER(InspectStats), C.POINTER(BlobSummary), C.POINTER(Blob),
+                                                          C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_blobs_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)] + [C.c_int32] * 7 +
+                     [C.POINTER(InspectStats), C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32]),
+    "fpm_op_blobs": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
+                               C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_blobs_set_round": (C.c_int, [_P, C.c_int32]),
+    "fpm_blobs_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -16,6 +16,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -152,8 +153,10 @@ struct KProf {
     int64_t launches = 0, bytes = 0;
 };
 // Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
-// alignment's one (fpm_align_profile), which have no FPM_K_* index: FPM_K_COUNT stays what it is.
-enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfSlots };
+// alignment's one (fpm_align_profile) and the blob labelling's five (fpm_blobs_profile), which have no FPM_K_* index:
+// FPM_K_COUNT stays what it is.
+enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfBlobTile, kProfBlobMerge,
+       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfSlots };
 
 }  // namespace
 
@@ -239,6 +242,11 @@ struct fpm_ctx {
     PinBuf h_insacc;
     DevBuf d_alnacc;          // the alignment's per-hit records (fpm_align_*) and their host copy
     PinBuf h_alnacc;
+    // defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): the label and area planes of one round
+    // of images, the round's counters and records with their host copy, fpm_op_blobs' images and the labels' host copy
+    int blobs_round = 0;      // fpm_blobs_set_round: images per round, 0 = the engine's choice
+    DevBuf d_blobplanes, d_blobrec, d_blobimg;
+    PinBuf h_blobrec, h_bloblab;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -2516,14 +2524,16 @@ int model_band_ensure(fpm_ctx* ctx, int a, int kq) {
 }
 
 // The inspection of `poses` (n >= 1) against the model: the planes for (a, kq), one launch of k_model_inspect (after
-// the sums launch and the tables with FPM_COMPARE_NORMALIZE).  Returns when out (and img) are filled.
+// the sums launch and the tables with FPM_COMPARE_NORMALIZE).  Returns when out (and img) are filled.  keep_device: the
+// excess images are written to the pitched patch buffer also without img, and stay there (the blob entries label them).
 int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int a, int kq, int flags,
-                    fpm_inspect_stats* out, uint8_t* img, size_t row_stride, size_t patch_stride) {
+                    fpm_inspect_stats* out, uint8_t* img, size_t row_stride, size_t patch_stride,
+                    bool keep_device = false) {
     const int n = (int)poses.size();
     const bool norm = (flags & FPM_COMPARE_NORMALIZE) != 0;
     const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
     uint8_t* d = nullptr;   // the excess images: the context's pitched buffer, as for the host patches
-    if (img) {
+    if (img || keep_device) {
         HIP_TRY(ctx->d_patch.ensure(pbytes * (size_t)n));
         d = ctx->d_patch.as<uint8_t>();
     }
@@ -2555,7 +2565,7 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     HIP_TRY(hipGetLastError());
     InspectAcc* h = ctx->h_insacc.as<InspectAcc>();
     HIP_TRY(hipMemcpyAsync(h, ctx->d_insacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
-    if (d) {
+    if (img) {
         rc = copy_patches_out(ctx, r, (size_t)n, d, pitch, pbytes, img, row_stride, patch_stride);
         if (rc != FPM_OK) return rc;
     }
@@ -2577,6 +2587,133 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
                            (int64_t)sums[i].s[kCmpSumTT], (int64_t)sums[i].s[kCmpSumIT], true, &z, &s.gain, &s.offset, nullptr);
         }
     }
+    return FPM_OK;
+}
+
+// ---- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs) ----
+static_assert(sizeof(BlobRec) == sizeof(fpm_blob) && offsetof(BlobRec, hit) == offsetof(fpm_blob, hit) &&
+                  offsetof(BlobRec, seed) == offsetof(fpm_blob, seed) && offsetof(BlobRec, area) == offsetof(fpm_blob, area) &&
+                  offsetof(BlobRec, x0) == offsetof(fpm_blob, x0) && offsetof(BlobRec, y1) == offsetof(fpm_blob, y1) &&
+                  offsetof(BlobRec, max_value) == offsetof(fpm_blob, max_value) &&
+                  offsetof(BlobRec, sum_value) == offsetof(fpm_blob, sum_value) &&
+                  offsetof(BlobRec, sum_x) == offsetof(fpm_blob, sum_x) && offsetof(BlobRec, sum_y) == offsetof(fpm_blob, sum_y),
+              "the kernels' record is fpm_blob, field for field");
+static_assert(sizeof(BlobCount) == sizeof(BlobCounters) && offsetof(BlobCount, fg) == offsetof(BlobCounters, fg_pixels) &&
+                  offsetof(BlobCount, comps) == offsetof(BlobCounters, n_components) &&
+                  offsetof(BlobCount, qual) == offsetof(BlobCounters, n_qualifying) &&
+                  offsetof(BlobCount, largest) == offsetof(BlobCounters, largest_area),
+              "the kernels' counters are blobs_gather's");
+
+// Design constants, not measurements: the label and area planes of a round stay within 256 MiB (8 bytes per pixel and
+// image), its records within 64 MiB.
+constexpr size_t kBlobPlaneBudget = (size_t)256 << 20;
+constexpr size_t kBlobRecBudget = (size_t)64 << 20;
+
+struct BlobRun {
+    int n = 0, w = 0, h = 0, round = 0, cap_dev = 0;
+    size_t npx = 0, rec_off = 0;   // the records' offset behind the counters in d_blobrec / h_blobrec
+    bool labels = false;
+};
+
+// Everything a labelling call allocates, sized for its largest round.  It comes before the call's first launch: ensure()
+// frees and reallocates, so no buffer may grow between rounds, and pointers are taken only afterwards (blobs_run).
+int blobs_reserve(fpm_ctx* ctx, int n, int w, int h, int min_area, int cap_per_hit, bool labels, BlobRun* b) {
+    b->n = n; b->w = w; b->h = h; b->labels = labels;
+    b->npx = (size_t)w * h;
+    b->cap_dev = blobs_cap_dev(w, h, min_area, cap_per_hit);
+    size_t round = std::max<size_t>(1, kBlobPlaneBudget / (2 * sizeof(int32_t) * b->npx));
+    round = std::min(round, std::max<size_t>(1, kBlobRecBudget / (sizeof(BlobRec) * (size_t)b->cap_dev)));
+    if (ctx->blobs_round > 0) round = std::min(round, (size_t)ctx->blobs_round);
+    b->round = (int)std::min<size_t>(round, (size_t)std::min(n, 65535));
+    b->rec_off = round_up(sizeof(BlobCount) * (size_t)b->round, (size_t)256);
+    const size_t rec_bytes = b->rec_off + sizeof(BlobRec) * (size_t)b->round * b->cap_dev;
+    HIP_TRY(ctx->d_blobplanes.ensure(2 * sizeof(int32_t) * b->npx * b->round));
+    HIP_TRY(ctx->d_blobrec.ensure(rec_bytes));
+    HIP_TRY(ctx->h_blobrec.ensure(rec_bytes));
+    if (labels) HIP_TRY(ctx->h_bloblab.ensure(sizeof(int32_t) * b->npx * b->round));
+    return FPM_OK;
+}
+
+// Labels the n images at d_img (image i at d_img + i * img_stride, rows pitch apart) round by round after
+// blobs_reserve: counters and records cleared on the stream, the five launches, one copy of counters and records (and
+// of the labels) into the context's pinned buffers, then blobs_gather into the caller's memory.  Device results never go
+// straight into caller memory.
+int blobs_run(fpm_ctx* ctx, const BlobRun& b, const uint8_t* d_img, size_t pitch, size_t img_stride, int level,
+              int connectivity, int min_area, int cap_per_hit, fpm_blob_summary* summary, fpm_blob* out, int32_t* labels) {
+    hipStream_t st = ctx->stream;
+    int32_t* dL = ctx->d_blobplanes.as<int32_t>();
+    char* drec = ctx->d_blobrec.as<char>();
+    char* hrec = ctx->h_blobrec.as<char>();
+    const int32_t* hlab = b.labels ? ctx->h_bloblab.as<int32_t>() : nullptr;
+    for (int i0 = 0; i0 < b.n; i0 += b.round) {
+        const int nr = std::min(b.round, b.n - i0);
+        const size_t used = b.rec_off + sizeof(BlobRec) * (size_t)nr * b.cap_dev;
+        const int64_t px = (int64_t)nr * (int64_t)b.npx;
+        HIP_TRY(hipMemsetAsync(drec, 0, used, st));
+        BlobArgs a{};
+        a.img = d_img + (size_t)i0 * img_stride;
+        a.pitch = pitch; a.img_stride = img_stride;
+        a.n = nr; a.w = b.w; a.h = b.h;
+        a.level = level; a.conn8 = connectivity == 8 ? 1 : 0; a.min_area = min_area;
+        a.cap_dev = b.cap_dev; a.hit0 = i0;
+        a.L = dL;
+        a.A = dL + (size_t)b.round * b.npx;
+        a.cnt = (BlobCount*)drec;
+        a.rec = (BlobRec*)(drec + b.rec_off);
+        const int64_t tiles = (int64_t)nr * ((b.w + 63) / 64) * ((b.h + 15) / 16);
+        bool ok = true;
+        {   // the excess pixels read, L and A written
+            ProfScope ps(ctx, kProfBlobTile, 9 * px);
+            ok = launch_blob_tile(a, st);
+        }
+        if (ok) {   // the labels of the border pixels and of their neighbours beyond the border
+            ProfScope ps(ctx, kProfBlobMerge, tiles * (64 + 15 + 15) * 2 * (int64_t)sizeof(int32_t));
+            ok = launch_blob_merge(a, st);
+        }
+        if (ok) {   // L read and written (the area adds go to the roots)
+            ProfScope ps(ctx, kProfBlobFlatten, 8 * px);
+            ok = launch_blob_flatten(a, st);
+        }
+        if (ok) {   // L read (A at the roots)
+            ProfScope ps(ctx, kProfBlobSlots, 4 * px);
+            ok = launch_blob_slots(a, st);
+        }
+        if (ok) {   // L and the excess pixels read, A at the roots
+            ProfScope ps(ctx, kProfBlobFeatures, 5 * px);
+            ok = launch_blob_features(a, st);
+        }
+        if (!ok) { ctx->err = "too many tiles for one labelling launch"; return FPM_E_INVALID_ARG; }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(hrec, drec, used, hipMemcpyDeviceToHost, st));
+        if (hlab) HIP_TRY(hipMemcpyAsync((void*)hlab, dL, sizeof(int32_t) * (size_t)px, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        prof_collect(ctx);
+        blobs_gather((const BlobCounters*)hrec, (fpm_blob*)(hrec + b.rec_off), nr, b.cap_dev, min_area, cap_per_hit,
+                     out + (size_t)i0 * cap_per_hit, summary + i0);
+        if (hlab) {
+            int32_t* lab = labels + (size_t)i0 * b.npx;
+            for (int64_t k = 0; k < px; ++k) lab[k] = hlab[k] + 1;   // seed + 1, background 0
+        }
+    }
+    return FPM_OK;
+}
+
+// The inspection with its excess images kept in the pitched patch buffer, then the labelling of those images.
+int blobs_of_poses(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int a, int kq, int flags,
+                   int level, int connectivity, int min_area, int cap_per_hit, fpm_inspect_stats* stats,
+                   fpm_blob_summary* summary, fpm_blob* out) {
+    const int n = (int)poses.size();
+    BlobRun b;
+    int rc = blobs_reserve(ctx, n, r.w, r.h, min_area, cap_per_hit, false, &b);
+    if (rc != FPM_OK) return rc;
+    std::vector<fpm_inspect_stats> st((size_t)n);
+    rc = inspect_to_host(ctx, r, poses, a, kq, flags, st.data(), nullptr, 0, 0, true);
+    if (rc != FPM_OK) return rc;
+    const size_t pitch = round_up((size_t)r.w, (size_t)64);
+    rc = blobs_run(ctx, b, ctx->d_patch.as<uint8_t>(), pitch, pitch * (size_t)r.h, level, connectivity, min_area,
+                   cap_per_hit, summary, out, nullptr);
+    if (rc != FPM_OK) return rc;
+    if (stats) std::copy(st.begin(), st.end(), stats);
     return FPM_OK;
 }
 
@@ -2840,6 +2977,8 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_tacc.release(); ctx->h_tacc.release();
     ctx->d_model.release(); ctx->d_band.release(); ctx->d_insacc.release(); ctx->h_insacc.release();
     ctx->d_alnacc.release(); ctx->h_alnacc.release();
+    ctx->d_blobplanes.release(); ctx->d_blobrec.release(); ctx->d_blobimg.release();
+    ctx->h_blobrec.release(); ctx->h_bloblab.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -3461,6 +3600,111 @@ int fpm_model_learn(fpm_ctx* ctx) {
 int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
     if (!ctx || which < 0 || which > 2 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
     const KProf& p = ctx->kp[kProfModelTrain + which];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
+}
+
+// --- defect blobs on the device -----------------------------------------------------------
+static int blob_args(fpm_ctx* ctx, int64_t n, int32_t level, int32_t connectivity, int32_t min_area, int32_t cap_per_hit,
+                     const fpm_blob_summary* summary, const fpm_blob* out) {
+    if (const char* bad = blobs_bad_args(n, level, connectivity, min_area, cap_per_hit)) { ctx->err = bad; return FPM_E_INVALID_ARG; }
+    if (!summary || !out) { ctx->err = "null blob summary or record buffer"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+int fpm_last_blobs(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, int32_t level,
+                   int32_t connectivity, int32_t min_area, fpm_inspect_stats* stats, fpm_blob_summary* summary,
+                   fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = inspect_args(ctx, a, kq, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r, mr;
+    std::vector<PatchPose> poses;
+    rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = model_need(ctx, &mr);
+    if (rc == FPM_OK) rc = last_patches_begin(ctx, &mr, source, cap, n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    rc = blob_args(ctx, (int64_t)poses.size(), level, connectivity, min_area, cap_per_hit, summary, out);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return blobs_of_poses(ctx, r, poses, a, kq, flags, level, connectivity, min_area, cap_per_hit, stats, summary, out);
+}
+
+int fpm_blobs_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                 int32_t a, int32_t kq, int32_t flags, int32_t level, int32_t connectivity, int32_t min_area,
+                 fpm_inspect_stats* stats, fpm_blob_summary* summary, fpm_blob* out, int32_t cap_per_hit) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = inspect_args(ctx, a, kq, flags);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r, mr;
+    rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = model_need(ctx, &mr);
+    if (rc == FPM_OK) rc = compare_rect(ctx, &mr, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    rc = blob_args(ctx, n_poses, level, connectivity, min_area, cap_per_hit, summary, out);
+    if (rc != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return blobs_of_poses(ctx, r, poses, a, kq, flags, level, connectivity, min_area, cap_per_hit, stats, summary, out);
+}
+
+int fpm_op_blobs(fpm_ctx* ctx, const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
+                 int32_t connectivity, int32_t min_area, fpm_blob_summary* summary, fpm_blob* out, int32_t cap_per_hit,
+                 int32_t* labels) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (ctx->pending) { ctx->err = kInFlight; return FPM_E_INVALID_ARG; }
+    if (!images || n < 1 || n > 65535 || w < 1 || h < 1 || (int64_t)w * h > ((int64_t)1 << 22) || stride < (size_t)w ||
+        stride > (size_t)INT32_MAX) {
+        ctx->err = "bad blob images";
+        return FPM_E_INVALID_ARG;
+    }
+    int rc = blob_args(ctx, n, level, connectivity, min_area, cap_per_hit, summary, out);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct ProfOff {   // the launches below are not an inspection's: the profile counters stay as they were
+        fpm_ctx* c; bool was;
+        explicit ProfOff(fpm_ctx* x) : c(x), was(x->prof) { c->prof = false; }
+        ~ProfOff() { c->prof = was; }
+    } prof_off(ctx);
+    const size_t pitch = round_up(stride, (size_t)64), rows = (size_t)n * h;
+    BlobRun b;
+    rc = blobs_reserve(ctx, n, w, h, min_area, cap_per_hit, labels != nullptr, &b);
+    if (rc != FPM_OK) return rc;
+    // all stride bytes of every row, as the caller has them (the kernels mask by u < w); of the last row of the last
+    // image only the w bytes fpm_blobs_host's addressing guarantees.  One copy from the host: into place when the
+    // stride is the pitch, else to a staging area behind the images and from there row by row on the device (a 2D copy
+    // from pageable memory goes row by row over the bus)
+    const size_t host_bytes = (rows - 1) * stride + (size_t)w;
+    HIP_TRY(ctx->d_blobimg.ensure(pitch * rows + (pitch == stride ? 0 : round_up(host_bytes, (size_t)64))));
+    uint8_t* d = ctx->d_blobimg.as<uint8_t>();
+    if (pitch == stride) {
+        HIP_TRY(hipMemcpyAsync(d, images, host_bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        uint8_t* stage = d + pitch * rows;
+        HIP_TRY(hipMemcpyAsync(stage, images, host_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (rows > 1)
+            HIP_TRY(hipMemcpy2DAsync(d, pitch, stage, stride, stride, rows - 1, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d + (rows - 1) * pitch, stage + (rows - 1) * stride, (size_t)w, hipMemcpyDeviceToDevice,
+                               ctx->stream));
+    }
+    return blobs_run(ctx, b, d, pitch, pitch * (size_t)h, level, connectivity, min_area, cap_per_hit, summary, out, labels);
+}
+
+int fpm_blobs_set_round(fpm_ctx* ctx, int32_t images) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (images < 0) { ctx->err = "images per round must be >= 0"; return FPM_E_INVALID_ARG; }
+    ctx->blobs_round = images;
+    return FPM_OK;
+}
+
+int fpm_blobs_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || which < 0 || which > 4 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfBlobTile + which];
     *ms = p.ms;
     *launches = p.launches;
     *bytes = p.bytes;

@@ -610,6 +610,21 @@ void blobs_tail(fpm_blob* recs, int64_t m, int64_t missing, int64_t fg_pixels, i
     summary->reserved = 0;
 }
 
+int32_t blobs_cap_dev(int32_t w, int32_t h, int32_t min_area, int32_t cap_per_hit) {
+    const int64_t px = (int64_t)w * h;
+    return (int32_t)std::min<int64_t>(cap_per_hit, std::max<int64_t>(1, std::min((px + 1) / 2, px / min_area)));
+}
+
+void blobs_gather(const BlobCounters* counters, fpm_blob* recs, int32_t images, int32_t cap_dev, int32_t min_area,
+                  int32_t cap_per_hit, fpm_blob* out, fpm_blob_summary* summary) {
+    for (int32_t i = 0; i < images; ++i) {
+        const BlobCounters& c = counters[i];
+        const int64_t valid = std::min<int64_t>(std::max(c.n_qualifying, 0), cap_dev);
+        blobs_tail(recs + (size_t)i * cap_dev, valid, c.n_qualifying - valid, c.fg_pixels, c.n_components, c.largest_area,
+                   min_area, cap_per_hit, out + (size_t)i * cap_per_hit, summary + i);
+    }
+}
+
 }  // namespace fpm
 
 // Two-pass union-find over one image at a time: pass 1 links every foreground pixel to its left and upper neighbours

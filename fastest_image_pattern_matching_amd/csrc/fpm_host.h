@@ -52,5 +52,18 @@ void blobs_tail(fpm_blob* recs, int64_t m, int64_t missing, int64_t fg_pixels, i
                 int32_t min_area, int32_t cap, fpm_blob* out, fpm_blob_summary* summary);
 // the argument rules the blob entries share; nullptr = fine, else what is wrong
 const char* blobs_bad_args(int64_t n, int32_t level, int32_t connectivity, int32_t min_area, int32_t cap_per_hit);
+// What one round of the device labelling leaves per image beside its records: the foreground
+// pixels, all components, the qualifying ones (the true count, also beyond cap_dev) and the largest area.
+struct BlobCounters {
+    int32_t fg_pixels, n_components, n_qualifying, largest_area;
+};
+// Record slots per image of the device labelling: no w x h image has more components of at least min_area pixels than
+// min(ceil(w h / 2), w h / min_area), so slots beyond that (or beyond cap_per_hit) would never be drawn.
+int32_t blobs_cap_dev(int32_t w, int32_t h, int32_t min_area, int32_t cap_per_hit);
+// One round's device output into the caller's memory, through blobs_tail: image i of the round has its first
+// min(n_qualifying, cap_dev) records valid at recs + i * cap_dev (any order; sorted in place here) and goes to
+// out + i * cap_per_hit and summary + i.  Pure host code: every write into caller memory of a device blob entry is here.
+void blobs_gather(const BlobCounters* counters, fpm_blob* recs, int32_t images, int32_t cap_dev, int32_t min_area,
+                  int32_t cap_per_hit, fpm_blob* out, fpm_blob_summary* summary);
 
 }  // namespace fpm

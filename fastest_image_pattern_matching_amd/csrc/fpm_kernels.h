@@ -318,6 +318,44 @@ struct AlignArgs {
 // k_patch_align, k_patch_warp's grid; the table form when luts is set.  Returns false, launching nothing, for a grid past
 // 2^31 - 1 or a rectangle beyond the caps.
 bool launch_patch_align(AlignArgs c, hipStream_t st);
+// ---- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): connected
+// components of n pitched u8 images of one size, by a union-find per 64 x 16 tile in LDS and a merge of the tile pieces
+// in device memory.  A label is the row-major index v * w + u, within its image, of a pixel of the same component that is
+// not larger than the pixel's own; after k_blob_flatten it is the component's seed.
+// The device record: fpm_blob, field for field (the engine asserts the offsets).
+struct BlobRec {
+    int32_t hit, seed, area, x0, y0, x1, y1, max_value;
+    unsigned long long sum_value, sum_x, sum_y;   // 64-bit integer atomic adds
+};
+static_assert(sizeof(BlobRec) == 56, "the device record is fpm_blob, field for field");
+// Per image, zero-filled before the launches: foreground pixels, all components, the components of at least min_area
+// pixels (the true count, also when it exceeds cap_dev) and the largest area.
+struct BlobCount {
+    int32_t fg, comps, qual, largest;
+};
+struct BlobArgs {
+    const uint8_t* img;      // image i at img + i * img_stride, rows pitch bytes apart; pitch is a multiple of 64, so a
+    size_t pitch;            // tile's dwords lie inside the row.  The bytes at u >= w are NOT clean: masked by u < w
+    size_t img_stride;
+    int32_t n, w, h;         // images of this round; w * h <= 2^22
+    int32_t tiles_x, tiles_y;   // 64 x 16 tiles per image (set by the launchers)
+    int32_t level;           // foreground: e > level
+    int32_t conn8;           // 1: 8-connectivity, 0: 4-connectivity
+    int32_t min_area;
+    int32_t cap_dev;         // record slots per image
+    int32_t hit0;            // BlobRec::hit of image 0 of the round
+    int32_t* L;              // labels, dense [n][h][w]; -1 = background
+    int32_t* A;              // areas at the roots after k_blob_flatten; the slot (or -1) at the roots after k_blob_slots
+    BlobCount* cnt;          // [n]
+    BlobRec* rec;            // [n][cap_dev], zero-filled before the launches
+};
+// One launch each, in this order, on one stream: the kernel boundaries publish the labels.  Every launcher returns
+// false, launching nothing, for a grid past 2^31 - 1.
+bool launch_blob_tile(BlobArgs a, hipStream_t st);
+bool launch_blob_merge(BlobArgs a, hipStream_t st);
+bool launch_blob_flatten(const BlobArgs& a, hipStream_t st);
+bool launch_blob_slots(const BlobArgs& a, hipStream_t st);
+bool launch_blob_features(const BlobArgs& a, hipStream_t st);
 // ---- learning on the device (fpm_learn_device / fpm_learn_at / fpm_learn_hit): what learnPattern
 // derives from a template pyramid that already lies in the template slab, in one launch over all its levels.
 constexpr int kTmplPrepMaxLevels = 16;   // a 2^26-pixel template at min_reduce_area 1 has 13 levels above level 0

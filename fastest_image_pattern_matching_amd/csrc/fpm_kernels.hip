@@ -3334,6 +3334,360 @@ bool launch_model_inspect(InspectArgs c, hipStream_t st) {
     return true;
 }
 
+// ============================================================================================== defect blobs
+// Connected components of pitched u8 images (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): a
+// union-find per 64 x 16 tile in LDS, a merge of the tile pieces across the tile borders in device memory, a flatten
+// with the areas, the record slots, the features.  Everything is kept in exact integers and every union links the
+// larger index to the smaller, so labels, areas and records are the same for every schedule; only which qualifying
+// component draws which record slot is not.
+//
+// The invariant every find below rests on, in LDS and in device memory alike: the label stored at p is the index of a
+// pixel of p's component, not larger than p; a root is its own label.  A label only ever goes down, so a chain of labels
+// is strictly decreasing and ends at a root, whichever of the concurrent values a load returns.
+constexpr uint32_t kBlobNone = 0xffffffffu;   // background in the tile's LDS table
+
+__device__ __forceinline__ uint32_t blob_lds_find(volatile uint32_t* par, uint32_t x) {
+    for (;;) {   // strictly decreasing: at most 1023 steps
+        const uint32_t q = par[x];
+        if (q == x) return x;
+        x = q;
+    }
+}
+
+// Lock-free union of the pieces of two foreground pixels of one tile.  No iteration waits for another lane: it ends
+// (same root, or this lane's atomic linked the root a), or it goes on from a strictly smaller a.
+__device__ __forceinline__ void blob_lds_unite(volatile uint32_t* par, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = blob_lds_find(par, a);
+        b = blob_lds_find(par, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin((uint32_t*)&par[a], b);
+        if (old == a) return;   // a was a root and now points to b
+        a = old;                // another lane linked a first (old < a): old and b are still to be united
+    }
+}
+
+// k_blob_tile: one workgroup per (image, 64 x 16 tile), k_model_inspect's tile and lane layout (a lane's four pixels
+// are one aligned dword of the pitched image).  The tile's union-find lives in LDS as one 32-bit word per pixel --
+// ds_min_u32 is the native form; the LDS has no 16-bit atomic minimum, and 4 KB per workgroup bounds no occupancy.
+// Pixels at u >= w or v >= h are background whatever the buffer holds there.  Writes L (the global row-major index of
+// the tile-local root: local row-major order is monotone in the global one, so it is the smallest index of the piece; -1
+// for background) and A = 0 for every pixel of the image, and adds the tile's foreground count to the image's.
+__global__ __launch_bounds__(256) void k_blob_tile(const BlobArgs a) {
+    __shared__ uint32_t par_s[kPatchTw * kPatchTh];
+    __shared__ int32_t wsum[4];
+    volatile uint32_t* par = par_s;
+    const int tid = threadIdx.x;
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int i = blockIdx.x / tiles, t = blockIdx.x - i * tiles;
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = tx * kPatchTw + gx, y = ty * kPatchTh + r;
+    const int left = a.w - x;
+    const int nu = y >= a.h || left <= 0 ? 0 : (left < 4 ? left : 4);
+    uint32_t ew = 0;
+    if (nu > 0) ew = *(const uint32_t*)(a.img + (size_t)i * a.img_stride + (size_t)y * a.pitch + x);
+    const uint32_t l0 = (uint32_t)(r * kPatchTw + gx);
+    uint32_t fg = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const bool f = u < nu && (int)((ew >> (8 * u)) & 255u) > a.level;
+        fg |= (uint32_t)f << u;
+        par[l0 + u] = f ? l0 + u : kBlobNone;
+    }
+    __syncthreads();
+    // the half-neighbourhood inside the tile: W and N, with 8-connectivity also NW and NE.  A background entry stays
+    // kBlobNone for good, so the test does not depend on the unions under way
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (!((fg >> u) & 1u)) continue;
+        const uint32_t l = l0 + u;
+        const int c = gx + u;
+        if (c > 0 && par[l - 1] != kBlobNone) blob_lds_unite(par, l, l - 1);
+        if (r > 0) {
+            if (par[l - kPatchTw] != kBlobNone) blob_lds_unite(par, l, l - kPatchTw);
+            if (a.conn8) {
+                if (c > 0 && par[l - kPatchTw - 1] != kBlobNone) blob_lds_unite(par, l, l - kPatchTw - 1);
+                if (c < kPatchTw - 1 && par[l - kPatchTw + 1] != kBlobNone) blob_lds_unite(par, l, l - kPatchTw + 1);
+            }
+        }
+    }
+    __syncthreads();
+    const size_t plane = (size_t)i * a.w * a.h;
+    int32_t* Li = a.L + plane;
+    int32_t* Ai = a.A + plane;
+    for (int u = 0; u < nu; ++u) {
+        const int p = y * a.w + x + u;
+        int32_t lab = -1;
+        if ((fg >> u) & 1u) {
+            const uint32_t root = blob_lds_find(par, l0 + u);
+            lab = (ty * kPatchTh + (int)(root >> 6)) * a.w + tx * kPatchTw + (int)(root & 63u);
+        }
+        Li[p] = lab;
+        Ai[p] = 0;
+    }
+    int cnt = __popc(fg);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (total) atomicAdd(&a.cnt[i].fg, total);
+    }
+}
+
+// The labels in device memory while other workgroups, on other XCDs, unite on them: an XCD's L2 is not coherent with
+// another's and a plain load can return a line cached before the launch, so every access is an agent-scope atomic.
+__device__ __forceinline__ int32_t blob_load(const int32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int32_t blob_find(const int32_t* L, int32_t x) {
+    for (;;) {   // strictly decreasing, by the invariant above
+        const int32_t q = blob_load(L + x);
+        if (q == x) return x;
+        x = q;
+    }
+}
+
+// The union across a tile border.  No iteration waits for another workgroup: an iteration ends (same root, or this
+// thread's own atomic lowered the label of the root a to b), or it goes on from old < a, a strictly smaller index.  Only
+// labels of the same component are ever stored, and only smaller ones, which is all the correctness of find needs.
+__device__ __forceinline__ void blob_unite(int32_t* L, int32_t a, int32_t b) {
+    for (;;) {
+        a = blob_find(L, a);
+        b = blob_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        const int32_t old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// k_blob_merge: one 128-thread workgroup per (image, tile), one lane per pixel whose half-neighbourhood reaches into
+// another tile: the top row (lanes 0 .. 63), rows 1 .. 15 of the left column (64 .. 78) and, with 8-connectivity, rows
+// 1 .. 15 of the right column (79 .. 93), whose NE neighbour lies in the next tile.  Each unites its pixel with the
+// foreground half-neighbours that lie in another tile.
+constexpr int kBlobMergeThreads = 128;
+__global__ __launch_bounds__(kBlobMergeThreads) void k_blob_merge(const BlobArgs a) {
+    const int tid = threadIdx.x;
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int i = blockIdx.x / tiles, t = blockIdx.x - i * tiles;
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    int x, y;
+    if (tid < kPatchTw) { x = tx * kPatchTw + tid; y = ty * kPatchTh; }
+    else if (tid < kPatchTw + kPatchTh - 1) { x = tx * kPatchTw; y = ty * kPatchTh + tid - (kPatchTw - 1); }
+    else if (tid < kPatchTw + 2 * (kPatchTh - 1) && a.conn8) {
+        x = tx * kPatchTw + kPatchTw - 1;
+        y = ty * kPatchTh + tid - (kPatchTw + kPatchTh - 2);
+    } else return;
+    if (x >= a.w || y >= a.h) return;
+    int32_t* Li = a.L + (size_t)i * a.w * a.h;
+    const int32_t p = y * a.w + x;
+    if (blob_load(Li + p) < 0) return;   // background is -1 for good
+    auto link = [&](int qx, int qy) {
+        if (qx < 0 || qx >= a.w || qy < 0) return;
+        if ((qx >> 6) == (x >> 6) && (qy >> 4) == (y >> 4)) return;   // the same tile: k_blob_tile linked them
+        const int32_t q = qy * a.w + qx;
+        if (blob_load(Li + q) >= 0) blob_unite(Li, p, q);
+    };
+    link(x - 1, y);
+    link(x, y - 1);
+    if (a.conn8) {
+        link(x - 1, y - 1);
+        link(x + 1, y - 1);
+    }
+}
+
+// k_blob_flatten, a launch of its own (the kernel boundary publishes the merges): L[p] = the root of p, and one count
+// per pixel into A[root].  A wave's 64 pixels are consecutive in row-major order and mostly of one component: where all
+// its foreground lanes share the root one lane adds their number, otherwise every lane adds 1.  Other lanes store roots
+// into L while this one walks a chain; a stored root is a label of the same component, so the walk ends at the same root.
+__global__ __launch_bounds__(256) void k_blob_flatten(const BlobArgs a) {
+    const int npx = a.w * a.h;
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    const size_t plane = (size_t)i * npx;
+    int32_t* Li = a.L + plane;
+    const int32_t l = p < npx ? Li[p] : -1;
+    const bool fg = l >= 0;
+    int32_t root = -1;
+    if (fg) {
+        root = blob_find(Li, l);
+        if (root != l) __hip_atomic_store(Li + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const uint64_t m = __ballot(fg);
+    if (!m) return;
+    const int lead = __ffsll((long long)m) - 1;
+    const int32_t r0 = __shfl(root, lead, 64);
+    int32_t* Ai = a.A + plane;
+    if (__all(!fg || root == r0)) {
+        if ((int)(threadIdx.x & 63) == lead) atomicAdd(Ai + r0, __popcll(m));
+    } else if (fg) {
+        atomicAdd(Ai + root, 1);
+    }
+}
+
+// k_blob_slots, over the roots (L[p] == p): counts the components, takes the largest area, and draws a record slot for
+// every root of at least min_area pixels -- one atomic per wave for each.  The qualifying counter keeps the true count;
+// a root whose slot is below cap_dev initialises its record (an empty box) and leaves the slot in A[p], every other
+// root leaves -1 there.
+__global__ __launch_bounds__(256) void k_blob_slots(const BlobArgs a) {
+    const int npx = a.w * a.h;
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const size_t plane = (size_t)i * npx;
+    int32_t* Ai = a.A + plane;
+    const bool isroot = p < npx && a.L[plane + p] == p;
+    const int32_t area = isroot ? Ai[p] : 0;
+    const uint64_t m = __ballot(isroot);
+    if (!m) return;
+    int32_t mx = area;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) { const int32_t o = __shfl_xor(mx, s, 64); mx = o > mx ? o : mx; }
+    BlobCount* c = a.cnt + i;
+    if (lane == __ffsll((long long)m) - 1) {
+        atomicAdd(&c->comps, __popcll(m));
+        atomicMax(&c->largest, mx);
+    }
+    const bool q = isroot && area >= a.min_area;
+    const uint64_t mq = __ballot(q);
+    int32_t base = 0;
+    if (mq) {
+        const int leadq = __ffsll((long long)mq) - 1;
+        if (lane == leadq) base = atomicAdd(&c->qual, __popcll(mq));
+        base = __shfl(base, leadq, 64);
+    }
+    if (!isroot) return;
+    int32_t slot = -1;
+    if (q) {
+        const int32_t s = base + __popcll(mq & ((1ull << lane) - 1ull));
+        if (s < a.cap_dev) {
+            slot = s;
+            BlobRec* rec = a.rec + (size_t)i * a.cap_dev + s;
+            rec->hit = a.hit0 + i;
+            rec->seed = p;
+            rec->area = area;
+            rec->x0 = a.w; rec->y0 = a.h; rec->x1 = -1; rec->y1 = -1;
+            rec->max_value = 0;
+            rec->sum_value = 0; rec->sum_x = 0; rec->sum_y = 0;
+        }
+    }
+    Ai[p] = slot;
+}
+
+// k_blob_features: every foreground pixel whose root holds a slot adds itself to the record: the box and max_value by
+// integer minima and maxima, the three sums by 64-bit integer adds.  The wave aggregation is k_blob_flatten's: where all
+// the contributing lanes share the root the wave folds its pixels first and one lane issues the eight atomics.
+__global__ __launch_bounds__(256) void k_blob_features(const BlobArgs a) {
+    const int npx = a.w * a.h;
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    const size_t plane = (size_t)i * npx;
+    const int32_t l = p < npx ? a.L[plane + p] : -1;
+    const int32_t slot = l >= 0 ? a.A[plane + l] : -1;
+    const bool act = slot >= 0;
+    const uint64_t m = __ballot(act);
+    if (!m) return;
+    int32_t x = 0, y = 0, e = 0;
+    if (act) {
+        y = p / a.w;
+        x = p - y * a.w;
+        e = a.img[(size_t)i * a.img_stride + (size_t)y * a.pitch + x];
+    }
+    const int lead = __ffsll((long long)m) - 1;
+    const int32_t l0 = __shfl(l, lead, 64);
+    if (__all(!act || l == l0)) {
+        int32_t x0 = act ? x : INT_MAX, y0 = act ? y : INT_MAX, x1 = act ? x : -1, y1 = act ? y : -1, em = e;
+        uint32_t se = (uint32_t)e, sx = (uint32_t)x, sy = (uint32_t)y;   // 64 pixels: 64 * 2^22 fits
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            int32_t o;
+            o = __shfl_xor(x0, s, 64); x0 = o < x0 ? o : x0;
+            o = __shfl_xor(y0, s, 64); y0 = o < y0 ? o : y0;
+            o = __shfl_xor(x1, s, 64); x1 = o > x1 ? o : x1;
+            o = __shfl_xor(y1, s, 64); y1 = o > y1 ? o : y1;
+            o = __shfl_xor(em, s, 64); em = o > em ? o : em;
+            se += __shfl_xor(se, s, 64);
+            sx += __shfl_xor(sx, s, 64);
+            sy += __shfl_xor(sy, s, 64);
+        }
+        if ((int)(threadIdx.x & 63) == lead) {
+            BlobRec* rec = a.rec + (size_t)i * a.cap_dev + slot;
+            atomicMin(&rec->x0, x0); atomicMin(&rec->y0, y0);
+            atomicMax(&rec->x1, x1); atomicMax(&rec->y1, y1);
+            atomicMax(&rec->max_value, em);
+            atomicAdd(&rec->sum_value, (unsigned long long)se);
+            atomicAdd(&rec->sum_x, (unsigned long long)sx);
+            atomicAdd(&rec->sum_y, (unsigned long long)sy);
+        }
+    } else if (act) {
+        BlobRec* rec = a.rec + (size_t)i * a.cap_dev + slot;
+        atomicMin(&rec->x0, x); atomicMin(&rec->y0, y);
+        atomicMax(&rec->x1, x); atomicMax(&rec->y1, y);
+        atomicMax(&rec->max_value, e);
+        atomicAdd(&rec->sum_value, (unsigned long long)e);
+        atomicAdd(&rec->sum_x, (unsigned long long)x);
+        atomicAdd(&rec->sum_y, (unsigned long long)y);
+    }
+}
+
+static bool blob_tile_grid(BlobArgs& a, unsigned* grid) {
+    a.tiles_x = (a.w + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.h + kPatchTh - 1) / kPatchTh;
+    const int64_t g = (int64_t)a.n * a.tiles_x * a.tiles_y;
+    *grid = (unsigned)g;
+    return g <= INT_MAX;
+}
+
+bool launch_blob_tile(BlobArgs a, hipStream_t st) {
+    unsigned g;
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return true;
+    if (!blob_tile_grid(a, &g)) return false;
+    hipLaunchKernelGGL(k_blob_tile, dim3(g), dim3(256), 0, st, a);
+    return true;
+}
+
+bool launch_blob_merge(BlobArgs a, hipStream_t st) {
+    unsigned g;
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return true;
+    if (!blob_tile_grid(a, &g)) return false;
+    hipLaunchKernelGGL(k_blob_merge, dim3(g), dim3(kBlobMergeThreads), 0, st, a);
+    return true;
+}
+
+// the per-pixel kernels: 256 pixels per workgroup along x, the image along y (at most 65535)
+static bool blob_pixel_grid(const BlobArgs& a, dim3* g) {
+    if (a.n > 65535) return false;
+    *g = dim3((unsigned)(((int64_t)a.w * a.h + 255) / 256), (unsigned)a.n);
+    return true;
+}
+
+bool launch_blob_flatten(const BlobArgs& a, hipStream_t st) {
+    dim3 g;
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return true;
+    if (!blob_pixel_grid(a, &g)) return false;
+    hipLaunchKernelGGL(k_blob_flatten, g, dim3(256), 0, st, a);
+    return true;
+}
+
+bool launch_blob_slots(const BlobArgs& a, hipStream_t st) {
+    dim3 g;
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return true;
+    if (!blob_pixel_grid(a, &g)) return false;
+    hipLaunchKernelGGL(k_blob_slots, g, dim3(256), 0, st, a);
+    return true;
+}
+
+bool launch_blob_features(const BlobArgs& a, hipStream_t st) {
+    dim3 g;
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return true;
+    if (!blob_pixel_grid(a, &g)) return false;
+    hipLaunchKernelGGL(k_blob_features, g, dim3(256), 0, st, a);
+    return true;
+}
+
 // ============================================================================================== template prep
 // What learnPattern derives from the template pyramid (fpm_learn's host block), for a pyramid that lies in the template
 // slab: the i8 MFMA operand T ^ 0x80, the per-row sums of T and the exact sum of T and of T^2 per level, one launch over

@@ -1171,6 +1171,96 @@ class TemplateMatcher:
             self._patch_fail(rc, "inspect_at")
         return (stats, img) if image else stats
 
+    # -- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs) -----------------------------------
+    def last_blobs(self, source: int = 0, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
+                   level: int = 0, min_area: int = 4, connectivity: int = 8, cap: int = 64, stats: bool = False):
+        """The defect list of every result of the last search (fpm_last_blobs): last_inspect's excess images cut into
+        connected components where they lie, on the device -- no image crosses the host.  Returns what
+        ``blobs_host(last_inspect(..., image=True)[1], level, min_area, connectivity, cap)`` returns, ``(summary,
+        blobs)``, one summary row and one BLOB_DTYPE array per result of ``source`` in result order (``source=-1``: all
+        sources); of a truncated hit any ``cap`` of its qualifying components come back, in ascending seed.
+        ``stats=True``: also last_inspect's rows, ``(summary, blobs, stats)``."""
+        a, kq = model_thresholds(abs_threshold, k)
+        self._model_size("last_blobs")
+        flags = L.COMPARE_NORMALIZE if normalize else 0
+        args = (int(level), int(connectivity), int(min_area))
+        n = C.c_int32()
+        rc = self._lib.fpm_last_blobs(self._ctx, int(source), a, kq, flags, *args, None, None, None, int(cap), 0,
+                                      C.byref(n))
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_blobs")
+        rows = np.zeros(n.value, INSPECT_DTYPE)
+        summary, recs, _, _ = _blob_buffers(n.value, 0, 0, cap, False)
+        if n.value:
+            rc = self._lib.fpm_last_blobs(self._ctx, int(source), a, kq, flags, *args,
+                                          rows.ctypes.data_as(C.POINTER(L.InspectStats)),
+                                          summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                          recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), n.value, C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_blobs")
+        out = _blob_result(summary, recs, None, False)
+        return out + (rows,) if stats else out
+
+    def blobs_at(self, src_index, lts, angles, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
+                 level: int = 0, min_area: int = 4, connectivity: int = 8, cap: int = 64, stats: bool = False):
+        """last_blobs at poses the caller supplies, on the staged sources (fpm_blobs_at); poses as patches_at."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        a, kq = model_thresholds(abs_threshold, k)
+        self._model_size("blobs_at")
+        n = len(idx)
+        rows = np.zeros(n, INSPECT_DTYPE)
+        summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
+        rc = self._lib.fpm_blobs_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                    n, a, kq, L.COMPARE_NORMALIZE if normalize else 0, int(level), int(connectivity),
+                                    int(min_area), rows.ctypes.data_as(C.POINTER(L.InspectStats)),
+                                    summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                    recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "blobs_at")
+        out = _blob_result(summary, recs, None, False)
+        return out + (rows,) if stats else out
+
+    def op_blobs(self, images, level: int = 0, min_area: int = 4, connectivity: int = 8, cap: int = 64,
+                 labels: bool = False):
+        """blobs_host's arguments and results through the labelling kernels (fpm_op_blobs, parity vehicle): needs no
+        template, sources or model and changes none of them.  ``images``: (h, w) or (n, h, w) uint8; a view with unit
+        pixel stride whose rows and images are evenly spaced (a padded batch cut to its width) is uploaded with its row
+        stride as it is, padding included."""
+        a = np.asarray(images)
+        if a.dtype != np.uint8:
+            a = _blob_images(a)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.size == 0:
+            raise ValueError("images: a (h, w) or (n, h, w) uint8 array with at least one pixel expected")
+        n, h, w = a.shape
+        stride = a.strides[1]
+        if a.strides[2] != 1 or stride < w or (n > 1 and a.strides[0] != stride * h) or h == 1:
+            a = np.ascontiguousarray(a)
+            stride = w
+        summary, recs, lab, plab = _blob_buffers(n, h, w, cap, labels)
+        rc = self._lib.fpm_op_blobs(self._ctx, C.cast(a.ctypes.data, C.POINTER(C.c_uint8)), n, w, h, stride, int(level),
+                                    int(connectivity), int(min_area), summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                    recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), plab)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "op_blobs")
+        return _blob_result(summary, recs, lab, labels)
+
+    def blobs_set_round(self, images: int = 0):
+        """Images per round of the labelling launches (fpm_blobs_set_round); 0 = the engine's choice.  The results do
+        not depend on it: it is there for tests."""
+        if self._lib.fpm_blobs_set_round(self._ctx, int(images)) != L.FPM_OK:
+            raise ValueError(f"blobs_set_round({images!r}): a count >= 0 expected")
+
+    def blobs_profile(self, which: int):
+        """``(ms, launches, bytes)`` of L.BLOB_TILE .. L.BLOB_FEATURES, collected under profile(True) and cleared by
+        profile_reset (fpm_blobs_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_blobs_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError(f"fpm_blobs_profile({which}) failed")
+        return ms.value, n.value, b.value
+
     def model_learn(self):
         """Learns the model's mean image as the new template, on the device (fpm_model_learn): re-teach from many good
         parts instead of one.  State afterwards as after learn_at; the model survives with the rectangle (0, 0, w, h).

@@ -535,8 +535,8 @@ int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t
  * one-pixel excesses and one 40-pixel scratch are the same record, two defects in opposite corners one box the size of
  * the part.  The step after it segments the excess image into connected regions, drops those below a minimum area and
  * reports each with its area, box, centroid sums and strength.  This block states that contract and gives its host
- * entry, fpm_blobs_host, which takes the images fpm_last_inspect / fpm_inspect_at write (or any u8 images).  Entries
- * that label where the excess images lie, on the device, are not part of the library yet.
+ * entry, fpm_blobs_host, which takes the images fpm_last_inspect / fpm_inspect_at write (or any u8 images).  The entries
+ * that label where the excess images lie, on the device, follow it ("defect blobs on the device").
  * Foreground.  The input is a w x h image of u8 values e(u, v) and a level t = 0 .. 254; pixel (u, v) is foreground iff
  * e(u, v) > t.
  * Connectivity.  4 (edge neighbours) or 8 (edge and corner neighbours); a component is a maximal connected set of
@@ -583,6 +583,49 @@ typedef struct fpm_blob_summary {
 int fpm_blobs_host(const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
                    int32_t connectivity, int32_t min_area, fpm_blob_summary* summary, fpm_blob* out,
                    int32_t cap_per_hit, int32_t* labels);
+
+/* --- defect blobs on the device: the hits cut into blobs where their excess images lie (no reference equivalent) -------
+ * The contract is "defect blobs" above, unchanged: foreground e > level, connectivity 4 or 8, a component named by its
+ * seed, fpm_blob and fpm_blob_summary, filter, order, capacity and FPM_BLOBS_TRUNCATED.  Of a truncated image these
+ * entries return cap_per_hit exact records of distinct qualifying components in ascending seed, not necessarily the
+ * first by seed (the record slots are drawn in parallel); everything else is fully determined.
+ * fpm_last_blobs / fpm_blobs_at run the inspection of fpm_last_inspect / fpm_inspect_at with its excess images written to
+ * the context's pitched patch buffer, label them there and bring back the records: no image crosses the host.  source,
+ * cap (hits), *n, a, kq, flags, the state and model rules and every error are those of fpm_last_inspect /
+ * fpm_inspect_at (cap = 0 with out = NULL asks for the count; a cap below the count is FPM_E_CAPACITY with nothing
+ * written); level, connectivity, min_area and cap_per_hit are checked as fpm_blobs_host checks them, with the actual
+ * number of hits.  summary holds one entry per hit, out cap_per_hit records per hit; stats, when not NULL, receives what
+ * fpm_last_inspect would write.  A call that fails launches nothing and writes nothing.  The calls change no search
+ * state: results, poses, candidates, staged sources, template and model stay as they were.
+ * fpm_op_blobs is fpm_blobs_host's signature behind a context: the labelling kernels alone on caller-supplied images
+ * (parity vehicle).  It needs no template, sources or model and leaves plan, sources, results, model and the profile
+ * counters as they were.  The images are uploaded with the caller's row stride (the device pitch is stride rounded up to
+ * 64, all stride bytes of a row are copied), so whatever lies between w and stride lies beside the image on the device
+ * too: the kernels mask by u < w.
+ * Launches.  Per round of images five kernels, none part of a search or of a captured graph: k_blob_tile (a union-find
+ * per 64 x 16 tile), k_blob_merge (the tile pieces united across tile borders), k_blob_flatten (every pixel to its seed,
+ * the areas), k_blob_slots (counts, record slots), k_blob_features (box, maximum and sums).  Scratch is 8 bytes per
+ * pixel and image; a round takes as many images as keep it within 256 MiB (fpm_blobs_set_round overrides the number,
+ * for tests; the results do not depend on it).  Integer arithmetic throughout: the results are the same for every
+ * schedule.  Additive entries: FPM_ABI_VERSION is unchanged. */
+/* the hits of the last search against the model, cut into blobs where the excess images lie */
+int fpm_last_blobs(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags,
+                   int32_t level, int32_t connectivity, int32_t min_area,
+                   fpm_inspect_stats* stats /* may be NULL */, fpm_blob_summary* summary, fpm_blob* out,
+                   int32_t cap_per_hit, int32_t cap /* hits */, int32_t* n);
+/* the same at caller-supplied poses on the staged sources */
+int fpm_blobs_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                 int32_t a, int32_t kq, int32_t flags, int32_t level, int32_t connectivity, int32_t min_area,
+                 fpm_inspect_stats* stats, fpm_blob_summary* summary, fpm_blob* out, int32_t cap_per_hit);
+/* the labelling kernels alone on caller-supplied u8 images: fpm_blobs_host's signature behind a context (parity vehicle) */
+int fpm_op_blobs(fpm_ctx* ctx, const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
+                 int32_t connectivity, int32_t min_area, fpm_blob_summary* summary, fpm_blob* out,
+                 int32_t cap_per_hit, int32_t* labels /* may be NULL */);
+int fpm_blobs_set_round(fpm_ctx* ctx, int32_t images);   /* images per round of launches; 0 = the engine's choice */
+/* Timing of the labelling kernels, collected under fpm_profile_enable and cleared by fpm_profile_reset as
+ * fpm_model_profile's (no FPM_K_* index: FPM_K_COUNT is unchanged).  which: 0 = k_blob_tile, 1 = k_blob_merge, 2 =
+ * k_blob_flatten, 3 = k_blob_slots, 4 = k_blob_features; bytes = the excess pixels and plane bytes read and written. */
+int fpm_blobs_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
 
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------

@@ -176,7 +176,7 @@ class Peak(C.Structure):
 PEAKS_STATS_CALL, PEAKS_STATS_JOB = 8, 4   # FPM_PEAKS_STATS_CALL / _JOB
 PEAKS_RAN_BLOCKS, PEAKS_RAN_NMS, PEAKS_RAN_FAST, PEAKS_RAN_GREEDY = 1, 2, 4, 8   # stats[0] of fpm_op_peaks
 TOP_MAPS_STATS = 8   # FPM_TOP_MAPS_STATS
-TOP_FUSED_STATS = 8   # FPM_TOP_FUSED_STATS
+TOP_FUSED_STATS = 10  # FPM_TOP_FUSED_STATS
 TOP_FORM_EXACT16, TOP_FORM_EXACT14, TOP_FORM_SMALL, TOP_FORM_LARGE = 0, 1, 2, 3   # stats[5] of fpm_op_top_maps
 
 # every symbol include/fpm.h declares, with (restype, argtypes)

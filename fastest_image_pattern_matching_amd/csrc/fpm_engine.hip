@@ -938,6 +938,35 @@ size_t plan_top_fused_lds(const fpm_ctx* ctx, size_t* need = nullptr) {
     return lds > top_fused_lds_limit() ? 0 : lds;
 }
 
+// What a launch of k_top_fused may do beside the plain form (TopFusedOpts), decided per plan when the launch is recorded:
+//   level_copy  the taps read an LDS copy of the source level in every job whose map region holds it (copy_angles, where
+//               asked for: how many of the plan's angles).  The copy lies in the map's LDS, so neither the launch's
+//               dynamic LDS (plan_top_fused_lds: the fused / split choice) nor the workgroups per CU change.  Needs a
+//               border colour of one byte;
+//   bound       k_top_mma's f32 bound ahead of the exact score, under k_top_mma's conditions (plan_top_mma: area <= 258,
+//               layer score > 0.01, not ResultEqual1) and with its constants (top_mma_thresholds).
+TopFusedOpts plan_top_fused_opts(const fpm_ctx* ctx, int* copy_angles = nullptr) {
+    const Plan& P = ctx->plan;
+    const TmplLevel& tt = ctx->tmpl[P.L];
+    const SrcLevel& top = ctx->src[P.L];
+    TopFusedOpts o{};
+    int fits = 0;
+    for (int a = 0; a < P.nang; ++a) fits += top_fused_level_fits(top.w, top.h, P.map_w[a], P.map_h[a]) ? 1 : 0;
+    o.level_copy = fits > 0 && ctx->border >= 0 && ctx->border <= 255 ? 1 : 0;
+    if (copy_angles) *copy_angles = o.level_copy ? fits : 0;
+    const double thr = P.layer_score[P.L];
+    o.area = (uint32_t)(tt.w * tt.h);
+    if (o.area <= 258 && thr > 0.01 && !tt.equal1 && tt.px.size() == (size_t)o.area) {
+        TopMmaArgs A{};
+        A.area = (int32_t)o.area;
+        top_mma_thresholds(A, thr, tt);
+        o.thrK = A.thrK; o.E = A.E;
+        for (uint8_t v : tt.px) o.tsum += v;
+        o.bound = 1;
+    }
+    return o;
+}
+
 // The top layer's form as the search selects it: *fused_lds > 0 = k_top_fused with that much dynamic LDS (small
 // canvases with the plain peak path and enough (source, angle) jobs to fill the chip; FPM_TOP_FUSED=0 keeps the
 // three-kernel form, =1 forces the fused one whatever the job count), *use_mma = the matrix-core form (where the plan
@@ -1019,7 +1048,7 @@ int enqueue_search(fpm_ctx* ctx) {
         ProfScope ps(ctx, FPM_K_TOP_NCC, bytes * S);
         launch_top_fused(P.d_jobs.as<WarpJob>(P.off_warp), P.d_jobs.as<NccJob>(P.off_ncc), na, J, fused_lds,
                          pyr_zero ? nullptr : P.d_livecnt.as<int32_t>(), pyr_zero ? 0 : P.nzero, st,
-                         top_init ? &ca : nullptr, P.d_jobs.as<int32_t>(P.off_order), false);
+                         top_init ? &ca : nullptr, P.d_jobs.as<int32_t>(P.off_order), false, plan_top_fused_opts(ctx));
         cand_fused = top_init;
     }
     if (use_mma) {
@@ -4529,6 +4558,8 @@ int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_
     if (cap) *cap = P.cap;
     size_t need = 0;
     const size_t lds = plan_top_fused_lds(ctx, &need);
+    int copy_angles = 0;
+    const TopFusedOpts opts = plan_top_fused_opts(ctx, &copy_angles);
     if (stats) {
         size_t chosen = 0;
         bool use_mma = false;
@@ -4542,6 +4573,8 @@ int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_
         stats[5] = P.cap;
         stats[6] = chosen > 0 ? 1 : 0;
         stats[7] = (int32_t)top_fused_static_lds(true);
+        stats[8] = copy_angles;
+        stats[9] = opts.bound;
     }
     if (lds == 0 && J > 0) {
         ctx->err = "top fused: the plan cannot take the fused form (block mode, the template level or the LDS limit)";
@@ -4587,7 +4620,8 @@ int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_
         na.peaks = ctx->d_op_b.as<Peak>(o_peaks[v]);
         na.counts = ctx->d_op_b.as<int32_t>(o_counts[v]);
         launch_top_fused(P.d_jobs.as<WarpJob>(P.off_warp), P.d_jobs.as<NccJob>(P.off_ncc), na, J, lds,
-                         P.d_livecnt.as<int32_t>(), P.nzero, st, nullptr, P.d_jobs.as<int32_t>(P.off_order), v == 1);
+                         P.d_livecnt.as<int32_t>(), P.nzero, st, nullptr, P.d_jobs.as<int32_t>(P.off_order), v == 1,
+                         opts);
         HIP_TRY(hipGetLastError());
     }
     std::vector<float> hm(P.map_floats * S);

@@ -418,15 +418,34 @@ void launch_cand_init(const CandInitArgs& a, hipStream_t st);
 size_t top_fused_lds(int bw, int bh, int tw, int th);
 size_t top_fused_lds_limit();   // 64 KB minus k_top_fused's static LDS (hipFuncGetAttributes, per device)
 constexpr int kTopFusedMinJobs = 256;   // fewer jobs than CUs: the three split kernels finish sooner
+// What the host decides per launch of k_top_fused (the engine's plan_top_fused_opts).
+struct TopFusedOpts {
+    int32_t level_copy;      // 1: a job whose map region holds it samples from an LDS copy of its source level
+    int32_t bound;           // 1: f32 bound before the exact f64 score (product instantiation only; area <= 258,
+                             //    thr > 0.01, not equal1: k_top_mma's conditions)
+    float thrK, E;           // the bound's constants, as TopMmaArgs::thrK / E (top_mma_thresholds)
+    uint32_t tsum, area;     // sum of the template level's pixels, tw * th
+};
+// The LDS copy of a sw x sh source level holds horizontal pixel pairs: u16 entry [y + 1][x + 1] = pixel (x, y) | pixel
+// (x + 1, y) << 8 for x in [-1, sw - 1], y in [-1, sh], the border value wherever a pixel lies outside the level.  Its
+// row pitch in entries (a multiple of 4: four entries are staged per item) and its size in bytes
+constexpr int top_fused_level_pitch(int sw) { return (sw + 1 + 3) & ~3; }
+constexpr size_t top_fused_level_bytes(int sw, int sh) { return 2 * (size_t)top_fused_level_pitch(sw) * (size_t)(sh + 2); }
+// whether a job with an ow x oh map samples from the copy: it lies in the map's LDS, which nothing else uses until the
+// canvas is complete, so the copy adds nothing to the job's LDS (host and kernel decide by this one function)
+constexpr bool top_fused_level_fits(int sw, int sh, int ow, int oh) {
+    return ow > 0 && oh > 0 && top_fused_level_bytes(sw, sh) <= 4 * (size_t)ow * (size_t)oh;
+}
 // ci (cap <= kNmsInitCap): the candidate init fused as in k_nms; the live counter must be zero before the launch
 // (zero / nzero are then 0: block 0's clearing would race with the other blocks' atomics)
 // order (optional): the job each workgroup takes, costliest angles first (fewer workgroups than resident slots are
 // left for the last round)
 // dump: the map-writing instantiation (fpm_op_top_fused): every job's LDS map, unpainted, also goes to NccJob::out; the
 // search passes false.  top_fused_static_lds: the kernel's static LDS as compiled (0 if the query fails)
+// opts: the level copy and the bound (TopFusedOpts)
 void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& a, int njobs_n, size_t lds,
                       int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci, const int32_t* order,
-                      bool dump);
+                      bool dump, const TopFusedOpts& opts);
 size_t top_fused_static_lds(bool dump);
 int top_fused_grid(int njobs_n);   // the workgroups launch_top_fused starts for njobs_n jobs (FPM_GRID_TOP)
 // ---- the top layer on the matrix cores (k_top_mma): warp + TM_CCORR + CCOEFF_Denominator for every (source, angle)

@@ -88,6 +88,25 @@ __device__ __forceinline__ int warp_tap(const uint8_t* __restrict__ src, int sw,
     return (v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15;
 }
 
+// warp_tap on k_top_fused's LDS copy of the level (fpm_kernels.h: u16 entries of horizontal pixel pairs, lv[(y + 1) * lp +
+// x + 1] = pixel (x, y) | pixel (x + 1, y) << 8, lp = top_fused_level_pitch(sw), the border value for every pixel outside
+// the level).  A tap set with sx in [-1, sw - 1] and sy in [-1, sh - 1] reads its two entries with no test: a border
+// byte in an entry is exactly what BORDER_CONSTANT substitutes.  Every other tap set lies wholly outside (warp_tap
+// returns cval there) and reads entry 0 twice, two border bytes, whose blend is the border again (the weights sum to
+// 2^15).  The blend is warp_tap's integer, regrouped: v0 w0 + v1 w1 = 32 (32 - fy) (v0 (32 - fx) + v1 fx), each row's
+// bracket one v_dot4 of the entry with the bytes (32 - fx, fx, 0, 0).  The coordinates pass sat_s16 as in warp_tap, and
+// the unsigned range test keeps every index inside the copy.
+__device__ __forceinline__ int warp_tap_lds(const uint16_t* lv, int lp, int sw, int sh, int X, int Y) {
+    const int sx = sat_s16(X >> kInterBits), sy = sat_s16(Y >> kInterBits);
+    const int fx = X & (kInterTab - 1), fy = Y & (kInterTab - 1);
+    const bool in = (unsigned)(sx + 1) <= (unsigned)sw && (unsigned)(sy + 1) <= (unsigned)sh;   // sx + 1 in [0, sw]
+    const int i0 = in ? (sy + 1) * lp + sx + 1 : 0, i1 = in ? i0 + lp : 0;
+    const uint32_t wx = (uint32_t)(kInterTab - fx) | (uint32_t)fx << 8;
+    const uint32_t r0 = __builtin_amdgcn_udot4((uint32_t)lv[i0], wx, 0u, false);
+    const uint32_t r1 = __builtin_amdgcn_udot4((uint32_t)lv[i1], wx, 0u, false);
+    return (int)(((r0 * (uint32_t)(kInterTab - fy) + r1 * (uint32_t)fy) * 32u + (1u << 14)) >> 15);
+}
+
 // CCOEFF_Denominator's per-position body (TemplateMatcher.cpp:567-595).
 __device__ __forceinline__ float ccoeff(double num, double wsum, double wsq, double mean0, double tnorm,
                                         double inv_area) {
@@ -2115,6 +2134,26 @@ void launch_cand_init(const CandInitArgs& a, hipStream_t st) {
 // search's counters (as k_warp does on the split path).  Src7, 43 sources (1763 jobs): 75.5 us per launch against
 // 106.4 for k_warp + k_ncc_tile + k_nms; round-3 ablations (a profiling build, since removed from the product) put
 // 21 us in the taps, 19 in the correlation, 3 in the peak loop.
+// Level copy (TopFusedOpts::level_copy): a job whose map region holds the source level as u16 horizontal pixel pairs
+// with the border colour around it (top_fused_level_fits; Src7: 64 entries x 50 rows = 6.4 KB, which every angle's map holds)
+// first stages it there with aligned word loads and takes every tap from LDS (warp_tap_lds: two reads and two v_dot4
+// per tap, same integers, no border branch, no dependent global load); the map is written only after the canvas is
+// complete, so the job's LDS, and with it the workgroups per CU, stay what they were.  Jobs whose map is smaller than
+// the copy keep the taps in global memory (warp_tap).  (Measured, 64-source Src7 launch: a copy of plain bytes, four
+// reads per tap, was slower than the global taps, 5.90 against 5.58 ms per 50 launches -- presumably because the
+// correlation already keeps the LDS pipe busy; the pairs: 5.04.  profiles/top_fused_lds/README.txt)
+// Bound (TopFusedOpts::bound, the product instantiation only): with the exact integers d = sum T I, s1 = sum I, s2 =
+// sum I^2 of an output, nf = area d - s1 tsum and df = area s2 - s1^2, the f64 score is num / (sqrt(s2 - s1^2 / area)
+// norm) with num = d - s1 mean, so score >= thr > 0 needs nf > 0 and nf^2 >= thr^2 norm^2 area df up to the f64
+// roundings of mean, inv_area and the quotient (relative 1e-15), and the branch that returns +-1 needs |num| >= t, which
+// implies the same for thr <= 1 (for thr > 1 no score reaches thr at all).  The kernel tests nf + E > 0 and (nf + E)^2
+// >= thrK df in f32, thrK = (thr (1 - 1e-5))^2 norm^2 area: for area <= 258 d < 2^24, s1 and tsum < 2^17 and df < 2^32
+// (as a u32 product difference, exact), so d, s1, tsum convert exactly -- d is the u8 x u8 sum itself, no +-128
+// correction term as in k_top_mma -- and s1 tsum, the fma and the sum with E round by at most 256 + 256 + 512 = E at
+// magnitudes below 2^33, so the computed nf + E is never below nf; (float)df, the two f32 products and thrK's own
+// rounding are relative 2^-24 each, far inside thrK's 1e-5 margin.  So no output with (double)score >= thr fails the
+// test; one that fails gets -2.f, below every threshold the bound is enabled for (thr > 0.01) and below the painted
+// -1.f, and is never a peak.  df == 0 is a flat window: score 0 (ccoeff's t = 0 branch), also below thr.
 constexpr int kTopThreads = 256;   // k_top_fused workgroup (measured: 512 threads per job no faster)
 // one (source, angle) job of k_top_fused (returns when the job is done; the caller separates jobs by a barrier).
 // DUMP = false is the product kernel; DUMP = true (fpm_op_top_fused only) also copies the finished LDS map, before any
@@ -2122,8 +2161,8 @@ constexpr int kTopThreads = 256;   // k_top_fused workgroup (measured: 512 threa
 template <bool DUMP>
 __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict__ wjobs,
                                               const NccJob* __restrict__ njobs, const NmsArgs& a,
-                                              const CandInitArgs& ci, int ci_mode, uint32_t* tf_lds, float* sv,
-                                              int* si, Peak* spk, int* sbase_p) {
+                                              const CandInitArgs& ci, int ci_mode, const TopFusedOpts& o,
+                                              uint32_t* tf_lds, float* sv, int* si, Peak* spk, int* sbase_p) {
     int& sbase = *sbase_p;
     const int tid = threadIdx.x;
     const WarpJob& w = wjobs[job];
@@ -2149,20 +2188,74 @@ __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict
         tab[2 * dw + y] = rint_i((w.M[1] * y + w.M[2]) * kAbScale) + kRoundDelta;
         tab[2 * dw + dh + y] = rint_i((w.M[4] * y + w.M[5]) * kAbScale) + kRoundDelta;
     }
+    // the level copy (TopFusedOpts::level_copy and a map region that holds it; uniform per job): the source level as
+    // horizontal pixel pairs (warp_tap_lds), in the map's LDS, which is idle until the canvas is complete (the barrier
+    // after K2).  Four entries per item: columns x = 4 k - 1 .. 4 k + 2 of row y = r - 1, from source bytes 4 k - 1 ..
+    // 4 k + 3 -- one aligned word (bytewise where the level's address or pitch is not a multiple of 4, or the word would
+    // leave the row's pitch) and the byte before it; every byte outside the level is the border
+    const int lp = top_fused_level_pitch(w.sw);
+    const bool lvl = o.level_copy && top_fused_level_fits(w.sw, w.sh, ow, oh);
+    if (lvl) {
+        uint32_t* Lw = (uint32_t*)Mp;
+        const int lpi = lp >> 2;
+        const uint32_t b1 = (uint32_t)(w.border & 0xff), b4 = b1 * 0x01010101u;
+        const bool al = ((((uintptr_t)w.src) | (uintptr_t)(uint32_t)w.sp) & 3) == 0;
+        for (int i = tid; i < lpi * (w.sh + 2); i += kTopThreads) {
+            const int r = i / lpi, k = i - r * lpi;
+            const int y = r - 1, x = 4 * k;
+            uint32_t v = b4, prev = b1;
+            if ((unsigned)y < (unsigned)w.sh) {
+                const uint8_t* p = w.src + (size_t)y * w.sp + x;
+                if (k > 0 && x - 1 < w.sw) prev = p[-1];
+                const int nb = w.sw - x;   // source bytes from column x on
+                if (nb > 0) {
+                    if (al && x + 4 <= w.sp) {
+                        v = *(const uint32_t*)p;
+                    } else {
+                        v = 0;
+                        for (int b = 0; b < 4 && b < nb; ++b) v |= (uint32_t)p[b] << (8 * b);
+                    }
+                    if (nb < 4) {
+                        const uint32_t keep = (1u << (8 * nb)) - 1u;
+                        v = (v & keep) | (b4 & ~keep);
+                    }
+                }
+            }
+            Lw[2 * i] = prev | (v & 0xffu) << 8 | (v & 0xffffu) << 16;
+            Lw[2 * i + 1] = ((v >> 8) & 0xffffu) | (v >> 16) << 16;
+        }
+    }
     __syncthreads();
     // K2: the rotated canvas, four pixels (one word) per item
-    for (int i = tid; i < dh * cpw; i += kTopThreads) {
-        const int y = i / cpw, k = i - y * cpw;
-        const int X0 = tab[2 * dw + y], Y0 = tab[2 * dw + dh + y];
-        uint32_t word = 0;
-        for (int b = 0; b < 4; ++b) {   // (measured: branch-free taps with clamped loads are slower, 75 -> 80 us:
-            const int x = 4 * k + b;    // the canvas corners outside the image then load too)
-            if (x >= dw) break;
-            const int ad = tab[x], bd = tab[dw + x];
-            const int X = (X0 + ad) >> (kAbBits - kInterBits), Y = (Y0 + bd) >> (kAbBits - kInterBits);
-            word |= (uint32_t)warp_tap(w.src, w.sw, w.sh, w.sp, X, Y, w.border) << (8 * b);
+    if (lvl) {
+        const uint16_t* lv = (const uint16_t*)Mp;
+        for (int i = tid; i < dh * cpw; i += kTopThreads) {
+            const int y = i / cpw, k = i - y * cpw;
+            const int X0 = tab[2 * dw + y], Y0 = tab[2 * dw + dh + y];
+            uint32_t word = 0;
+            for (int b = 0; b < 4; ++b) {
+                const int x = 4 * k + b;
+                if (x >= dw) break;
+                const int ad = tab[x], bd = tab[dw + x];
+                const int X = (X0 + ad) >> (kAbBits - kInterBits), Y = (Y0 + bd) >> (kAbBits - kInterBits);
+                word |= (uint32_t)warp_tap_lds(lv, lp, w.sw, w.sh, X, Y) << (8 * b);
+            }
+            Cw[i] = word;
         }
-        Cw[i] = word;
+    } else {   // the taps from global memory: levels too large for the map's LDS
+        for (int i = tid; i < dh * cpw; i += kTopThreads) {
+            const int y = i / cpw, k = i - y * cpw;
+            const int X0 = tab[2 * dw + y], Y0 = tab[2 * dw + dh + y];
+            uint32_t word = 0;
+            for (int b = 0; b < 4; ++b) {   // (measured: branch-free taps with clamped loads are slower, 75 -> 80 us:
+                const int x = 4 * k + b;    // the canvas corners outside the image then load too)
+                if (x >= dw) break;
+                const int ad = tab[x], bd = tab[dw + x];
+                const int X = (X0 + ad) >> (kAbBits - kInterBits), Y = (Y0 + bd) >> (kAbBits - kInterBits);
+                word |= (uint32_t)warp_tap(w.src, w.sw, w.sh, w.sp, X, Y, w.border) << (8 * b);
+            }
+            Cw[i] = word;
+        }
     }
     for (int i = tid; i < th * ntw; i += kTopThreads) {
         const int r = i / ntw, k = i - r * ntw;
@@ -2202,12 +2295,39 @@ __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict
                 w0 = w1;
             }
         }
+        // the item's outputs that need the exact score: all four, or those that pass the bound (k_top_mma's test on
+        // this kernel's exact integers; see the header).  The four exact scores stay one straight block, as without
+        // the bound; an item none of whose outputs passes skips it
+        uint32_t pm = 0xfu;
+        if constexpr (!DUMP) {
+            if (o.bound) {   // (uniform)
+                pm = 0;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int x = 4 * q + u;
-            if (x >= ow) break;
-            const double num = (double)(float)(double)(uint64_t)d[u];   // TM_CCORR's f32 result (fold == 0)
-            Mp[y * ow + x] = j.equal1 ? 1.f : ccoeff(num, (double)s1[u], (double)s2[u], j.mean, j.norm, j.inv_area);
+                for (int u = 0; u < 4; ++u) {
+                    const uint32_t dfi = o.area * s2[u] - s1[u] * s1[u];
+                    const float nfp =
+                        __builtin_fmaf((float)o.area, (float)d[u], -((float)s1[u] * (float)o.tsum)) + o.E;
+                    if (dfi != 0u && nfp > 0.f && nfp * nfp >= o.thrK * (float)dfi) pm |= 1u << u;
+                }
+            }
+        }
+        if (pm) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int x = 4 * q + u;
+                if (x >= ow) break;
+                const double num = (double)(float)(double)(uint64_t)d[u];   // TM_CCORR's f32 result (fold == 0)
+                const float sc =
+                    j.equal1 ? 1.f : ccoeff(num, (double)s1[u], (double)s2[u], j.mean, j.norm, j.inv_area);
+                Mp[y * ow + x] = (pm >> u) & 1u ? sc : -2.f;
+            }
+        } else {   // -2.f: below every threshold the bound is enabled for, and below the painted -1.f
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int x = 4 * q + u;
+                if (x >= ow) break;
+                Mp[y * ow + x] = -2.f;
+            }
         }
     }
     __syncthreads();
@@ -2261,12 +2381,14 @@ __device__ __forceinline__ void top_fused_job(int job, const WarpJob* __restrict
 }
 
 // jobs k = blockIdx.x, + gridDim.x, ... in `order` (the grid may be smaller than the job count: FPM_GRID_TOP)
+// (launch bound 6 waves per SIMD = 6 workgroups per CU: 80 VGPRs, no scratch.  Without it the level copy and the bound
+// take 83 and the Src7 launch loses a resident workgroup: 90.3 against 86.2 us per 64-source launch)
 template <bool DUMP>
-__global__ __launch_bounds__(kTopThreads) void k_top_fused(const WarpJob* __restrict__ wjobs,
+__global__ __launch_bounds__(kTopThreads, 6) void k_top_fused(const WarpJob* __restrict__ wjobs,
                                                            const NccJob* __restrict__ njobs,
                                                            NmsArgs a, int32_t* zero, int nzero,
                                                            CandInitArgs ci, int ci_mode, const int32_t* order,
-                                                           int njobs_n) {
+                                                           int njobs_n, TopFusedOpts o) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tf_lds[];
     __shared__ float sv[kTopThreads / 64];
     __shared__ int si[kTopThreads / 64];
@@ -2276,7 +2398,7 @@ __global__ __launch_bounds__(kTopThreads) void k_top_fused(const WarpJob* __rest
         for (int i = threadIdx.x; i < nzero; i += kTopThreads) zero[i] = 0;
     for (int k = blockIdx.x; k < njobs_n; k += gridDim.x) {
         if (k != (int)blockIdx.x) __syncthreads();   // the previous job is done with the LDS
-        top_fused_job<DUMP>(order ? order[k] : k, wjobs, njobs, a, ci, ci_mode, tf_lds, sv, si, spk, &sbase);
+        top_fused_job<DUMP>(order ? order[k] : k, wjobs, njobs, a, ci, ci_mode, o, tf_lds, sv, si, spk, &sbase);
     }
 }
 
@@ -2321,7 +2443,7 @@ int top_fused_grid(int njobs_n) {
 
 void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& a, int njobs_n, size_t lds,
                       int32_t* zero, int nzero, hipStream_t st, const CandInitArgs* ci, const int32_t* order,
-                      bool dump) {
+                      bool dump, const TopFusedOpts& opts) {
     if (njobs_n <= 0) return;
     if (dump) {   // both instantiations declare the same arrays, so one LDS limit (top_fused_lds_limit) serves both
         static std::once_flag once;
@@ -2346,10 +2468,10 @@ void launch_top_fused(const WarpJob* wjobs, const NccJob* njobs, const NmsArgs& 
     const int grid = top_fused_grid(njobs_n);
     if (dump)
         hipLaunchKernelGGL(k_top_fused<true>, dim3(grid), dim3(kTopThreads), lds, st, wjobs, njobs, a, zero, nzero,
-                           fuse ? *ci : cz, mode, order, njobs_n);
+                           fuse ? *ci : cz, mode, order, njobs_n, opts);
     else
         hipLaunchKernelGGL(k_top_fused<false>, dim3(grid), dim3(kTopThreads), lds, st, wjobs, njobs, a, zero, nzero,
-                           fuse ? *ci : cz, mode, order, njobs_n);
+                           fuse ? *ci : cz, mode, order, njobs_n, opts);
 }
 
 // ============================================================================================== K6+K7+K8

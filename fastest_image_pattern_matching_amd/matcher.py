@@ -1575,7 +1575,8 @@ class TemplateMatcher:
 
         def stats():
             return dict(lds=int(st[0]), static_lds=int(st[1]), lds_limit=int(st[2]), grid=int(st[3]), jobs=int(st[4]),
-                        cap=int(st[5]), search_takes_it=int(st[6]), dump_static_lds=int(st[7]))
+                        cap=int(st[5]), search_takes_it=int(st[6]), dump_static_lds=int(st[7]), copy_angles=int(st[8]),
+                        bound=int(st[9]))
 
         def call(geom, gcap, maps, mcap, pk, cnt, dpk, dcnt, slots):
             rc = self._check(self._lib.fpm_op_top_fused(

@@ -834,12 +834,15 @@ int fpm_op_top_maps(fpm_ctx* ctx, int32_t form, double thr, int32_t* n_sources, 
  * entries: [0] the dynamic LDS of the launches in bytes (the largest job's need, also where it is refused), [1] the
  * product kernel's static LDS, [2] the dynamic LDS limit (64 KB - [1]), [3] the grid (FPM_GRID_TOP caps it; the jobs
  * loop), [4] jobs, [5] cap, [6] the search itself takes the fused form for this plan, [7] the map-writing kernel's
- * static LDS (equal to [1]; checked once per process).
+ * static LDS (equal to [1]; checked once per process), [8] the angles whose jobs sample from an LDS copy of the source
+ * level (it lies in the job's map region, so [0] does not grow; 0: no map holds the level and every tap reads global
+ * memory), [9] 1 where the product launch takes an f32 bound ahead of the exact score (top template area <= 258, layer
+ * score > 0.01, not ResultEqual1).  Neither changes a peak, a count or a map.
  * State.  As fpm_op_top_maps: FPM_E_INVALID_ARG while a search is in flight, without staged sources and for a missing
  * output; the template, the sources, the parameters, the last results and candidates, the model and the profile
  * counters stay as they were; a following fpm_match_staged returns what it returns without the call.  Additive entry:
  * FPM_ABI_VERSION is unchanged. */
-#define FPM_TOP_FUSED_STATS 8
+#define FPM_TOP_FUSED_STATS 10
 int fpm_op_top_fused(fpm_ctx* ctx, int32_t* n_sources, int32_t* n_angles, int64_t* map_floats, int32_t* cap,
                      int32_t* geom, int32_t geom_cap, float* maps, int64_t maps_cap, fpm_peak* peaks, int32_t* counts,
                      fpm_peak* dump_peaks, int32_t* dump_counts, int64_t peak_slots, int32_t* stats);

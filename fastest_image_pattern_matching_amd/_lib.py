@@ -68,6 +68,12 @@ BLOBS_MAX_CAP, BLOBS_MAX_SLOTS = 65536, 1 << 22
 # fpm_blobs_profile's `which`: the labelling kernels have no FPM_K_* index
 BLOB_TILE, BLOB_MERGE, BLOB_FLATTEN, BLOB_SLOTS, BLOB_FEATURES = 0, 1, 2, 3, 4
 BLOB_KERNEL_SYMBOLS = ["k_blob_tile", "k_blob_merge", "k_blob_flatten", "k_blob_slots", "k_blob_features"]
+# fpm_last_calipers / fpm_calipers_at: the summary's flags and the caps; the kernel has no FPM_K_* index
+# (fpm_caliper_profile)
+CALIPER_TRUNCATED, CALIPER_OUTSIDE = 1, 2
+CALIPER_MAX_LENGTH, CALIPER_MAX_WIDTH, CALIPER_MAX_HALF = 1024, 256, 16
+CALIPER_MAX_CALS, CALIPER_MAX_CAP, CALIPER_MAX_SLOTS = 64, 64, 1 << 22
+CALIPER_KERNEL_SYMBOL = "k_caliper"
 
 
 class Params(C.Structure):
@@ -158,6 +164,33 @@ class BlobSummary(C.Structure):
 
     _fields_ = [("fg_pixels", C.c_int64)] + \
                [(n, C.c_int32) for n in ("n_components", "n_blobs", "n_returned", "largest_area", "flags", "reserved")]
+
+
+class Caliper(C.Structure):
+    """fpm_caliper -- one caliper, drawn on the taught image (fpm_last_calipers / fpm_calipers_at)."""
+
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("phi", C.c_double)] + \
+               [(n, C.c_int32) for n in ("length", "width", "half", "contrast", "polarity", "reserved")]
+
+
+class EdgeRaw(C.Structure):
+    """fpm_edge_raw -- the four exact integers of one edge (fpm_caliper_edges_host)."""
+
+    _fields_ = [(n, C.c_int32) for n in ("index", "d_prev", "d", "d_next")]
+
+
+class Edge(C.Structure):
+    """fpm_edge -- one edge: the raw integers and what fpm_caliper_derive makes of them."""
+
+    _fields_ = [(n, C.c_int32) for n in ("index", "d_prev", "d", "d_next")] + \
+               [(n, C.c_double) for n in ("t", "contrast", "tx", "ty", "sx", "sy")]
+
+
+class CaliperSummary(C.Structure):
+    """fpm_caliper_summary -- one (hit, caliper): counts, flags and the sampling pose."""
+
+    _fields_ = [(n, C.c_int32) for n in ("n_edges", "n_returned", "strongest", "flags")] + \
+               [("lt_x", C.c_float), ("lt_y", C.c_float), ("angle", C.c_double)]
 
 
 class RoiRecord(C.Structure):
@@ -300,6 +333,18 @@ SIGNATURES = {
                                C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_blobs_set_round": (C.c_int, [_P, C.c_int32]),
     "fpm_blobs_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_caliper_pose": (C.c_int, [C.c_float, C.c_float, C.c_double, C.POINTER(Caliper), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "fpm_caliper_edges_host": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(Caliper), C.c_int32, C.POINTER(EdgeRaw),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fpm_caliper_derive": (C.c_int, [C.POINTER(Caliper), C.c_float, C.c_float, C.c_double, C.POINTER(EdgeRaw), C.c_int32,
+                                     C.POINTER(Edge)]),
+    "fpm_calipers_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32,
+                                  C.POINTER(Caliper), C.c_int32, C.c_int32, C.POINTER(CaliperSummary), C.POINTER(Edge),
+                                  C.POINTER(C.c_int32), C.c_int32]),
+    "fpm_last_calipers": (C.c_int, [_P, C.c_int32, C.POINTER(Caliper), C.c_int32, C.c_int32, C.POINTER(CaliperSummary),
+                                    C.POINTER(Edge), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_caliper_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -153,10 +153,10 @@ struct KProf {
     int64_t launches = 0, bytes = 0;
 };
 // Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
-// alignment's one (fpm_align_profile) and the blob labelling's five (fpm_blobs_profile), which have no FPM_K_* index:
-// FPM_K_COUNT stays what it is.
+// alignment's one (fpm_align_profile), the blob labelling's five (fpm_blobs_profile) and the calipers' one
+// (fpm_caliper_profile), which have no FPM_K_* index: FPM_K_COUNT stays what it is.
 enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfBlobTile, kProfBlobMerge,
-       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfSlots };
+       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfSlots };
 
 }  // namespace
 
@@ -247,6 +247,9 @@ struct fpm_ctx {
     int blobs_round = 0;      // fpm_blobs_set_round: images per round, 0 = the engine's choice
     DevBuf d_blobplanes, d_blobrec, d_blobimg;
     PinBuf h_blobrec, h_bloblab;
+    // edge calipers (fpm_last_calipers / fpm_calipers_at): the raw records, counts and profiles of a call and their host copy
+    DevBuf d_calout;
+    PinBuf h_calout;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -2918,6 +2921,153 @@ int align_iterate(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Patch
     return FPM_OK;
 }
 
+// ---- edge calipers (fpm_last_calipers, fpm_calipers_at) ----
+static_assert(sizeof(fpm_caliper) == 48 && sizeof(fpm_edge) == 64 && sizeof(fpm_caliper_summary) == 32,
+              "the caliper structs have no padding");
+static_assert(sizeof(fpm_edge_raw) == sizeof(int4), "the kernel's record is fpm_edge_raw, field for field");
+static_assert(kCaliperMaxLength == FPM_CALIPER_MAX_LENGTH && kCaliperMaxWidth == FPM_CALIPER_MAX_WIDTH &&
+              kCaliperMaxHalf == FPM_CALIPER_MAX_HALF && kCaliperMaxCap == FPM_CALIPER_MAX_CAP, "one set of caps");
+
+// Staged sources, no search in flight; unlike patch_state no template: a caliper reads level 0 alone.
+int caliper_state(fpm_ctx* ctx) {
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (!ctx->src_valid || ctx->S <= 0 || ctx->src.empty() || !ctx->d_src.p) {
+        ctx->err = "no staged sources to measure on";
+        return FPM_E_INVALID_ARG;
+    }
+    return FPM_OK;
+}
+
+// the rules of a call's calipers and capacity that do not depend on the number of hits
+int caliper_args(fpm_ctx* ctx, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per) {
+    if (!cals || n_cals < 1 || n_cals > FPM_CALIPER_MAX_CALS) { ctx->err = "1 .. 64 calipers expected"; return FPM_E_INVALID_ARG; }
+    if (cap_per < 1 || cap_per > FPM_CALIPER_MAX_CAP) { ctx->err = "cap_per_caliper must be 1 .. 64"; return FPM_E_INVALID_ARG; }
+    for (int k = 0; k < n_cals; ++k)
+        if (const char* bad = caliper_bad(cals[k])) { ctx->err = bad; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+// and those that do: the outputs and the slots
+int caliper_outputs(fpm_ctx* ctx, size_t hits, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per,
+                    const fpm_caliper_summary* summary, const fpm_edge* edges, const int32_t* profiles, int32_t stride) {
+    if (!summary || !edges) { ctx->err = "null summary or edge buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)hits * n_cals * cap_per > FPM_CALIPER_MAX_SLOTS) {
+        ctx->err = "hits x calipers x cap_per_caliper above 2^22";
+        return FPM_E_INVALID_ARG;
+    }
+    int max_len = 0;
+    for (int k = 0; k < n_cals; ++k) max_len = std::max(max_len, cals[k].length);
+    if (profiles && stride < max_len) { ctx->err = "profile_stride below the largest length"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+// The calipers of `poses` (n >= 1), every argument checked: the job table, one launch of k_caliper, the raw records,
+// counts and profiles to pinned memory, then the derivation into the caller's buffers.  Caller memory is written only
+// after the device pass has succeeded.
+int calipers_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_caliper* cals, int n_cals, int cap_per,
+                     fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t stride) {
+    const int njobs = (int)poses.size() * n_cals;
+    const SrcLevel& l0 = ctx->src[0];
+    int max_len = 0;
+    for (int k = 0; k < n_cals; ++k) max_len = std::max(max_len, cals[k].length);
+    const size_t tab = round_up(sizeof(CaliperJob) * (size_t)njobs, (size_t)256);
+    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
+    HIP_TRY(ctx->h_patchtab.ensure(tab));
+    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    // the device output: records, counts, then the profiles at the largest length (the caller's stride is the host's)
+    const size_t rec_b = sizeof(int4) * (size_t)njobs * cap_per, cnt_b = round_up(sizeof(int32_t) * (size_t)njobs, (size_t)16);
+    const size_t prof_b = profiles ? sizeof(int32_t) * (size_t)njobs * max_len : 0;
+    HIP_TRY(ctx->d_calout.ensure(rec_b + cnt_b + prof_b));
+    HIP_TRY(ctx->h_calout.ensure(rec_b + cnt_b + prof_b));
+    std::vector<fpm_caliper_summary> sm((size_t)njobs);
+    int64_t bytes = (int64_t)(rec_b + sizeof(int32_t) * (size_t)njobs + prof_b);
+    CaliperJob* jobs = ctx->h_patchtab.as<CaliperJob>();
+    for (int i = 0, j = 0; i < (int)poses.size(); ++i)
+        for (int k = 0; k < n_cals; ++k, ++j) {
+            const fpm_caliper& c = cals[k];
+            PatchPose q{poses[i].src, poses[i].pose};
+            if (!std::isfinite(q.pose.x) || !std::isfinite(q.pose.y) || !std::isfinite(q.pose.angle)) {
+                ctx->err = "pose " + std::to_string(i) + ": not finite";
+                return FPM_E_INVALID_ARG;
+            }
+            caliper_pose(poses[i].pose.x, poses[i].pose.y, poses[i].pose.angle, c, &q.pose.x, &q.pose.y, &q.pose.angle);
+            const fpm_patch_rect r{0, 0, c.length, c.width};
+            CaliperJob& job = jobs[j];
+            const int rc = patch_pose_matrix(ctx, r, q, i, nullptr, job.p.M);
+            if (rc != FPM_OK) return rc;
+            job.p.out_off = (int64_t)j * cap_per;
+            job.p.src = q.src;
+            job.p.pad = 0;
+            job.L = c.length; job.W = c.width; job.s = c.half;
+            job.thr = c.contrast * c.half * c.width;
+            job.polarity = c.polarity;
+            job.pad = 0;
+            job.prof_off = (int64_t)j * max_len;
+            bytes += (int64_t)c.length * c.width;
+            // border zeros in the profile: a corner sample outside the source, through the matrix the sampler takes
+            bool outside = false;
+            for (int e = 0; e < 4; ++e) {
+                const double x = (e & 1) ? c.length - 1 : 0, y = (e & 2) ? c.width - 1 : 0;
+                const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
+                outside = outside || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
+            }
+            sm[j] = fpm_caliper_summary{0, 0, -1, outside ? FPM_CALIPER_OUTSIDE : 0, q.pose.x, q.pose.y, q.pose.angle};
+        }
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    CaliperArgs a{};
+    a.jobs = ctx->d_patchtab.as<CaliperJob>();
+    a.njobs = njobs;
+    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    a.img_stride = l0.img_bytes;
+    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    a.cap = cap_per;
+    a.prof_stride = max_len;
+    a.edges = ctx->d_calout.as<int4>();
+    a.counts = ctx->d_calout.as<int32_t>(rec_b);
+    a.profiles = profiles ? ctx->d_calout.as<int32_t>(rec_b + cnt_b) : nullptr;
+    {
+        ProfScope ps(ctx, kProfCaliper, bytes);   // L W source pixels per job + the records, counts and profiles written
+        if (!launch_caliper(a, ctx->stream)) { ctx->err = "bad caliper launch"; return FPM_E_INTERNAL; }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_calout.p, ctx->d_calout.p, rec_b + cnt_b + prof_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const fpm_edge_raw* raw = ctx->h_calout.as<fpm_edge_raw>();
+    const int32_t* counts = ctx->h_calout.as<int32_t>(rec_b);
+    const int32_t* prof = ctx->h_calout.as<int32_t>(rec_b + cnt_b);
+    for (int j = 0; j < njobs; ++j) {   // what the device wrote is checked before anything of it reaches the caller
+        const fpm_caliper& c = cals[j % n_cals];
+        const int32_t n = counts[j], nret = std::min(n, (int32_t)cap_per);
+        fpm_edge e;
+        bool ok = n >= 0 && n <= c.length;
+        for (int32_t i = 0; ok && i < nret; ++i)
+            ok = caliper_derive(c, sm[j].lt_x, sm[j].lt_y, sm[j].angle, raw[(size_t)j * cap_per + i], &e);
+        if (!ok) { ctx->err = "k_caliper returned a record that is no edge"; return FPM_E_INTERNAL; }
+    }
+    for (int j = 0; j < njobs; ++j) {
+        const fpm_caliper& c = cals[j % n_cals];
+        const fpm_edge_raw* rj = raw + (size_t)j * cap_per;
+        fpm_edge* ej = edges + (size_t)j * cap_per;
+        fpm_caliper_summary& s = sm[j];
+        s.n_edges = counts[j];
+        s.n_returned = std::min(s.n_edges, (int32_t)cap_per);
+        if (s.n_edges > cap_per) s.flags |= FPM_CALIPER_TRUNCATED;
+        s.strongest = caliper_strongest(rj, s.n_returned);
+        for (int32_t i = 0; i < s.n_returned; ++i) (void)caliper_derive(c, s.lt_x, s.lt_y, s.angle, rj[i], ej + i);
+        if (s.n_returned < cap_per) std::memset(ej + s.n_returned, 0, sizeof(fpm_edge) * (size_t)(cap_per - s.n_returned));
+        summary[j] = s;
+        if (profiles) {
+            int32_t* pj = profiles + (size_t)j * stride;
+            std::memcpy(pj, prof + (size_t)j * max_len, sizeof(int32_t) * (size_t)max_len);
+            if (stride > max_len) std::memset(pj + max_len, 0, sizeof(int32_t) * (size_t)(stride - max_len));
+        }
+    }
+    return FPM_OK;
+}
+
 // fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
 // the device learn's second half
 int learn_from_model(fpm_ctx* ctx) {
@@ -3008,6 +3158,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_alnacc.release(); ctx->h_alnacc.release();
     ctx->d_blobplanes.release(); ctx->d_blobrec.release(); ctx->d_blobimg.release();
     ctx->h_blobrec.release(); ctx->h_bloblab.release();
+    ctx->d_calout.release(); ctx->h_calout.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -3822,6 +3973,51 @@ int fpm_align_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int
 int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
     if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
     const KProf& p = ctx->kp[kProfAlign];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
+}
+
+// --- edge calipers (fpm_caliper_pose, fpm_caliper_edges_host and fpm_caliper_derive: fpm_host.cpp) --
+int fpm_calipers_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                    const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper, fpm_caliper_summary* summary,
+                    fpm_edge* edges, int32_t* profiles, int32_t profile_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = caliper_args(ctx, cals, n_cals, cap_per_caliper);
+    if (rc == FPM_OK) rc = caliper_state(ctx);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    rc = caliper_outputs(ctx, (size_t)n_poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
+    if (rc != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return calipers_to_host(ctx, poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
+}
+
+int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper,
+                      fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t profile_stride,
+                      int32_t cap, int32_t* n) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = caliper_args(ctx, cals, n_cals, cap_per_caliper);
+    if (rc == FPM_OK) rc = patch_state(ctx, true);
+    std::vector<PatchPose> poses;
+    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
+    if (rc != FPM_OK) return rc;
+    *n = (int32_t)poses.size();
+    if ((int)poses.size() > cap) { ctx->err = "caliper buffers too small"; return FPM_E_CAPACITY; }
+    if (poses.empty()) return FPM_OK;
+    rc = caliper_outputs(ctx, poses.size(), cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return calipers_to_host(ctx, poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
+}
+
+int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfCaliper];
     *ms = p.ms;
     *launches = p.launches;
     *bytes = p.bytes;

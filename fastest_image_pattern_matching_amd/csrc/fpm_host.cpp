@@ -625,7 +625,123 @@ void blobs_gather(const BlobCounters* counters, fpm_blob* recs, int32_t images, 
     }
 }
 
+// ---- edge calipers (include/fpm.h, "edge calipers").  The file is built with -ffp-contract=off: every product and sum
+// below is rounded on its own, in the header's order.
+const char* caliper_bad(const fpm_caliper& k) {
+    if (!std::isfinite(k.cx) || !std::isfinite(k.cy) || !std::isfinite(k.phi)) return "caliper: cx, cy and phi must be finite";
+    if (k.length < 2 || k.length > FPM_CALIPER_MAX_LENGTH) return "caliper: length must be 2 .. 1024";
+    if (k.width < 1 || k.width > FPM_CALIPER_MAX_WIDTH) return "caliper: width must be 1 .. 256";
+    if (k.half < 1 || k.half > FPM_CALIPER_MAX_HALF || 2 * k.half > k.length) return "caliper: half must be 1 .. 16 with 2 half <= length";
+    if (k.contrast < 1 || k.contrast > 255) return "caliper: contrast must be 1 .. 255";
+    if (k.polarity < -1 || k.polarity > 1) return "caliper: polarity must be +1, -1 or 0";
+    if (k.reserved != 0) return "caliper: reserved must be 0";
+    return nullptr;
+}
+
+namespace {
+// the template point of sample (0, 0), the scan direction's cos and sin, and hw
+struct CaliperFrame {
+    double ox, oy, cp, sp, hw;
+};
+CaliperFrame caliper_frame(const fpm_caliper& k) {
+    const double hl = (k.length - 1) / 2.0, hw = (k.width - 1) / 2.0;
+    const double rp = k.phi * kD2R, cp = std::cos(rp), sp = std::sin(rp);
+    return {k.cx - (hl * cp - hw * sp), k.cy - (hl * sp + hw * cp), cp, sp, hw};
+}
+}  // namespace
+
+void caliper_pose(float lt_x, float lt_y, double angle, const fpm_caliper& k, float* ltk_x, float* ltk_y, double* angle_k) {
+    const CaliperFrame f = caliper_frame(k);
+    const double ra = angle * kD2R, c = std::cos(ra), s = std::sin(ra);
+    *ltk_x = (float)((double)lt_x + (f.ox * c - f.oy * s));
+    *ltk_y = (float)((double)lt_y + (f.ox * s + f.oy * c));
+    *angle_k = angle + k.phi;
+}
+
+int32_t caliper_edges(const int32_t* profile, const fpm_caliper& k, int32_t cap, fpm_edge_raw* out) {
+    const int L = k.length, s = k.half, thr = k.contrast * k.half * k.width;
+    std::vector<int32_t> D((size_t)L + 1, 0);   // D[0 .. L], 0 outside s .. L - s
+    for (int i = s; i <= L - s; ++i) {
+        int32_t d = 0;
+        for (int j = 0; j < s; ++j) d += profile[i + j] - profile[i - 1 - j];
+        D[i] = d;
+    }
+    int32_t n = 0;
+    for (int i = s; i <= L - s; ++i) {
+        const int32_t d = D[i], dp = D[i - 1], dn = D[i + 1];
+        const bool up = d >= thr && d > dp && d >= dn, down = -d >= thr && d < dp && d <= dn;
+        if (!((k.polarity >= 0 && up) || (k.polarity <= 0 && down))) continue;
+        if (n < cap) out[n] = fpm_edge_raw{i, dp, d, dn};
+        ++n;
+    }
+    for (int32_t i = std::min(n, cap); i < cap; ++i) out[i] = fpm_edge_raw{0, 0, 0, 0};
+    return n;
+}
+
+bool caliper_derive(const fpm_caliper& k, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw& r, fpm_edge* e) {
+    if (r.d == 0 || r.index < k.half || r.index > k.length - k.half) return false;
+    const int64_t g = r.d > 0 ? 1 : -1;
+    const int64_t am = g * r.d_prev, a0 = g * r.d, ap = g * r.d_next;
+    if (!(am < a0 && ap <= a0)) return false;   // the local-maximum rule: den < 0 and delta in (-0.5, 0.5] follow
+    const int64_t den = (am - a0) + (ap - a0);
+    const CaliperFrame f = caliper_frame(k);
+    const double delta = 0.5 * (double)(am - ap) / (double)den;
+    const double t = ((double)r.index - 0.5) + delta;
+    const double rk = angle_k * kD2R, ck = std::cos(rk), sk = std::sin(rk);
+    e->index = r.index; e->d_prev = r.d_prev; e->d = r.d; e->d_next = r.d_next;
+    e->t = t;
+    e->contrast = (double)a0 / (double)(k.half * k.width);
+    e->tx = f.ox + (t * f.cp - f.hw * f.sp);
+    e->ty = f.oy + (t * f.sp + f.hw * f.cp);
+    e->sx = (double)ltk_x + (t * ck - f.hw * sk);
+    e->sy = (double)ltk_y + (t * sk + f.hw * ck);
+    return true;
+}
+
+int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n) {
+    int32_t best = -1;
+    int64_t top = -1;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t a = r[i].d < 0 ? -(int64_t)r[i].d : (int64_t)r[i].d;
+        if (a > top) { top = a; best = i; }
+    }
+    return best;
+}
+
 }  // namespace fpm
+
+int fpm_caliper_pose(float lt_x, float lt_y, double angle, const fpm_caliper* cal, float* ltk_x, float* ltk_y,
+                     double* angle_k) {
+    if (!cal || !ltk_x || !ltk_y || !angle_k || fpm::caliper_bad(*cal) || !std::isfinite(lt_x) || !std::isfinite(lt_y) ||
+        !std::isfinite(angle))
+        return FPM_E_INVALID_ARG;
+    fpm::caliper_pose(lt_x, lt_y, angle, *cal, ltk_x, ltk_y, angle_k);
+    return FPM_OK;
+}
+
+int fpm_caliper_edges_host(const int32_t* profile, const fpm_caliper* cal, int32_t cap_per_caliper, fpm_edge_raw* out,
+                           int32_t* n_edges, int32_t* flags) {
+    if (!profile || !cal || !out || !n_edges || !flags || fpm::caliper_bad(*cal) || cap_per_caliper < 1 ||
+        cap_per_caliper > FPM_CALIPER_MAX_CAP)
+        return FPM_E_INVALID_ARG;
+    for (int32_t u = 0; u < cal->length; ++u)
+        if (profile[u] < 0 || profile[u] > 255 * cal->width) return FPM_E_INVALID_ARG;   // of no width pixels
+    *n_edges = fpm::caliper_edges(profile, *cal, cap_per_caliper, out);
+    *flags = *n_edges > cap_per_caliper ? FPM_CALIPER_TRUNCATED : 0;
+    return FPM_OK;
+}
+
+int fpm_caliper_derive(const fpm_caliper* cal, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw* raw,
+                       int32_t n, fpm_edge* out) {
+    if (!cal || n < 0 || (n > 0 && (!raw || !out)) || fpm::caliper_bad(*cal) || !std::isfinite(ltk_x) ||
+        !std::isfinite(ltk_y) || !std::isfinite(angle_k))
+        return FPM_E_INVALID_ARG;
+    fpm_edge e;
+    for (int32_t i = 0; i < n; ++i)   // every record is checked before the first is written
+        if (!fpm::caliper_derive(*cal, ltk_x, ltk_y, angle_k, raw[i], &e)) return FPM_E_INVALID_ARG;
+    for (int32_t i = 0; i < n; ++i) (void)fpm::caliper_derive(*cal, ltk_x, ltk_y, angle_k, raw[i], out + i);
+    return FPM_OK;
+}
 
 // Two-pass union-find over one image at a time: pass 1 links every foreground pixel to its left and upper neighbours
 // (the smaller index becomes the parent, so a root is its component's seed), pass 2 resolves every pixel to its root,

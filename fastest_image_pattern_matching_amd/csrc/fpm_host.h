@@ -65,5 +65,17 @@ int32_t blobs_cap_dev(int32_t w, int32_t h, int32_t min_area, int32_t cap_per_hi
 // out + i * cap_per_hit and summary + i.  Pure host code: every write into caller memory of a device blob entry is here.
 void blobs_gather(const BlobCounters* counters, fpm_blob* recs, int32_t images, int32_t cap_dev, int32_t min_area,
                   int32_t cap_per_hit, fpm_blob* out, fpm_blob_summary* summary);
+// ---- edge calipers (include/fpm.h, "edge calipers"): the host half every caliper entry shares ----
+// the range rules of one caliper; nullptr = fine, else what is wrong
+const char* caliper_bad(const fpm_caliper& k);
+// the sampling pose of caliper k on a hit at (lt, angle)
+void caliper_pose(float lt_x, float lt_y, double angle, const fpm_caliper& k, float* ltk_x, float* ltk_y, double* angle_k);
+// the step and edge rules on a profile of k.length entries: the first min(count, cap) raw records to out, zero-filled
+// records behind them up to cap; returns the true count
+int32_t caliper_edges(const int32_t* profile, const fpm_caliper& k, int32_t cap, fpm_edge_raw* out);
+// one raw record of caliper k sampled at (ltk, angle_k) into *e; false (nothing written) for a record that is no edge
+bool caliper_derive(const fpm_caliper& k, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw& r, fpm_edge* e);
+// the returned record with the largest |d|, the earliest on ties; -1 for n = 0
+int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n);
 
 }  // namespace fpm

@@ -318,6 +318,33 @@ struct AlignArgs {
 // k_patch_align, k_patch_warp's grid; the table form when luts is set.  Returns false, launching nothing, for a grid past
 // 2^31 - 1 or a rectangle beyond the caps.
 bool launch_patch_align(AlignArgs c, hipStream_t st);
+// ---- edge calipers (fpm_last_calipers / fpm_calipers_at): one L x W patch per (hit, caliper), each
+// of its own size, summed across its width into a profile of L integers that never leaves LDS, then the step filter,
+// the local-maximum test and an ordered compaction of the edges.  One descriptor per job, built on the host.
+constexpr int kCaliperMaxLength = 1024, kCaliperMaxWidth = 256, kCaliperMaxHalf = 16, kCaliperMaxCap = 64;
+struct CaliperJob {
+    PatchJob p;              // the inverted matrix and the source, as for k_patch_warp; out_off = the job's first record
+                             // (in records) from CaliperArgs::edges
+    int32_t L, W, s;         // length, width, half
+    int32_t thr;             // c s W: the least |D| of an edge
+    int32_t polarity;        // +1, -1, 0 = both
+    int32_t pad;
+    int64_t prof_off;        // the job's first profile entry (in entries) from CaliperArgs::profiles
+};
+struct CaliperArgs {
+    const CaliperJob* jobs;
+    int32_t njobs;
+    const uint8_t* level0;   // as PatchArgs
+    size_t img_stride;
+    int32_t sw, sh, sp;
+    int32_t cap;             // records per job, 1 .. kCaliperMaxCap
+    int32_t prof_stride;     // entries per job of profiles: those from L on are written as 0
+    int4* edges;             // [njobs][cap]: index, d_prev, d, d_next; those behind the count written as 0
+    int32_t* counts;         // [njobs]: the true count
+    int32_t* profiles;       // [njobs][prof_stride] or null
+};
+// k_caliper: one workgroup per job.  Returns false, launching nothing, for a capacity outside its range.
+bool launch_caliper(const CaliperArgs& a, hipStream_t st);
 // ---- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): connected
 // components of n pitched u8 images of one size, by a union-find per 64 x 16 tile in LDS and a merge of the tile pieces
 // in device memory.  A label is the row-major index v * w + u, within its image, of a pixel of the same component that is

@@ -3239,6 +3239,117 @@ bool launch_patch_align(AlignArgs c, hipStream_t st) {
     return true;
 }
 
+// ============================================================================================== edge calipers
+// k_caliper (fpm_last_calipers / fpm_calipers_at): one workgroup owns one (hit, caliper) job, a
+// patch of the job's own L x W samples that is never written.  It walks the patch in k_patch_warp's 64 x 16 tiles with
+// the patch family's staging and sampler (patch_tile_stage_at / patch_sample4, the job's size standing in for
+// PatchArgs::pw / ph), so the pixels are k_patch_warp's by construction.  Column sums: a lane holds 4 adjacent columns
+// of one tile row; down a column of tiles (W <= 256: at most 16 tiles) it adds them into two words of two 16-bit
+// halves each (16 * 255 per half), then the four rows a wave holds are folded across lanes l, l ^ 16, l ^ 32 (4 * 16 *
+// 255 = 16320 per half, still 16 bits) -- one fold per 64 columns, not one per tile -- and the four waves meet in LDS as
+// 32-bit words: P[u] <= 255 * 256.  The profile stays in LDS (at most 1024 words); the step filter D, the local-maximum
+// test and an ordered compaction (lane votes per wave and chunk of 256 indices, prefix counts in (chunk, wave) order)
+// run over it there, so the records come in ascending index with no atomic: nothing is shared between workgroups.
+// Lanes past the patch's right or bottom edge take part in every barrier and fold with nu = 0.  The loop bounds come
+// from the job, the same words for every lane: every barrier is workgroup-uniform.
+__global__ __launch_bounds__(256) void k_caliper(const CaliperArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ __attribute__((aligned(16))) uint32_t part[4][kPatchTw];
+    __shared__ int32_t P[kCaliperMaxLength];
+    __shared__ int32_t D[kCaliperMaxLength + 1];   // D[0 .. L]; 0 outside s .. L - s
+    __shared__ int32_t wcnt[4][4];                 // edges per (chunk of 256 indices, wave)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const CaliperJob& J = c.jobs[blockIdx.x];
+    const int L = __builtin_amdgcn_readfirstlane(J.L), W = __builtin_amdgcn_readfirstlane(J.W);
+    const int s = __builtin_amdgcn_readfirstlane(J.s), thr = __builtin_amdgcn_readfirstlane(J.thr);
+    const int pol = __builtin_amdgcn_readfirstlane(J.polarity);
+    PatchArgs a{};
+    a.jobs = &J.p;
+    a.njobs = 1;
+    a.level0 = c.level0;
+    a.img_stride = c.img_stride;
+    a.sw = c.sw; a.sh = c.sh; a.sp = c.sp;
+    a.pw = L; a.ph = W;
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int ntx = (L + kPatchTw - 1) / kPatchTw, nty = (W + kPatchTh - 1) / kPatchTh;
+#pragma unroll 1
+    for (int tx = 0; tx < ntx; ++tx) {
+        const int left = L - (tx * kPatchTw + gx);
+        uint32_t acc01 = 0, acc23 = 0;   // columns gx, gx + 1 and gx + 2, gx + 3 as 16-bit halves
+#pragma unroll 1
+        for (int ty = 0; ty < nty; ++ty) {
+            const int nu = ty * kPatchTh + r >= W || left <= 0 ? 0 : (left < 4 ? left : 4);
+            const PatchTile T = patch_tile_stage_at(a, tab, FT, tid, 0, tx, ty);
+            const uint32_t w = patch_sample4(a, T, tab, FT, r, gx, nu);
+            acc01 += (w & 0xffu) | ((w & 0xff00u) << 8);
+            acc23 += ((w >> 16) & 0xffu) | ((w >> 8) & 0xff0000u);
+            __syncthreads();   // the next tile's tables and footprint overwrite what a slower wave still samples
+        }
+        acc01 += (uint32_t)__shfl_xor((int)acc01, 16);
+        acc23 += (uint32_t)__shfl_xor((int)acc23, 16);
+        acc01 += (uint32_t)__shfl_xor((int)acc01, 32);
+        acc23 += (uint32_t)__shfl_xor((int)acc23, 32);
+        if (lane < 16) *(uint4*)&part[wave][gx] = make_uint4(acc01 & 0xffffu, acc01 >> 16, acc23 & 0xffffu, acc23 >> 16);
+        __syncthreads();
+        // the next write of part comes after the barriers of the next column of tiles
+        if (tid < kPatchTw && tx * kPatchTw + tid < L)
+            P[tx * kPatchTw + tid] = (int32_t)(part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+    }
+    __syncthreads();
+    if (c.profiles) {
+        int32_t* prof = c.profiles + J.prof_off;
+        for (int u = tid; u < c.prof_stride; u += 256) prof[u] = u < L ? P[u] : 0;
+    }
+    for (int i = tid; i <= L; i += 256) {
+        int d = 0;
+        if (i >= s && i <= L - s)
+            for (int k = 0; k < s; ++k) d += P[i + k] - P[i - 1 - k];
+        D[i] = d;
+    }
+    __syncthreads();
+    // edges: index i = 256 k + tid of chunk k; i <= L - s <= 1023
+    unsigned long long mk[4];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = 256 * k + tid;
+        bool e = false;
+        if (i >= s && i <= L - s) {
+            const int d = D[i], dp = D[i - 1], dn = D[i + 1];
+            const bool up = d >= thr && d > dp && d >= dn, down = -d >= thr && d < dp && d <= dn;
+            e = (pol >= 0 && up) || (pol <= 0 && down);
+        }
+        mk[k] = __ballot(e);
+        mine |= (uint32_t)e << k;
+        if (lane == 0) wcnt[k][wave] = __popcll(mk[k]);
+    }
+    __syncthreads();
+    int base[4] = {0, 0, 0, 0}, total = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        if ((q & 3) == wave) base[q >> 2] = total;
+        total += wcnt[q >> 2][q & 3];
+    }
+    int4* out = c.edges + J.p.out_off;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!((mine >> k) & 1u)) continue;
+        const int rank = base[k] + __popcll(mk[k] & ((1ull << lane) - 1ull));
+        const int i = 256 * k + tid;
+        if (rank < c.cap) out[rank] = make_int4(i, D[i - 1], D[i], D[i + 1]);
+    }
+    if (tid < c.cap && tid >= total) out[tid] = make_int4(0, 0, 0, 0);
+    if (tid == 0) c.counts[blockIdx.x] = total;
+}
+
+bool launch_caliper(const CaliperArgs& a, hipStream_t st) {
+    if (a.njobs <= 0) return true;
+    if (a.cap < 1 || a.cap > kCaliperMaxCap || !a.edges || !a.counts) return false;
+    hipLaunchKernelGGL(k_caliper, dim3((unsigned)a.njobs), dim3(256), 0, st, a);
+    return true;
+}
+
 // ============================================================================================== variation model
 // k_model_accum (fpm_model_train_last / fpm_model_train_at): the per-pixel sum and sum of squares
 // of the patches of a job table, none of them written.  k_patch_warp's tile and 4 pixels per lane; a workgroup owns one

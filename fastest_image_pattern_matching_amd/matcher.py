@@ -468,6 +468,112 @@ def align_update(src_w: int, src_h: int, rect, lt, angle: float, du: float, dv: 
     return (ox.value, oy.value), oa.value
 
 
+# -- edge calipers (fpm_caliper_* / fpm_last_calipers / fpm_calipers_at): edges measured across every hit -------------
+# fpm_caliper, fpm_edge_raw, fpm_edge and fpm_caliper_summary, field for field
+CALIPER_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Caliper._fields_], align=True)
+EDGE_RAW_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.EdgeRaw._fields_], align=True)
+EDGE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Edge._fields_], align=True)
+CALIPER_SUMMARY_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.CaliperSummary._fields_], align=True)
+assert CALIPER_DTYPE.itemsize == C.sizeof(L.Caliper) == 48 and EDGE_DTYPE.itemsize == C.sizeof(L.Edge) == 64
+assert CALIPER_SUMMARY_DTYPE.itemsize == C.sizeof(L.CaliperSummary) == 32 and EDGE_RAW_DTYPE.itemsize == 16
+
+
+def caliper(cx: float, cy: float, phi: float, length: int, width: int, half: int = 2, contrast: int = 12,
+            polarity: int = 0) -> np.ndarray:
+    """One caliper as a CALIPER_DTYPE record: the centre (cx, cy) of its sample grid in template coordinates, the scan
+    direction ``phi`` in degrees in the template's frame (0 = along +x), ``length`` samples along the scan and ``width``
+    across it, ``half`` samples summed on each side of a boundary, the least step ``contrast`` in gray levels, and
+    ``polarity`` +1 (dark to bright along the scan), -1 or 0 (both).  Raises ValueError outside the ranges of
+    include/fpm.h.  Pure: no device."""
+    vals = [int(v) for v in (length, width, half, contrast, polarity)]
+    if vals != [length, width, half, contrast, polarity]:
+        raise ValueError("length, width, half, contrast and polarity must be whole numbers")
+    length, width, half, contrast, polarity = vals
+    if not (np.isfinite(cx) and np.isfinite(cy) and np.isfinite(phi)):
+        raise ValueError("cx, cy and phi must be finite")
+    if not 2 <= length <= L.CALIPER_MAX_LENGTH or not 1 <= width <= L.CALIPER_MAX_WIDTH:
+        raise ValueError(f"length {length} must be 2 .. {L.CALIPER_MAX_LENGTH}, width {width} 1 .. {L.CALIPER_MAX_WIDTH}")
+    if not 1 <= half <= L.CALIPER_MAX_HALF or 2 * half > length:
+        raise ValueError(f"half {half} must be 1 .. {L.CALIPER_MAX_HALF} with 2 half <= length")
+    if not 1 <= contrast <= 255 or polarity not in (-1, 0, 1):
+        raise ValueError("contrast must be 1 .. 255 and polarity +1, -1 or 0")
+    rec = np.zeros((), CALIPER_DTYPE)
+    rec["cx"], rec["cy"], rec["phi"] = float(cx), float(cy), float(phi)
+    rec["length"], rec["width"], rec["half"], rec["contrast"], rec["polarity"] = length, width, half, contrast, polarity
+    return rec
+
+
+def _calipers(cals) -> np.ndarray:
+    """A contiguous CALIPER_DTYPE array of one or more calipers (records of caliper(), or such an array)."""
+    if isinstance(cals, np.ndarray) and cals.dtype == CALIPER_DTYPE:
+        arr = np.ascontiguousarray(cals).reshape(-1)
+    else:
+        arr = np.array([np.asarray(c, CALIPER_DTYPE).reshape(()) for c in cals], CALIPER_DTYPE).reshape(-1)
+    if not 1 <= arr.size <= L.CALIPER_MAX_CALS:
+        raise ValueError(f"1 .. {L.CALIPER_MAX_CALS} calipers expected, got {arr.size}")
+    return arr
+
+
+def _caliper_ptr(cal):
+    arr = _calipers([cal] if not (isinstance(cal, np.ndarray) and cal.ndim >= 1) else cal)
+    if arr.size != 1:
+        raise ValueError("one caliper expected")
+    return arr, arr.ctypes.data_as(C.POINTER(L.Caliper))
+
+
+def caliper_pose(lt, angle: float, cal):
+    """fpm_caliper_pose: ``((lt_x, lt_y), angle)`` -- the pose at which caliper ``cal`` samples on a hit at ptLT ``lt``
+    (as f32) and ``angle`` (degrees): its rectangle (0, 0, length, width) at that pose is the caliper's sample grid.
+    ``lt`` comes back as float32 values.  Host only (no device)."""
+    arr, p = _caliper_ptr(cal)
+    ox, oy, oa = C.c_float(), C.c_float(), C.c_double()
+    rc = L.load().fpm_caliper_pose(float(np.float32(lt[0])), float(np.float32(lt[1])), float(angle), p, C.byref(ox),
+                                   C.byref(oy), C.byref(oa))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_caliper_pose failed with {rc}")
+    return (ox.value, oy.value), oa.value
+
+
+def caliper_edges_host(profile, cal, cap: int = 8):
+    """fpm_caliper_edges_host: the step filter and edge rules of include/fpm.h on a profile of ``cal['length']`` integers
+    (each 0 .. 255 width): ``(raw, n_edges, flags)`` with ``raw`` an EDGE_RAW_DTYPE array of the first min(n_edges, cap)
+    edges in ascending index and ``flags`` L.CALIPER_TRUNCATED when there are more.  Host only (no device)."""
+    arr, p = _caliper_ptr(cal)
+    prof = np.ascontiguousarray(profile, np.int32).reshape(-1)
+    if prof.size != int(arr[0]["length"]) or not np.array_equal(prof, np.asarray(profile).reshape(-1)):
+        raise ValueError("profile must hold cal['length'] int32 values")
+    if int(cap) != cap or not 1 <= int(cap) <= L.CALIPER_MAX_CAP:
+        raise ValueError(f"cap {cap!r} must be a whole number 1 .. {L.CALIPER_MAX_CAP}")
+    raw = np.zeros(int(cap), EDGE_RAW_DTYPE)
+    n, flags = C.c_int32(), C.c_int32()
+    rc = L.load().fpm_caliper_edges_host(prof.ctypes.data_as(C.POINTER(C.c_int32)), p, int(cap),
+                                         raw.ctypes.data_as(C.POINTER(L.EdgeRaw)), C.byref(n), C.byref(flags))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_caliper_edges_host failed with {rc}")
+    return raw[:min(n.value, int(cap))], n.value, flags.value
+
+
+def caliper_derive(cal, lt_k, angle_k: float, raw) -> np.ndarray:
+    """fpm_caliper_derive: the raw records ``raw`` (EDGE_RAW_DTYPE, or rows of index, d_prev, d, d_next) of caliper
+    ``cal`` sampled at the pose (``lt_k`` as f32, ``angle_k``) as an EDGE_DTYPE array: the sub-sample position t, the
+    contrast in gray levels, the edge point in template (tx, ty) and source (sx, sy) coordinates.  Host only."""
+    arr, p = _caliper_ptr(cal)
+    if isinstance(raw, np.ndarray) and raw.dtype == EDGE_RAW_DTYPE:
+        r = np.ascontiguousarray(raw).reshape(-1)
+    else:
+        rows = np.asarray(raw, np.int64).reshape(-1, 4)
+        r = np.zeros(len(rows), EDGE_RAW_DTYPE)
+        for i, name in enumerate(EDGE_RAW_DTYPE.names):
+            r[name] = rows[:, i]
+    out = np.zeros(len(r), EDGE_DTYPE)
+    rc = L.load().fpm_caliper_derive(p, float(np.float32(lt_k[0])), float(np.float32(lt_k[1])), float(angle_k),
+                                     r.ctypes.data_as(C.POINTER(L.EdgeRaw)), len(r),
+                                     out.ctypes.data_as(C.POINTER(L.Edge)))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_caliper_derive failed with {rc}")
+    return out
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -1364,6 +1470,75 @@ class TemplateMatcher:
         ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
         if self._lib.fpm_align_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
             raise ValueError("fpm_align_profile failed")
+        return ms.value, n.value, b.value
+
+    # -- edge calipers: edges measured across every hit, on the device (fpm_last_calipers / fpm_calipers_at) --------
+    @staticmethod
+    def _caliper_buffers(n, cals, cap, profiles):
+        if int(cap) != cap or not 1 <= int(cap) <= L.CALIPER_MAX_CAP:
+            raise ValueError(f"cap {cap!r} must be a whole number 1 .. {L.CALIPER_MAX_CAP}")
+        K, cap = len(cals), int(cap)
+        if n * K * cap > L.CALIPER_MAX_SLOTS:
+            raise ValueError(f"{n} hits x {K} calipers x cap {cap} above {L.CALIPER_MAX_SLOTS} records")
+        summary = np.zeros((n, K), CALIPER_SUMMARY_DTYPE)
+        edges = np.zeros((n, K, cap), EDGE_DTYPE)
+        stride = int(cals["length"].max())
+        prof = np.zeros((n, K, stride), np.int32) if profiles else None
+        return summary, edges, prof, stride
+
+    def last_calipers(self, cals, source: int = 0, cap: int = 8, profiles: bool = False):
+        """The calipers ``cals`` (records of caliper()) measured on every result of the last search, where the pixels
+        are: one launch of k_caliper, no image crosses the host (fpm_last_calipers).  Returns ``(summary, edges)``: a
+        CALIPER_SUMMARY_DTYPE array (n_hits, K) -- n_edges (the true count), n_returned, strongest (index of the
+        returned edge with the largest step, -1: none), flags (L.CALIPER_TRUNCATED: more than ``cap`` edges, the first
+        ``cap`` by index returned; L.CALIPER_OUTSIDE: the caliper leaves the source, border zeros are in its profile)
+        and the sampling pose -- and an EDGE_DTYPE array (n_hits, K, cap), the records behind n_returned zero: index,
+        the three steps d_prev, d, d_next, the sub-sample position t along the scan, the contrast in gray levels and
+        the edge point in template (tx, ty) and source (sx, sy) coordinates.  Hits come in result order of ``source``
+        (``source=-1``: all sources, in source order), sampled at the raw poses, or the aligned ones after
+        align_last(adopt=True).  ``profiles=True`` adds the int32 profiles, (n_hits, K, the largest length), zero
+        from a caliper's length on.  Under setBitwiseNot(True) the polarities are those of the inverted plane."""
+        arr = _calipers(cals)
+        pc = arr.ctypes.data_as(C.POINTER(L.Caliper))
+        if int(cap) != cap or not 1 <= int(cap) <= L.CALIPER_MAX_CAP:
+            raise ValueError(f"cap {cap!r} must be a whole number 1 .. {L.CALIPER_MAX_CAP}")
+        n = C.c_int32()
+        rc = self._lib.fpm_last_calipers(self._ctx, int(source), pc, len(arr), int(cap), None, None, None, 0, 0, C.byref(n))
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_calipers")
+        summary, edges, prof, stride = self._caliper_buffers(n.value, arr, cap, profiles)
+        if n.value:
+            rc = self._lib.fpm_last_calipers(self._ctx, int(source), pc, len(arr), int(cap),
+                                             summary.ctypes.data_as(C.POINTER(L.CaliperSummary)),
+                                             edges.ctypes.data_as(C.POINTER(L.Edge)),
+                                             prof.ctypes.data_as(C.POINTER(C.c_int32)) if profiles else None, stride,
+                                             n.value, C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_calipers")
+        return (summary, edges, prof) if profiles else (summary, edges)
+
+    def calipers_at(self, src_index, lts, angles, cals, cap: int = 8, profiles: bool = False):
+        """last_calipers at poses the caller supplies, on the staged sources (fpm_calipers_at); poses as patches_at.
+        Needs staged sources, not a search; nothing in the matcher changes."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        arr = _calipers(cals)
+        summary, edges, prof, stride = self._caliper_buffers(len(idx), arr, cap, profiles)
+        rc = self._lib.fpm_calipers_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                       len(idx), arr.ctypes.data_as(C.POINTER(L.Caliper)), len(arr), int(cap),
+                                       summary.ctypes.data_as(C.POINTER(L.CaliperSummary)),
+                                       edges.ctypes.data_as(C.POINTER(L.Edge)),
+                                       prof.ctypes.data_as(C.POINTER(C.c_int32)) if profiles else None, stride)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "calipers_at")
+        return (summary, edges, prof) if profiles else (summary, edges)
+
+    def caliper_profile(self):
+        """``(ms, launches, bytes)`` of k_caliper, collected under profile(True) and cleared by profile_reset
+        (fpm_caliper_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_caliper_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError("fpm_caliper_profile failed")
         return ms.value, n.value, b.value
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------

@@ -627,6 +627,124 @@ int fpm_blobs_set_round(fpm_ctx* ctx, int32_t images);   /* images per round of 
  * k_blob_flatten, 3 = k_blob_slots, 4 = k_blob_features; bytes = the excess pixels and plane bytes read and written. */
 int fpm_blobs_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
 
+/* --- edge calipers: edges measured across every hit, on the device (no reference equivalent) --------------------------
+ * The entries above answer "is the part good"; a caliper answers "how big is it".  A caliper is a narrow rectangle drawn
+ * on the taught image across an edge; on every hit it reports where that edge lies, to a fraction of a sample.  Widths,
+ * gaps and pin positions are differences of two such numbers.  Everything a caliper needs is resident after a staged
+ * search (level 0 of every source, the raw or adopted poses, the patch family's sampler), and the results are a few
+ * integers per edge: no image crosses the host.
+ * Caliper: fpm_caliper, 48 bytes, no padding.  (cx, cy) = the centre of the sample grid in template coordinates; phi =
+ * the scan direction in degrees in the template's frame (0 = along +x); length L = 2 .. 1024 samples along the scan;
+ * width W = 1 .. 256 samples across it; half s = 1 .. 16 with 2 s <= L; contrast c = 1 .. 255 gray levels; polarity +1
+ * (dark to bright along the scan), -1 or 0 (both); reserved = 0.  The centre and the rectangle may lie outside the
+ * template and outside the source; pixels outside the source are 0, as in a patch.
+ * Sampling pose (fpm_caliper_pose), in f64 with glibc cos / sin of degrees * (pi / 180), the expression of
+ * fpm_align_update.  With hl = (L - 1) / 2, hw = (W - 1) / 2, (cp, sp) = cos, sin of phi and (c, s) those of the hit's
+ * angle:
+ *     ox = cx - (hl cp - hw sp),  oy = cy - (hl sp + hw cp)           (the template point of sample (0, 0))
+ *     lt_k = ((float)(lt_x + (ox c - oy s)), (float)(lt_y + (ox s + oy c)))      (each rounded to f32 once)
+ *     angle_k = angle + phi
+ * This is the header's convention for where a pose puts a template point in the source, lt + L (x, y) with L = [[cos a,
+ * -sin a], [sin a, cos a]], which fpm_align_update takes as exact.
+ * Pixels.  I_k(u, v) is pixel (u, v) of the patch fpm_patches_at gives for the rectangle (0, 0, L, W) at the pose (lt_k,
+ * angle_k) on that source: same matrix, same fixed-point bilinear arithmetic, border 0, the inverted plane under
+ * bitwise_not -- so under bitwise_not the polarities are those of the INVERTED plane: a dark-to-bright edge of the
+ * image as acquired is polarity -1.
+ * Profile.  P[u] = sum over v of I_k(u, v), u = 0 .. L - 1: exact integers, 0 <= P <= 255 W.
+ * Step.  D[i] = (P[i] + .. + P[i + s - 1]) - (P[i - 1] + .. + P[i - s]) for i = s .. L - s, the step across the boundary
+ * between samples i - 1 and i; D = 0 outside that range.  |D| <= 16 * 255 * 256 = 1,044,480.
+ * Edges.  For p = +1 or -1 let A = p D.  Index i is an edge of polarity p iff A[i] >= c s W and A[i] > A[i - 1] and A[i]
+ * >= A[i + 1] (the first sample of a plateau).  Polarity 0 is the union of both lists (an index cannot be in both).
+ * Edges come in ascending index.
+ * Capacity.  cap_per_caliper = 1 .. 64.  The true count is always reported; with more edges than capacity the first
+ * cap_per_caliper by index come back and the caliper carries FPM_CALIPER_TRUNCATED.  One workgroup owns a caliper, so
+ * unlike the blobs of a truncated image this is fully determined.  Records behind n_returned are zero-filled.
+ * Raw record and derivation.  The device writes four exact integers per edge (fpm_edge_raw): index, d_prev = D[i - 1], d
+ * = D[i], d_next = D[i + 1].  The host derives the rest in f64 (fpm_caliper_derive), integers combined first, then
+ * converted, no fused multiply-add.  With g = sign(d):
+ *     a- = g d_prev, a0 = g d, a+ = g d_next;  den = (a- - a0) + (a+ - a0)                (< 0 always)
+ *     delta = 0.5 * (double)(a- - a+) / (double)den                                        (in (-0.5, 0.5])
+ *     t = ((double)index - 0.5) + delta;  contrast = (double)|d| / (double)(s W)
+ *     template point (tx, ty) = (ox + (t cp - hw sp), oy + (t sp + hw cp))
+ *     source point   (sx, sy) = lt_k + ((t ck - hw sk), (t sk + hw ck)),  (ck, sk) = cos, sin of angle_k, lt_k the f32
+ *                               sampling pose widened to f64
+ * Record: fpm_edge, 64 bytes, no padding.  Summary: fpm_caliper_summary, 32 bytes, no padding, one per (hit, caliper):
+ * strongest = the returned edge with the largest |d|, the earliest on ties, -1 when there is none; lt_x, lt_y, angle =
+ * the sampling pose.  FPM_CALIPER_OUTSIDE is set on the host, in f64, when a corner sample (0, 0), (L - 1, 0), (0, W - 1)
+ * or (L - 1, W - 1) maps outside [0, sw - 1] x [0, sh - 1] through the inverted patch matrix: border zeros are in the
+ * profile.
+ * Limits.  n_cals = 1 .. 64; hits x n_cals x cap_per_caliper <= 2^22.  Any range violation, a non-finite cx, cy or phi,
+ * or a sampling pose beyond the samplers' 2^20 range: FPM_E_INVALID_ARG, nothing launched, nothing written.
+ * Launch.  k_caliper, one per call, one 256-lane workgroup per (hit, caliper), never part of a search or of a captured
+ * graph.  Integer arithmetic throughout: the results do not depend on any schedule.  The calls change no search state:
+ * results, poses, candidates, staged sources, template and model stay as they were.  Additive entries: FPM_ABI_VERSION
+ * is unchanged. */
+typedef struct fpm_caliper {
+    double cx, cy;               /* centre of the sample grid, template coordinates                  */
+    double phi;                  /* scan direction, degrees, template frame                          */
+    int32_t length, width;       /* L samples along the scan, W across it                            */
+    int32_t half;                /* s: samples summed on each side of a boundary                     */
+    int32_t contrast;            /* c: least step in gray levels                                     */
+    int32_t polarity;            /* +1, -1 or 0 (both)                                               */
+    int32_t reserved;            /* 0 */
+} fpm_caliper;
+typedef struct fpm_edge_raw {
+    int32_t index, d_prev, d, d_next;
+} fpm_edge_raw;
+typedef struct fpm_edge {
+    int32_t index, d_prev, d, d_next;
+    double t;                    /* sub-sample position along the scan, in samples                   */
+    double contrast;             /* |d| / (s W): the step in gray levels                             */
+    double tx, ty;               /* the edge point in template coordinates                           */
+    double sx, sy;               /* and in source coordinates                                        */
+} fpm_edge;
+typedef struct fpm_caliper_summary {
+    int32_t n_edges;             /* the true count (may exceed cap_per_caliper)                      */
+    int32_t n_returned;          /* min(n_edges, cap_per_caliper)                                    */
+    int32_t strongest;           /* index into the caliper's returned records, -1 = none             */
+    int32_t flags;               /* FPM_CALIPER_TRUNCATED | FPM_CALIPER_OUTSIDE                      */
+    float lt_x, lt_y;            /* the sampling pose                                                */
+    double angle;
+} fpm_caliper_summary;
+#define FPM_CALIPER_TRUNCATED 1
+#define FPM_CALIPER_OUTSIDE 2
+#define FPM_CALIPER_MAX_LENGTH 1024
+#define FPM_CALIPER_MAX_WIDTH 256
+#define FPM_CALIPER_MAX_HALF 16
+#define FPM_CALIPER_MAX_CALS 64          /* n_cals */
+#define FPM_CALIPER_MAX_CAP 64           /* cap_per_caliper */
+#define FPM_CALIPER_MAX_SLOTS (1 << 22)  /* hits * n_cals * cap_per_caliper */
+
+/* host only, no context: the sampling pose of a caliper on a hit at (lt, angle), by the rule above */
+int fpm_caliper_pose(float lt_x, float lt_y, double angle, const fpm_caliper* cal, float* ltk_x, float* ltk_y,
+                     double* angle_k);
+/* host only, no context: the step and edge rules on a caller's profile of cal->length entries, each 0 .. 255 W (the
+ * reference form, as fpm_blobs_host is for blobs).  out holds cap_per_caliper records: the first min(*n_edges,
+ * cap_per_caliper) are written, the rest zero-filled; *flags receives FPM_CALIPER_TRUNCATED or 0. */
+int fpm_caliper_edges_host(const int32_t* profile, const fpm_caliper* cal, int32_t cap_per_caliper, fpm_edge_raw* out,
+                           int32_t* n_edges, int32_t* flags);
+/* host only, no context: n raw records of a caliper sampled at the pose (ltk, angle_k) into n fpm_edge, by the rule
+ * above.  FPM_E_INVALID_ARG also for a record that is no edge (d = 0, an index outside half .. length - half, or not
+ * a- < a0 and a+ <= a0, the local-maximum rule, from which den < 0 follows); nothing is written then. */
+int fpm_caliper_derive(const fpm_caliper* cal, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw* raw,
+                       int32_t n, fpm_edge* out);
+/* The calipers at caller-supplied poses on the staged sources.  Poses and state rules as fpm_patches_at with a non-NULL
+ * rectangle, except that no template is needed: staged sources are, a search is not.  summary: [pose][caliper]; edges:
+ * [pose][caliper][cap_per_caliper]; profiles (may be NULL): int32 [pose][caliper][profile_stride] with profile_stride >=
+ * the largest length, the entries from a caliper's length on 0. */
+int fpm_calipers_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                    const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper, fpm_caliper_summary* summary,
+                    fpm_edge* edges, int32_t* profiles, int32_t profile_stride);
+/* The calipers over the hits of the last search in result order (source = -1: of all sources), sampled at the context's
+ * last poses: the raw ones, or the aligned ones after FPM_ALIGN_ADOPT, exactly as fpm_last_compare.  source, cap (hits),
+ * *n, the count-only call (cap = 0 with null outputs) and every state rule are fpm_last_compare's. */
+int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper,
+                      fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t profile_stride,
+                      int32_t cap /* hits */, int32_t* n);
+/* Timing of k_caliper, collected under fpm_profile_enable and cleared by fpm_profile_reset as fpm_align_profile's (no
+ * FPM_K_* index: FPM_K_COUNT is unchanged).  bytes = L W source pixels per job + the records and profiles written. */
+int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent

@@ -345,6 +345,14 @@ SIGNATURES = {
     "fpm_last_calipers": (C.c_int, [_P, C.c_int32, C.POINTER(Caliper), C.c_int32, C.c_int32, C.POINTER(CaliperSummary),
                                     C.POINTER(Edge), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_caliper_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_mask_set": (C.c_int, [_P, _U8P, C.c_int32, C.c_int32, C.c_size_t]),
+    "fpm_mask_set_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_size_t, _P]),
+    "fpm_mask_clear": (C.c_int, [_P]),
+    "fpm_mask_enable": (C.c_int, [_P, C.c_int32]),
+    "fpm_mask_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int32)]),
+    "fpm_mask_get": (C.c_int, [_P, _U8P, C.c_size_t]),
+    "fpm_mask_count": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -250,6 +250,17 @@ struct fpm_ctx {
     // edge calipers (fpm_last_calipers / fpm_calipers_at): the raw records, counts and profiles of a call and their host copy
     DevBuf d_calout;
     PinBuf h_calout;
+    // template mask (fpm_mask_*): one u8 plane of the template's level-0 size and row pitch, 0x00 /
+    // 0xFF, zero behind a row's end; mask_host = its dense host copy (the counts, fpm_mask_get).  d_mask_in = the
+    // staging buffer (a host mask's upload, the plane being staged, the count); a set that fails leaves d_mask alone.
+    bool mask_set = false, mask_on = false;
+    int64_t mask_count = 0;
+    std::vector<uint8_t> mask_host;
+    DevBuf d_mask, d_mask_in;
+    // the used count of the rectangle asked for last (mask_count_rect): the tools ask for one rectangle call after call
+    mutable bool mask_rect_known = false;
+    mutable fpm_patch_rect mask_rect{0, 0, 0, 0};
+    mutable int64_t mask_rect_count = 0;
 };
 
 #define HIP_TRY(expr)                                                                   \
@@ -2093,6 +2104,92 @@ int compare_rect(fpm_ctx* ctx, const fpm_patch_rect* rect, fpm_patch_rect* r) {
     return FPM_OK;
 }
 
+// ---- template masks (fpm_mask_*) ----
+void mask_drop(fpm_ctx* ctx) {
+    ctx->mask_set = ctx->mask_on = false;
+    ctx->mask_count = 0;
+    ctx->mask_host.clear();
+    ctx->mask_rect_known = false;
+}
+
+// the plane the masked kernel forms read, or null: no mask, or a disabled one
+const uint8_t* mask_plane(const fpm_ctx* ctx) { return ctx->mask_set && ctx->mask_on ? ctx->d_mask.as<uint8_t>() : nullptr; }
+
+// pixels of rectangle r (inside the template) the stored mask keeps, from the host copy; counted once per rectangle
+// and mask, then remembered
+int64_t mask_count_rect(const fpm_ctx* ctx, const fpm_patch_rect& r) {
+    if (ctx->mask_rect_known && ctx->mask_rect.x == r.x && ctx->mask_rect.y == r.y && ctx->mask_rect.w == r.w &&
+        ctx->mask_rect.h == r.h)
+        return ctx->mask_rect_count;
+    const int tw = ctx->tmpl[0].w;
+    int64_t n = 0;
+    for (int y = r.y; y < r.y + r.h; ++y) {
+        const uint8_t* row = ctx->mask_host.data() + (size_t)y * tw + r.x;
+        for (int x = 0; x < r.w; ++x) n += row[x] != 0;
+    }
+    ctx->mask_rect = r;
+    ctx->mask_rect_count = n;
+    ctx->mask_rect_known = true;
+    return n;
+}
+
+// the pixels of r a masked tool uses: all of them without an active mask
+int64_t mask_used(const fpm_ctx* ctx, const fpm_patch_rect& r) {
+    return mask_plane(ctx) ? mask_count_rect(ctx, r) : (int64_t)r.w * r.h;
+}
+
+// A mask of the template's size staged into a fresh plane by k_mask_stage, which then replaces the context's: from
+// `host` (uploaded beside the plane first) or from device-readable memory at `dev`.  The context's mask is untouched
+// until everything has succeeded.  The new mask starts enabled.  Synchronises the stream.
+int mask_install(fpm_ctx* ctx, const uint8_t* host, const uint8_t* dev, size_t stride) {
+    const TmplLevel& t0 = ctx->tmpl[0];
+    const int w = t0.w, h = t0.h;
+    const size_t plane = round_up((size_t)t0.pitch * (h + 1), (size_t)256), px = (size_t)w * h;
+    HIP_TRY(ctx->d_mask_in.ensure(plane + 256 + (host ? px : 0)));
+    uint8_t* base = ctx->d_mask_in.as<uint8_t>();
+    HIP_TRY(hipMemsetAsync(base, 0, plane + 256, ctx->stream));   // the rows' padding, which the kernels read, and the count
+    if (host) {
+        HIP_TRY(hipMemcpy2DAsync(base + plane + 256, w, host, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+        dev = base + plane + 256;
+        stride = (size_t)w;
+    }
+    if (!launch_mask_stage(dev, w, h, stride, base, t0.pitch, (unsigned long long*)(base + plane), ctx->stream)) {
+        ctx->err = "mask plane layout: rows not 64-byte aligned";
+        return FPM_E_INTERNAL;
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> hm(px);
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpy2DAsync(hm.data(), w, base, t0.pitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&count, base + plane, sizeof(count), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::swap(ctx->d_mask, ctx->d_mask_in);
+    ctx->mask_host = std::move(hm);
+    ctx->mask_rect_known = false;
+    ctx->mask_count = (int64_t)count;
+    ctx->mask_set = ctx->mask_on = true;
+    return FPM_OK;
+}
+
+// state shared by the mask entries: no search in flight, a template
+int mask_state(fpm_ctx* ctx, bool need_mask) {
+    if (ctx->pending) { ctx->err = "a search is in flight (fpm_match_staged_finish first)"; return FPM_E_INVALID_ARG; }
+    if (!ctx->learned) { ctx->err = "template not learned"; return FPM_E_NOT_LEARNED; }
+    if (need_mask && !ctx->mask_set) { ctx->err = "no template mask (fpm_mask_set / fpm_mask_set_device first)"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+int mask_dims(fpm_ctx* ctx, const void* mask, int w, int h, size_t stride) {
+    if (!mask) { ctx->err = "null mask"; return FPM_E_INVALID_ARG; }
+    if (w != ctx->tmpl[0].w || h != ctx->tmpl[0].h) {
+        ctx->err = "the mask must have the learned template's size, " + std::to_string(ctx->tmpl[0].w) + " x " +
+                   std::to_string(ctx->tmpl[0].h);
+        return FPM_E_INVALID_ARG;
+    }
+    if (stride < (size_t)w) { ctx->err = "stride below the mask's width"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
 // What the sums give (include/fpm.h states the operation order; the file is built with -ffp-contract=off, so the
 // product and the sum of a table entry are two roundings).  lut may be null.
 void compare_derive(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt, int64_t sit, bool normalize,
@@ -2116,6 +2213,19 @@ void compare_derive(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt,
     }
 }
 
+// compare_derive over the n used pixels of a masked rectangle; with none (the mask misses the rectangle) the neutral
+// values: zncc 0, gain 1, offset 0, the identity table.
+void compare_derive_used(int64_t n, const CompareAcc& a, bool normalize, double* zncc, double* gain, double* offset,
+                         uint8_t* lut) {
+    if (n == 0) {
+        *zncc = 0.0; *gain = 1.0; *offset = 0.0;
+        if (lut) for (int v = 0; v < 256; ++v) lut[v] = (uint8_t)v;
+        return;
+    }
+    compare_derive(n, (int64_t)a.s[kCmpSumI], (int64_t)a.s[kCmpSumII], (int64_t)a.s[kCmpSumT], (int64_t)a.s[kCmpSumTT],
+                   (int64_t)a.s[kCmpSumIT], normalize, zncc, gain, offset, lut);
+}
+
 // The first half of a normalised comparison (and of normalised training and inspection of the variation model): the
 // sums launch into c.acc = d_cmpacc (zero-filled by the caller), the sums to h_cmpacc, a table per hit from them, the
 // tables to the device beside the job table (stage_patch_jobs' `extra` bytes: 256 n), their address in *d_luts.
@@ -2124,7 +2234,8 @@ int compare_norm_tables(fpm_ctx* ctx, CompareArgs c, const fpm_patch_rect& r, in
     const size_t accb = sizeof(CompareAcc) * (size_t)n, lut_off = patch_tab_bytes(n);
     c.p.out = nullptr;
     {
-        ProfScope ps(ctx, FPM_K_COMPARE, 2 * (int64_t)n * r.w * r.h);   // source pixels read + template pixels read
+        // source pixels read + template pixels read (+ mask bytes read)
+        ProfScope ps(ctx, FPM_K_COMPARE, (2 + (c.mask ? 1 : 0)) * (int64_t)n * r.w * r.h);
         if (!launch_patch_compare(c, kCompareSums, ctx->stream)) {
             ctx->err = "too many patch tiles for one launch";
             return FPM_E_INVALID_ARG;
@@ -2134,12 +2245,11 @@ int compare_norm_tables(fpm_ctx* ctx, CompareArgs c, const fpm_patch_rect& r, in
     CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
     HIP_TRY(hipMemcpyAsync(h, ctx->d_cmpacc.p, accb, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // also: the job table has left h_patchtab
-    const int64_t area = (int64_t)r.w * r.h;
+    const int64_t used = c.mask ? mask_count_rect(ctx, r) : (int64_t)r.w * r.h;
     uint8_t* luts = ctx->h_patchtab.as<uint8_t>(lut_off);
     for (int i = 0; i < n; ++i) {
         double z, g, o;
-        compare_derive(area, (int64_t)h[i].s[kCmpSumI], (int64_t)h[i].s[kCmpSumII], (int64_t)h[i].s[kCmpSumT],
-                       (int64_t)h[i].s[kCmpSumTT], (int64_t)h[i].s[kCmpSumIT], true, &z, &g, &o, luts + (size_t)256 * i);
+        compare_derive_used(used, h[i], true, &z, &g, &o, luts + (size_t)256 * i);
     }
     HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.as<uint8_t>(lut_off), luts, (size_t)256 * n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
@@ -2173,12 +2283,15 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     c.rx = r.x; c.ry = r.y;
     c.threshold = threshold;
     c.acc = ctx->d_cmpacc.as<CompareAcc>();
-    // bytes: source pixels read + template pixels read (+ difference pixels written), per launch
+    c.mask = mask_plane(ctx);
+    const int64_t used = mask_used(ctx, r);
+    // bytes: source pixels read + template pixels read (+ mask bytes read) (+ difference pixels written), per launch
     const int64_t px = (int64_t)n * r.w * r.h;
+    const int rd = 2 + (c.mask ? 1 : 0);
     const char* too_many = "too many patch tiles for one launch";
     CompareAcc* h = ctx->h_cmpacc.as<CompareAcc>();
     if (!norm) {
-        ProfScope ps(ctx, FPM_K_COMPARE, (2 + (c.p.out ? 1 : 0)) * px);
+        ProfScope ps(ctx, FPM_K_COMPARE, (rd + (c.p.out ? 1 : 0)) * px);
         if (!launch_patch_compare(c, kCompareRaw, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
     }
     HIP_TRY(hipGetLastError());
@@ -2188,7 +2301,7 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
         if (rc != FPM_OK) return rc;
         c.p = patch_args(ctx, r, n, d, pitch, pbytes);
         {
-            ProfScope ps(ctx, FPM_K_COMPARE, (2 + (d ? 1 : 0)) * px);
+            ProfScope ps(ctx, FPM_K_COMPARE, (rd + (d ? 1 : 0)) * px);
             if (!launch_patch_compare(c, kCompareDevLut, ctx->stream)) { ctx->err = too_many; return FPM_E_INVALID_ARG; }
         }
         HIP_TRY(hipGetLastError());
@@ -2202,7 +2315,7 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     prof_collect(ctx);
     for (int i = 0; i < n; ++i) {
         fpm_compare_stats& s = out[i];
-        s.n = (int64_t)r.w * r.h;
+        s.n = used;
         s.sum_i = (int64_t)h[i].s[kCmpSumI]; s.sum_ii = (int64_t)h[i].s[kCmpSumII];
         s.sum_t = (int64_t)h[i].s[kCmpSumT]; s.sum_tt = (int64_t)h[i].s[kCmpSumTT];
         s.sum_it = (int64_t)h[i].s[kCmpSumIT]; s.sum_abs = (int64_t)h[i].s[kCmpSumAbs];
@@ -2210,7 +2323,7 @@ int compare_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
         s.n_over = (int32_t)m[kCmpNOver - kCmpNOver]; s.max_abs = (int32_t)m[kCmpMaxAbs - kCmpNOver];
         s.x0 = r.w - (int32_t)m[kCmpX0 - kCmpNOver]; s.y0 = r.h - (int32_t)m[kCmpY0 - kCmpNOver];
         s.x1 = (int32_t)m[kCmpX1 - kCmpNOver] - 1; s.y1 = (int32_t)m[kCmpY1 - kCmpNOver] - 1;
-        compare_derive(s.n, s.sum_i, s.sum_ii, s.sum_t, s.sum_tt, s.sum_it, norm, &s.zncc, &s.gain, &s.offset, nullptr);
+        compare_derive_used(used, h[i], norm, &s.zncc, &s.gain, &s.offset, nullptr);
     }
     return FPM_OK;
 }
@@ -2260,6 +2373,7 @@ int learn_fail(fpm_ctx* ctx, int rc) {
     ctx->tmpl.clear();
     ctx->tmpl_gen++;
     ctx->model_n = 0;
+    mask_drop(ctx);
     return rc;
 }
 
@@ -2365,6 +2479,7 @@ int learn_from_image(fpm_ctx* ctx, const void* d_image, int w, int h, size_t str
                      hipStream_t producer) {
     std::vector<TmplLevel> lv;
     ctx->model_n = 0;   // the variation model belongs to the template before
+    mask_drop(ctx);     // and so does the mask
     int rc = learn_begin(ctx, w, h, lv);
     if (rc != FPM_OK) return rc;
     if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
@@ -2394,6 +2509,7 @@ int learn_from_image(fpm_ctx* ctx, const void* d_image, int w, int h, size_t str
 int learn_from_pose(fpm_ctx* ctx, const fpm_patch_rect& r, const PatchPose& pose) {
     std::vector<TmplLevel> lv;
     ctx->model_n = 0;   // the variation model belongs to the template before
+    mask_drop(ctx);     // and so does the mask
     int rc = learn_begin(ctx, r.w, r.h, lv);
     if (rc != FPM_OK) return rc;
     const TmplLevel& l0 = lv[0];
@@ -2465,6 +2581,7 @@ int model_norm_args(fpm_ctx* ctx, const fpm_patch_rect& r, int n, CompareArgs* c
     c->tp = t0.pitch;
     c->rx = r.x; c->ry = r.y;
     c->acc = ctx->d_cmpacc.as<CompareAcc>();
+    c->mask = mask_plane(ctx);   // the tables of a normalised call come from the used pixels
     return FPM_OK;
 }
 
@@ -2583,6 +2700,10 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     c.hi = c.lo + (size_t)mp * r.h;
     c.mp = mp;
     c.acc = ctx->d_insacc.as<InspectAcc>();
+    c.mask = mask_plane(ctx);
+    c.mkp = ctx->tmpl[0].pitch;
+    c.mx = r.x; c.my = r.y;
+    const int64_t used = mask_used(ctx, r);
     if (norm) {
         CompareArgs s;
         rc = model_norm_args(ctx, r, n, &s);
@@ -2590,8 +2711,8 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
         if (rc != FPM_OK) return rc;
     }
     {
-        // bytes: source pixels read + lo and hi read (+ excess pixels written)
-        ProfScope ps(ctx, kProfModelInspect, (3 + (d ? 1 : 0)) * (int64_t)n * r.w * r.h);
+        // bytes: source pixels read + lo and hi read (+ mask bytes read) (+ excess pixels written)
+        ProfScope ps(ctx, kProfModelInspect, (3 + (c.mask ? 1 : 0) + (d ? 1 : 0)) * (int64_t)n * r.w * r.h);
         if (!launch_model_inspect(c, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
     }
     HIP_TRY(hipGetLastError());
@@ -2607,7 +2728,7 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
     for (int i = 0; i < n; ++i) {
         fpm_inspect_stats& s = out[i];
         const uint32_t* f = h[i].f;
-        s.n = (int64_t)r.w * r.h;
+        s.n = used;
         s.sum_excess = (int64_t)f[kInsSumExcess];
         s.n_low = (int32_t)f[kInsNLow]; s.n_high = (int32_t)f[kInsNHigh]; s.max_excess = (int32_t)f[kInsMaxExcess];
         s.x0 = r.w - (int32_t)f[kInsX0]; s.y0 = r.h - (int32_t)f[kInsY0];
@@ -2615,8 +2736,7 @@ int inspect_to_host(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pat
         s.gain = 1.0; s.offset = 0.0;
         if (norm) {
             double z;
-            compare_derive(s.n, (int64_t)sums[i].s[kCmpSumI], (int64_t)sums[i].s[kCmpSumII], (int64_t)sums[i].s[kCmpSumT],
-                           (int64_t)sums[i].s[kCmpSumTT], (int64_t)sums[i].s[kCmpSumIT], true, &z, &s.gain, &s.offset, nullptr);
+            compare_derive_used(used, sums[i], true, &z, &s.gain, &s.offset, nullptr);
         }
     }
     return FPM_OK;
@@ -2844,8 +2964,10 @@ int align_launch(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchP
     c.rx = r.x; c.ry = r.y;
     c.luts = luts;
     c.acc = ctx->d_alnacc.as<AlignAcc>();
+    c.mask = mask_plane(ctx);
     {
-        ProfScope ps(ctx, kProfAlign, 2 * (int64_t)n * r.w * r.h);   // source pixels read + template pixels read
+        // source pixels read + template pixels read (+ mask bytes read)
+        ProfScope ps(ctx, kProfAlign, (2 + (c.mask ? 1 : 0)) * (int64_t)n * r.w * r.h);
         if (!launch_patch_align(c, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
     }
     HIP_TRY(hipGetLastError());
@@ -3159,6 +3281,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_blobplanes.release(); ctx->d_blobrec.release(); ctx->d_blobimg.release();
     ctx->h_blobrec.release(); ctx->h_bloblab.release();
     ctx->d_calout.release(); ctx->h_calout.release();
+    ctx->d_mask.release(); ctx->d_mask_in.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
     for (auto& k : ctx->kp)
@@ -3193,6 +3316,7 @@ int fpm_learn(fpm_ctx* ctx, const uint8_t* gray, int32_t w, int32_t h, size_t st
     ctx->staged = false;
     ctx->src_valid = false;   // the slab's layout follows the template's pyramid depth
     ctx->model_n = 0;         // the variation model belongs to the template before
+    mask_drop(ctx);           // and so does the mask
     ctx->tmpl.clear();
     const int L = top_layer(w, h, (int)std::sqrt((double)ctx->prm.min_reduce_area));
     std::vector<TmplLevel> lv(L + 1);
@@ -3275,6 +3399,7 @@ int fpm_clear_pattern(fpm_ctx* ctx) {
     ctx->tmpl.clear();
     ctx->tmpl_gen++;
     ctx->model_n = 0;
+    mask_drop(ctx);
     return FPM_OK;
 }
 
@@ -3771,9 +3896,96 @@ int fpm_model_learn(fpm_ctx* ctx) {
     if (rc == FPM_OK) rc = learn_size(ctx, r.w, r.h);
     if (rc != FPM_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
+    // the mask is re-framed as the model is: its crop to the rectangle, which becomes the new template, so that it keeps
+    // covering the same pixels.  The crop goes through a host temporary, since the plane's pitch follows the template.
+    std::vector<uint8_t> crop;
+    const bool had_mask = ctx->mask_set, was_on = ctx->mask_on;
+    if (had_mask) {
+        const int tw = ctx->tmpl[0].w;
+        crop.resize((size_t)r.w * r.h);
+        for (int y = 0; y < r.h; ++y)
+            std::copy_n(ctx->mask_host.data() + (size_t)(r.y + y) * tw + r.x, r.w, crop.data() + (size_t)y * r.w);
+        mask_drop(ctx);
+    }
     rc = learn_from_model(ctx);
     if (rc != FPM_OK) return learn_fail(ctx, rc);
     ctx->model_rect = fpm_patch_rect{0, 0, r.w, r.h};   // the new template's frame: the region the model was trained on
+    if (had_mask) {
+        rc = mask_install(ctx, crop.data(), nullptr, (size_t)r.w);
+        if (rc != FPM_OK) return rc;   // the template and the model stand; the mask is gone
+        ctx->mask_on = was_on;
+    }
+    return FPM_OK;
+}
+
+// --- template masks -------------------------------------------------------------------
+int fpm_mask_set(fpm_ctx* ctx, const uint8_t* mask, int32_t w, int32_t h, size_t stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    int rc = mask_state(ctx, false);
+    if (rc == FPM_OK) rc = mask_dims(ctx, mask, w, h, stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return mask_install(ctx, mask, nullptr, stride);
+}
+
+int fpm_mask_set_device(fpm_ctx* ctx, const void* d_mask, int32_t w, int32_t h, size_t stride, void* producer_stream) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    int rc = mask_state(ctx, false);
+    if (rc == FPM_OK) rc = mask_dims(ctx, d_mask, w, h, stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = check_device_images(ctx, &d_mask, 1, image_extent(w, h, stride, 0, FPM_FMT_GRAY8), "mask");
+    if (rc != FPM_OK) return rc;
+    if (!ctx->in_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctx->in_ev, (hipStream_t)producer_stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->in_ev, 0));
+    return mask_install(ctx, nullptr, (const uint8_t*)d_mask, stride);
+}
+
+int fpm_mask_clear(fpm_ctx* ctx) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    const int rc = mask_state(ctx, false);
+    if (rc != FPM_OK) return rc;
+    mask_drop(ctx);
+    return FPM_OK;
+}
+
+int fpm_mask_enable(fpm_ctx* ctx, int32_t enable) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    const int rc = mask_state(ctx, true);
+    if (rc != FPM_OK) return rc;
+    ctx->mask_on = enable != 0;
+    return FPM_OK;
+}
+
+int fpm_mask_info(const fpm_ctx* ctx, int32_t* width, int32_t* height, int64_t* count, int32_t* enabled) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    const bool has = ctx->learned && ctx->mask_set;
+    if (width) *width = has ? ctx->tmpl[0].w : 0;
+    if (height) *height = has ? ctx->tmpl[0].h : 0;
+    if (count) *count = has ? ctx->mask_count : 0;
+    if (enabled) *enabled = has && ctx->mask_on ? 1 : 0;
+    return FPM_OK;
+}
+
+int fpm_mask_get(fpm_ctx* ctx, uint8_t* out, size_t stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    const int rc = mask_state(ctx, true);
+    if (rc != FPM_OK) return rc;
+    const int w = ctx->tmpl[0].w, h = ctx->tmpl[0].h;
+    if (!out || stride < (size_t)w) { ctx->err = "null buffer or stride below the mask's width"; return FPM_E_INVALID_ARG; }
+    for (int y = 0; y < h; ++y) std::copy_n(ctx->mask_host.data() + (size_t)y * w, w, out + (size_t)y * stride);
+    return FPM_OK;
+}
+
+int fpm_mask_count(fpm_ctx* ctx, const fpm_patch_rect* rect, int64_t* n) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    int rc = mask_state(ctx, true);
+    fpm_patch_rect r;
+    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
+    if (rc != FPM_OK) return rc;
+    if (!n) { ctx->err = "null count"; return FPM_E_INVALID_ARG; }
+    *n = mask_count_rect(ctx, r);
     return FPM_OK;
 }
 

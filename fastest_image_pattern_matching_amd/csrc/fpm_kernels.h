@@ -251,6 +251,7 @@ struct CompareArgs {
     int32_t threshold;       // a pixel counts as deviating when d > threshold
     const uint8_t* luts;     // [njobs][256] (kCompareDevLut), 4-byte aligned
     CompareAcc* acc;         // [njobs]
+    const uint8_t* mask;     // the template mask plane (0x00 / 0xFF, the template's pitch tp) or null: the MASK forms
 };
 // the launches of a comparison: everything at once without a table; or the sums, then (the host having built the
 // tables from them) the deviations through the tables
@@ -294,6 +295,9 @@ struct InspectArgs {
     int32_t mp;
     const uint8_t* luts;     // [njobs][256] or null
     InspectAcc* acc;         // [njobs]
+    const uint8_t* mask;     // the template mask plane (0x00 / 0xFF, row pitch mkp) or null: the MASK forms
+    int32_t mkp;
+    int32_t mx, my;          // the model rectangle's origin in the template, where the mask lives
 };
 // k_model_inspect, k_patch_warp's grid; the table form when luts is set.  Returns false for a grid past 2^31 - 1.
 bool launch_model_inspect(InspectArgs c, hipStream_t st);
@@ -314,10 +318,17 @@ struct AlignArgs {
     int32_t rx, ry;          // the rectangle's origin in the template (the rectangle lies inside it)
     const uint8_t* luts;     // [njobs][256] or null
     AlignAcc* acc;           // [njobs]
+    const uint8_t* mask;     // the template mask plane (0x00 / 0xFF, the template's pitch tp) or null: the MASK forms
 };
 // k_patch_align, k_patch_warp's grid; the table form when luts is set.  Returns false, launching nothing, for a grid past
 // 2^31 - 1 or a rectangle beyond the caps.
 bool launch_patch_align(AlignArgs c, hipStream_t st);
+// ---- template masks (fpm_mask_*).  k_mask_stage: the w x h bytes at src (`stride` bytes between
+// rows, any base alignment; device-readable memory) normalised to 0x00 / 0xFF into dst with row pitch `pitch`, a
+// multiple of 64: whole 16-byte groups are stored, zero behind a row's end.  *count (device, zeroed by the caller)
+// receives the number of used pixels.  Returns false, launching nothing, for a misaligned plane or more than 2^31 pixels.
+bool launch_mask_stage(const uint8_t* src, int w, int h, size_t stride, uint8_t* dst, int pitch,
+                       unsigned long long* count, hipStream_t st);
 // ---- edge calipers (fpm_last_calipers / fpm_calipers_at): one L x W patch per (hit, caliper), each
 // of its own size, summed across its width into a profile of L integers that never leaves LDS, then the step filter,
 // the local-maximum test and an ordered compaction of the edges.  One descriptor per job, built on the host.

@@ -2938,6 +2938,11 @@ __global__ __launch_bounds__(256) void k_patch_warp(const PatchArgs a) {
 //   DEV:  d = |L[I] - T| per pixel: sum d, max d, the count of d > threshold and those pixels' bounding box
 //   LUT:  L = the job's 256-byte table, staged in LDS (else L = identity)
 //   IMG:  d is also stored as the difference image (PatchArgs::out, as k_patch_warp stores the patch)
+//   MASK: the template mask lies beneath the patch as the template does: the same dword pair of
+//         the mask plane is the byte mask of the lane's 4 pixels (0xFF = used, 0 = ignored).  The sums take the bytes
+//         ANDed with it, a zero byte adding nothing to any dot product; d is zeroed as a value, and so leaves the sum,
+//         the maximum, the votes and the difference image.  A lane whose pixels are all ignored runs on like a lane
+//         with nu = 0.
 // Lanes past the patch's right or bottom edge take part in every barrier and in the reduction with nu = 0: they
 // sample nothing, read no template byte and add nothing.  The reduction is by DPP within a wave for the sums and the
 // maximum and by lane votes (__ballot, then scalar bit counts) for the count and the box, through LDS across the four
@@ -2974,8 +2979,8 @@ __device__ __forceinline__ void vote_box(unsigned long long mk, int u, int& cnt,
     rmin = rlo < rmin ? rlo : rmin; rmax = rhi > rmax ? rhi : rmax;
 }
 
-template <bool SUMS, bool DEV, bool LUT, bool IMG>
-__global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
+template <bool SUMS, bool DEV, bool LUT, bool IMG, bool MASK>
+__device__ __forceinline__ void patch_compare_body(const CompareArgs c) {
     __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
     __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
     __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
@@ -2996,7 +3001,7 @@ __global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
     // the template's 4 bytes beneath: an aligned dword pair funnel-shifted to the group's first byte (the row pitch is
     // a multiple of 64 and the rectangle lies inside the template: the first dword is inside the row, the second is
     // read only where it is too), cut to nu bytes
-    uint32_t tw = 0;
+    uint32_t tw = 0, mw = 0;   // mw (MASK): 0xFF in the bytes of the used pixels
     if (nu > 0) {
         const int tx = c.rx + x;
         const uint8_t* trow = c.tmpl + (size_t)(c.ry + y) * c.tp;
@@ -3005,20 +3010,28 @@ __global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
         const uint32_t hi = (tx & 3) && c0 + 4 < c.tp ? *(const uint32_t*)(trow + c0 + 4) : 0u;
         tw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)tx);
         if (nu < 4) tw &= (1u << (8 * nu)) - 1u;
+        if (MASK) {   // the mask plane has the template's pitch: the same pair of dwords, under the same conditions
+            const uint8_t* mrow = c.mask + (size_t)(c.ry + y) * c.tp;
+            const uint32_t mlo = *(const uint32_t*)(mrow + c0);
+            const uint32_t mhi = (tx & 3) && c0 + 4 < c.tp ? *(const uint32_t*)(mrow + c0 + 4) : 0u;
+            mw = __builtin_amdgcn_alignbyte(mhi, mlo, (uint32_t)tx);
+            if (nu < 4) mw &= (1u << (8 * nu)) - 1u;
+        }
     }
     // wave totals (the same value in every lane) of the fields this form emits
     uint32_t wv[kCompareFields];
 #pragma unroll
     for (int k = 0; k < kCompareFields; ++k) wv[k] = 0;
     if (SUMS) {
+        const uint32_t is = MASK ? iw & mw : iw, ts = MASK ? tw & mw : tw;   // an ignored pixel: a zero byte in both
         // a wave's 256 pixels sum to at most 65280: sum I and sum T share one word, and one fold
-        const uint32_t it = wave_fold<false>(__builtin_amdgcn_udot4(iw, 0x01010101u, 0u, false) +
-                                             (__builtin_amdgcn_udot4(tw, 0x01010101u, 0u, false) << 16));
+        const uint32_t it = wave_fold<false>(__builtin_amdgcn_udot4(is, 0x01010101u, 0u, false) +
+                                             (__builtin_amdgcn_udot4(ts, 0x01010101u, 0u, false) << 16));
         wv[kCmpSumI] = it & 0xffffu;
         wv[kCmpSumT] = it >> 16;
-        wv[kCmpSumII] = wave_fold<false>(__builtin_amdgcn_udot4(iw, iw, 0u, false));
-        wv[kCmpSumTT] = wave_fold<false>(__builtin_amdgcn_udot4(tw, tw, 0u, false));
-        wv[kCmpSumIT] = wave_fold<false>(__builtin_amdgcn_udot4(iw, tw, 0u, false));
+        wv[kCmpSumII] = wave_fold<false>(__builtin_amdgcn_udot4(is, is, 0u, false));
+        wv[kCmpSumTT] = wave_fold<false>(__builtin_amdgcn_udot4(ts, ts, 0u, false));
+        wv[kCmpSumIT] = wave_fold<false>(__builtin_amdgcn_udot4(is, ts, 0u, false));
     }
     if (DEV) {
         uint32_t dw = 0, dmax = 0, over = 0;   // over: bit u = pixel u deviates by more than the threshold
@@ -3026,7 +3039,9 @@ __global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
         for (int u = 0; u < 4; ++u) {
             const int i = (iw >> (8 * u)) & 255, t = (tw >> (8 * u)) & 255;
             const int l = LUT ? (int)lut[i] : i;
-            const uint32_t d = u < nu ? (uint32_t)(l > t ? l - t : t - l) : 0u;   // past the edge: nothing (L[0] may not be 0)
+            // past the edge, or ignored by the mask (its bytes past the edge are 0): nothing (L[0] may not be 0)
+            const bool in = MASK ? ((mw >> (8 * u)) & 1u) != 0 : u < nu;
+            const uint32_t d = in ? (uint32_t)(l > t ? l - t : t - l) : 0u;
             dw |= d << (8 * u);
             dmax = d > dmax ? d : dmax;
             over |= (uint32_t)((int)d > c.threshold) << u;
@@ -3072,9 +3087,20 @@ __global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
     }
 }
 
+// The kernels: the forms without a mask keep their names and template lists, the MASK forms stand beside them.
+template <bool SUMS, bool DEV, bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_patch_compare(const CompareArgs c) {
+    patch_compare_body<SUMS, DEV, LUT, IMG, false>(c);
+}
+template <bool SUMS, bool DEV, bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_patch_compare_masked(const CompareArgs c) {
+    patch_compare_body<SUMS, DEV, LUT, IMG, true>(c);
+}
+
 template <bool SUMS, bool DEV, bool LUT, bool IMG>
 static void launch_compare_form(const CompareArgs& c, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_patch_compare<SUMS, DEV, LUT, IMG>), dim3(grid), dim3(256), 0, st, c);
+    if (c.mask) hipLaunchKernelGGL((k_patch_compare_masked<SUMS, DEV, LUT, IMG>), dim3(grid), dim3(256), 0, st, c);
+    else hipLaunchKernelGGL((k_patch_compare<SUMS, DEV, LUT, IMG>), dim3(grid), dim3(256), 0, st, c);
 }
 
 bool launch_patch_compare(CompareArgs c, int form, hipStream_t st) {
@@ -3120,6 +3146,9 @@ bool launch_patch_warp(PatchArgs a, hipStream_t st) {
 // template; every other pixel, and every lane past the patch's right or bottom edge, runs through each barrier and
 // fold with Tx = Ty = r = 0: the value is masked, not only the store.
 //   LUT: L = the job's 256-byte table, staged in LDS (else L = identity)
+//   MASK: a pixel is used only if its own byte of the template mask is set as well (the mask plane has the template's
+//         pitch: tmpl_read4 on its row ty gives the lane's byte mask).  The four neighbours' bytes do not matter: the
+//         gradient is read from the template, which is complete.
 // Template reads: rows v - 1, v, v + 1 beneath the lane's 4 pixels as aligned dwords, funnel-shifted to bytes u .. u + 3
 // (rows above and below) and u - 1 .. u + 4 (the centre row: the dword before the group only where the group starts a
 // dword, and never before the row).  The row pitch is a multiple of 64 and at least tw + 4, so every dword lies inside
@@ -3141,88 +3170,17 @@ __device__ __forceinline__ uint32_t tmpl_read4(const uint8_t* row, int x, int pi
     return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)x);
 }
 
+// The body is text shared by the two kernels (fpm_patch_align.inc): the form without a mask keeps its name and template
+// list and is, for the compiler, the kernel it was.
 template <bool LUT>
 __global__ __launch_bounds__(256) void k_patch_align(const AlignArgs c) {
-    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
-    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
-    __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
-    __shared__ unsigned long long part[4][kAlignFields];
-    const PatchArgs& a = c.p;
-    const int tid = threadIdx.x;
-    if (LUT) {
-        // the job index as patch_tile_stage derives it; the helper's first barrier orders these writes before any read
-        const int job = xcd_remap(blockIdx.x, gridDim.x) / (a.tiles_x * a.tiles_y);
-        if (tid < 64) ((uint32_t*)lut)[tid] = ((const uint32_t*)(c.luts + (size_t)job * 256))[tid];
-    }
-    const PatchTile T = patch_tile_stage(a, tab, FT, tid);
-    const int r = tid >> 4, gx = (tid & 15) * 4;
-    const int x = T.x0 + gx, y = T.y0 + r;
-    const int left = a.pw - x;
-    const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
-    const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
-    const int tx = c.rx + x, ty = c.ry + y;
-    const bool row_used = nu > 0 && ty >= 1 && ty <= c.th - 2;   // rows ty - 1 and ty + 1 exist
-    uint32_t cw = 0, lw = 0, rw = 0, uw = 0, dw = 0;   // the template at u, u - 1, u + 1, and in the rows above and below
-    if (row_used) {
-        const uint8_t* trow = c.tmpl + (size_t)ty * c.tp;
-        const int c0 = tx & ~3, k = tx & 3;
-        const uint32_t lo = *(const uint32_t*)(trow + c0);
-        const uint32_t hi = c0 + 4 < c.tp ? *(const uint32_t*)(trow + c0 + 4) : 0u;
-        const uint32_t pv = k == 0 && c0 >= 4 ? *(const uint32_t*)(trow + c0 - 4) : 0u;
-        cw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)k);
-        lw = k == 0 ? __builtin_amdgcn_alignbyte(lo, pv, 3u) : __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k - 1));
-        rw = k == 3 ? hi : __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k + 1));
-        uw = tmpl_read4(trow - c.tp, tx, c.tp);
-        dw = tmpl_read4(trow + c.tp, tx, c.tp);
-    }
-    // the lane's local moments over its 4 pixels
-    const int lv = r & 3;
-    int n = 0, sxx = 0, sxy = 0, syy = 0, sxj = 0, syj = 0, sxr = 0, syr = 0, sjr = 0, srr = 0;
-    uint32_t sjj = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const bool used = row_used && u < nu && tx + u >= 1 && tx + u <= c.tw - 2;
-        const int i = (iw >> (8 * u)) & 255;
-        const int v = LUT ? (int)lut[i] : i;
-        const int gxv = used ? (int)((rw >> (8 * u)) & 255) - (int)((lw >> (8 * u)) & 255) : 0;
-        const int gyv = used ? (int)((dw >> (8 * u)) & 255) - (int)((uw >> (8 * u)) & 255) : 0;
-        const int rv = used ? v - (int)((cw >> (8 * u)) & 255) : 0;   // unused: nothing (L[0] may not be 0)
-        const int jl = (gx + u) * gyv - lv * gxv;
-        n += used ? 1 : 0;
-        sxx += gxv * gxv; sxy += gxv * gyv; syy += gyv * gyv;
-        sxj += gxv * jl; syj += gyv * jl; sjj += (uint32_t)(jl * jl);
-        sxr += gxv * rv; syr += gyv * rv; sjr += jl * rv; srr += rv * rv;
-    }
-    // wave totals in scalar registers (signed sums fold as their bit patterns: they fit 32 bits)
-    const int64_t Sxx = wave_fold<false>((uint32_t)sxx), Syy = wave_fold<false>((uint32_t)syy);
-    const int64_t Sxy = (int32_t)wave_fold<false>((uint32_t)sxy);
-    const int64_t SxJ = (int32_t)wave_fold<false>((uint32_t)sxj), SyJ = (int32_t)wave_fold<false>((uint32_t)syj);
-    const int64_t Sxr = (int32_t)wave_fold<false>((uint32_t)sxr), Syr = (int32_t)wave_fold<false>((uint32_t)syr);
-    const int64_t SJr = (int32_t)wave_fold<false>((uint32_t)sjr);
-    const int64_t Srr = wave_fold<false>((uint32_t)srr);
-    const uint32_t jlo = wave_fold<false>(sjj & 0xffffu);                          // <= 64 * 65535
-    const uint32_t jhn = wave_fold<false>((sjj >> 16) | ((uint32_t)n << 21));      // high halves < 2^21; n <= 256 above
-    const int64_t SJJ = ((int64_t)(jhn & 0x1fffffu) << 16) + jlo;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t Xb = 2 * T.x0 - (a.pw - 1), Yb = 2 * (T.y0 + 4 * wave) - (a.ph - 1);
-    int64_t f[kAlignFields];
-    f[kAlnN] = jhn >> 21;
-    f[kAlnHxx] = Sxx; f[kAlnHxy] = Sxy; f[kAlnHyy] = Syy;
-    f[kAlnHxt] = Xb * Sxy - Yb * Sxx + 2 * SxJ;
-    f[kAlnHyt] = Xb * Syy - Yb * Sxy + 2 * SyJ;
-    f[kAlnHtt] = Xb * Xb * Syy - 2 * Xb * Yb * Sxy + Yb * Yb * Sxx + 4 * Xb * SyJ - 4 * Yb * SxJ + 4 * SJJ;
-    f[kAlnGx] = Sxr; f[kAlnGy] = Syr;
-    f[kAlnGt] = Xb * Syr - Yb * Sxr + 2 * SJr;
-    f[kAlnSsd] = Srr;
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kAlignFields; ++k) part[wave][k] = (unsigned long long)f[k];
-    }
-    __syncthreads();
-    if (tid < kAlignFields) {
-        const unsigned long long s = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
-        if (s) atomicAdd((unsigned long long*)&c.acc[T.job].f[tid], s);
-    }
+    constexpr bool MASK = false;
+#include "fpm_patch_align.inc"
+}
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_patch_align_masked(const AlignArgs c) {
+    constexpr bool MASK = true;
+#include "fpm_patch_align.inc"
 }
 
 bool launch_patch_align(AlignArgs c, hipStream_t st) {
@@ -3234,8 +3192,59 @@ bool launch_patch_align(AlignArgs c, hipStream_t st) {
     const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
     if (grid > INT_MAX) return false;
     const dim3 g((unsigned)grid), blk(256);
-    if (c.luts) hipLaunchKernelGGL((k_patch_align<true>), g, blk, 0, st, c);
-    else hipLaunchKernelGGL((k_patch_align<false>), g, blk, 0, st, c);
+    if (c.mask) {
+        if (c.luts) hipLaunchKernelGGL((k_patch_align_masked<true>), g, blk, 0, st, c);
+        else hipLaunchKernelGGL((k_patch_align_masked<false>), g, blk, 0, st, c);
+    } else {
+        if (c.luts) hipLaunchKernelGGL((k_patch_align<true>), g, blk, 0, st, c);
+        else hipLaunchKernelGGL((k_patch_align<false>), g, blk, 0, st, c);
+    }
+    return true;
+}
+
+// ============================================================================================== template masks
+// k_mask_stage (fpm_mask_set / fpm_mask_set_device): a caller's u8 mask, any stride and any base
+// alignment, into the context's mask plane, normalised: 0xFF where the byte is not 0, else 0.  k_stage_gray's walk -- a
+// wave per row, a lane per 16 pixels and turn, the general span fetch (load_span: only dwords that hold a byte of the
+// image are read) -- with whole 16-byte stores: the plane's pitch is a multiple of 64, so a row's last, partial group is
+// stored whole with zeros behind the row's end (the rest of the padding is zero from the plane's clearing).  The count
+// of used pixels: bit counts per lane, one fold per wave at the end (every lane reaches it), one u64 integer atomic per
+// wave that counted any.
+__global__ __launch_bounds__(256) void k_mask_stage(const uint8_t* __restrict__ src, int w, int h, size_t stride,
+                                                    uint8_t* __restrict__ dst, int pitch,
+                                                    unsigned long long* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int nwaves = gridDim.x * 4;
+    uint32_t cnt = 0;
+    for (int y = blockIdx.x * 4 + (threadIdx.x >> 6); y < h; y += nwaves) {
+        const uint8_t* s = src + (size_t)y * stride;
+        uint8_t* r = dst + (size_t)y * pitch;
+        for (int x = lane << 4; x < w; x += 64 << 4) {
+            const int n = min(16, w - x);   // pixels of this group inside the row
+            uint32_t o[4];
+            load_span<16, false>(s + x, n, o);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                // bit 7 of every byte that is not 0, cut to the bytes inside the row, then spread over the byte
+                uint32_t t = (((o[k] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | o[k]) & 0x80808080u;
+                const int left = n - 4 * k;
+                if (left < 4) t &= left <= 0 ? 0u : (1u << (8 * left)) - 1u;
+                cnt += (uint32_t)__popc(t);
+                o[k] = (t >> 7) * 0xffu;
+            }
+            *(uint4*)(r + x) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+    }
+    const uint32_t total = wave_fold<false>(cnt);   // a lane counts at most 2^31 / 64 pixels: launch_mask_stage's cap
+    if (lane == 0 && total) atomicAdd(count, (unsigned long long)total);
+}
+
+bool launch_mask_stage(const uint8_t* src, int w, int h, size_t stride, uint8_t* dst, int pitch,
+                       unsigned long long* count, hipStream_t st) {
+    if (w <= 0 || h <= 0) return true;
+    if (((uintptr_t)dst & 15) || (pitch & 63) || pitch < w || (int64_t)w * h > ((int64_t)1 << 31)) return false;
+    const unsigned g = (unsigned)std::min(((int64_t)h + 3) / 4, (int64_t)2048);
+    hipLaunchKernelGGL(k_mask_stage, dim3(g), dim3(256), 0, st, src, w, h, stride, dst, pitch, count);
     return true;
 }
 
@@ -3459,6 +3468,8 @@ void launch_model_prepare(const ModelPrepareArgs& a, hipStream_t st) {
 // k_patch_compare's: DPP for the sum and the maximum, lane votes for the counts and the box, LDS across the four
 // waves, one integer atomic per non-zero field and workgroup into the zero-filled record.
 //   IMG: e is also stored as the excess image (PatchArgs::out, as k_patch_warp stores the patch)
+//   MASK: e = 0 where the template mask ignores the pixel; the mask is in template coordinates, the model's rectangle
+//         starts at (mx, my) in it, and its plane is read as lo and hi are (plane_read4, its own pitch)
 __device__ __forceinline__ uint32_t plane_read4(const uint8_t* row, int x, int pitch) {
     // 4 bytes from column x: an aligned dword pair funnel-shifted to the first byte; the second dword is read only
     // where it is inside the row
@@ -3468,8 +3479,8 @@ __device__ __forceinline__ uint32_t plane_read4(const uint8_t* row, int x, int p
     return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)x);
 }
 
-template <bool LUT, bool IMG>
-__global__ __launch_bounds__(256) void k_model_inspect(const InspectArgs c) {
+template <bool LUT, bool IMG, bool MASK>
+__device__ __forceinline__ void model_inspect_body(const InspectArgs c) {
     __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
     __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
     __shared__ __attribute__((aligned(16))) uint8_t lut[LUT ? 256 : 4];
@@ -3487,17 +3498,18 @@ __global__ __launch_bounds__(256) void k_model_inspect(const InspectArgs c) {
     const int left = a.pw - x;
     const int nu = y >= a.ph || left <= 0 ? 0 : (left < 4 ? left : 4);
     const uint32_t iw = patch_sample4(a, T, tab, FT, r, gx, nu);
-    uint32_t lw = 0, hw = 0;
+    uint32_t lw = 0, hw = 0, mw = 0;
     if (nu > 0) {
         lw = plane_read4(c.lo + (size_t)y * c.mp, x, c.mp);
         hw = plane_read4(c.hi + (size_t)y * c.mp, x, c.mp);
+        if (MASK) mw = plane_read4(c.mask + (size_t)(c.my + y) * c.mkp, c.mx + x, c.mkp);
     }
     uint32_t ew = 0, emax = 0, low = 0, high = 0;   // low / high: bit u = pixel u lies below / above its interval
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = (iw >> (8 * u)) & 255, lo = (lw >> (8 * u)) & 255, hi = (hw >> (8 * u)) & 255;
         const int v = LUT ? (int)lut[i] : i;
-        const bool in = u < nu, isl = in && v < lo, ish = in && !isl && v > hi;
+        const bool in = u < nu && (!MASK || ((mw >> (8 * u)) & 1u)), isl = in && v < lo, ish = in && !isl && v > hi;
         const uint32_t e = isl ? (uint32_t)(lo - v) : (ish ? (uint32_t)(v - hi) : 0u);
         ew |= e << (8 * u);
         emax = e > emax ? e : emax;
@@ -3548,6 +3560,15 @@ __global__ __launch_bounds__(256) void k_model_inspect(const InspectArgs c) {
     }
 }
 
+template <bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_model_inspect(const InspectArgs c) {
+    model_inspect_body<LUT, IMG, false>(c);
+}
+template <bool LUT, bool IMG>
+__global__ __launch_bounds__(256) void k_model_inspect_masked(const InspectArgs c) {
+    model_inspect_body<LUT, IMG, true>(c);
+}
+
 bool launch_model_inspect(InspectArgs c, hipStream_t st) {
     PatchArgs& a = c.p;
     if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
@@ -3557,7 +3578,15 @@ bool launch_model_inspect(InspectArgs c, hipStream_t st) {
     if (grid > INT_MAX) return false;
     const dim3 g((unsigned)grid), blk(256);
     const bool img = a.out != nullptr;
-    if (c.luts) {
+    if (c.mask) {
+        if (c.luts) {
+            if (img) hipLaunchKernelGGL((k_model_inspect_masked<true, true>), g, blk, 0, st, c);
+            else hipLaunchKernelGGL((k_model_inspect_masked<true, false>), g, blk, 0, st, c);
+        } else {
+            if (img) hipLaunchKernelGGL((k_model_inspect_masked<false, true>), g, blk, 0, st, c);
+            else hipLaunchKernelGGL((k_model_inspect_masked<false, false>), g, blk, 0, st, c);
+        }
+    } else if (c.luts) {
         if (img) hipLaunchKernelGGL((k_model_inspect<true, true>), g, blk, 0, st, c);
         else hipLaunchKernelGGL((k_model_inspect<true, false>), g, blk, 0, st, c);
     } else {

@@ -316,6 +316,15 @@ class LearnError(ValueError):
         self.code = int(code)
 
 
+class MaskError(ValueError):
+    """A template-mask call (set_mask, clear_mask, mask_enable, mask, mask_count) the library rejected; ``code`` is its
+    FPM_E_* status."""
+
+    def __init__(self, code: int, message: str):
+        super().__init__(message)
+        self.code = int(code)
+
+
 def learn_derive(n: int, total: int, total_sq: int):
     """fpm_learn_derive: ``(mean, norm, inv_area, equal1)`` of a template level from its pixel count and the exact sums of
     its pixels and of their squares, by the engine's own code (fpm_learn's f64 expressions in their order).  Host only
@@ -1370,9 +1379,82 @@ class TemplateMatcher:
     def model_learn(self):
         """Learns the model's mean image as the new template, on the device (fpm_model_learn): re-teach from many good
         parts instead of one.  State afterwards as after learn_at; the model survives with the rectangle (0, 0, w, h).
+        A template mask survives too, cropped to the model's rectangle -- the new template's frame -- so that it keeps
+        covering the same pixels, and keeps its enabled state (every other learn entry drops the mask).
         Raises LearnError when the call is rejected."""
         self._push()
         self._learn_done(self._lib.fpm_model_learn(self._ctx), "model_learn")
+
+    # -- template mask: compare, align, inspect and cut blobs on the part only (fpm_mask_*) --------------------------
+    def _mask_done(self, rc, what):
+        self._check(rc, what)
+        if rc != L.FPM_OK:
+            raise MaskError(rc, f"{what} failed with {rc}: {self.last_error()}")
+
+    def set_mask(self, mask, stream=None):
+        """Sets the template mask (fpm_mask_set / fpm_mask_set_device): ``mask`` of shape (th, tw), the learned
+        template's, bool or uint8, nonzero = use the pixel, 0 = ignore it (background, a date code, a hole).  A numpy
+        array, or a uint8 / bool torch tensor on this context's device, contiguous or a view with unit column stride
+        (``stream``: the stream it was written on, as match_device).  With a mask set last_compare / compare_at,
+        align_* and last_inspect / inspect_at / last_blobs / blobs_at run over the used pixels only, and the normalising
+        tables are fitted to them; the search, the patches, the calipers and the training planes do not look at it.  The
+        mask starts enabled and lives as long as the template (model_learn crops it).  Raises MaskError (a ValueError
+        with the status in ``code``) when the call is rejected; the previous mask then stays in force."""
+        if isinstance(mask, np.ndarray) or not hasattr(mask, "data_ptr"):
+            a = np.asarray(mask)
+            if a.dtype == np.bool_:
+                a = a.view(np.uint8)
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise TypeError(f"expected a 2-D bool or uint8 mask, got {a.dtype} with shape {a.shape}")
+            if a.size and (a.strides[1] != 1 or a.strides[0] < a.shape[1]):
+                a = np.ascontiguousarray(a)
+            rc = self._lib.fpm_mask_set(self._ctx, L.u8ptr(a), a.shape[1], a.shape[0], a.strides[0] if a.size else 0)
+            return self._mask_done(rc, "set_mask")
+        import torch
+
+        t = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        if t.dim() != 2:
+            raise TypeError(f"expected a 2-D mask, got shape {tuple(t.shape)}")
+        ptr, h, w, row, _, _ = self._device_image(t, "bgr", None)
+        rc = self._lib.fpm_mask_set_device(self._ctx, ptr, w, h, row, self._producer_stream(stream))
+        self._mask_done(rc, "set_mask")
+
+    def clear_mask(self):
+        """Drops the template mask (fpm_mask_clear)."""
+        self._mask_done(self._lib.fpm_mask_clear(self._ctx), "clear_mask")
+
+    def mask_enable(self, flag: bool = True):
+        """Switches a set mask on or off; a disabled mask stays resident and every tool behaves as without one."""
+        self._mask_done(self._lib.fpm_mask_enable(self._ctx, 1 if flag else 0), "mask_enable")
+
+    def mask_info(self):
+        """``(w, h, count, enabled)`` of the template mask: its size, its used pixels, whether it is enabled;
+        ``(0, 0, 0, False)`` without one (fpm_mask_info)."""
+        w, h, e, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        if self._lib.fpm_mask_info(self._ctx, C.byref(w), C.byref(h), C.byref(n), C.byref(e)) != L.FPM_OK:
+            raise ValueError("fpm_mask_info failed")
+        return w.value, h.value, n.value, bool(e.value)
+
+    def mask(self):
+        """The mask as stored, uint8 (th, tw) of 0 / 255, or None without one (fpm_mask_get)."""
+        w, h, _, _ = self.mask_info()
+        if w == 0:
+            return None
+        out = np.zeros((h, w), np.uint8)
+        self._mask_done(self._lib.fpm_mask_get(self._ctx, L.u8ptr(out), w), "mask")
+        return out
+
+    def mask_count(self, rect=None) -> int:
+        """Used pixels of the mask inside ``rect`` (x, y, w, h), None = the whole template (fpm_mask_count): the ``n``
+        of a masked last_compare over that rectangle."""
+        r = None
+        if rect is not None:
+            x, y, w, h = normalize_rect(rect)
+            r = L.PatchRect(x, y, w, h)
+        n = C.c_int64()
+        self._mask_done(self._lib.fpm_mask_count(self._ctx, C.byref(r) if r is not None else None, C.byref(n)),
+                        "mask_count")
+        return n.value
 
     def model_profile(self, which: int):
         """``(ms, launches, bytes)`` of L.MODEL_TRAIN / L.MODEL_PREPARE / L.MODEL_INSPECT, collected under profile(True)

@@ -745,6 +745,58 @@ int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int
  * FPM_K_* index: FPM_K_COUNT is unchanged).  bytes = L W source pixels per job + the records and profiles written. */
 int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
 
+/* --- template masks: compare, align, inspect and cut blobs on the part only (no reference equivalent) ---
+ * The tools above work on a rectangle in template coordinates; a part rarely fills its rectangle (background in the
+ * corners of a round part, a date code that changes, a hole).  A template mask says which template pixels count.
+ * What a mask is.  One per context: a u8 image of exactly the learned template's level-0 size, in template
+ * coordinates.  A byte != 0 means "use this pixel", a byte 0 "ignore it"; every non-zero value counts alike, and the
+ * mask is stored, and returned by fpm_mask_get, as 0 or 255.  A mask of all zeros is legal.  The mask is context state,
+ * like the variation model: no call takes a flag for it, and no flag value changes its meaning.
+ * State rules.  Every entry: FPM_E_INVALID_ARG while a search is in flight (fpm_mask_info excepted), FPM_E_NOT_LEARNED
+ * without a template.  fpm_mask_set / fpm_mask_set_device: FPM_E_INVALID_ARG for a size other than the template's, a
+ * stride below the width, a null pointer, or (device) memory the context's device cannot read -- the pointer, extent and
+ * stream rules are fpm_learn_device's for FPM_FMT_GRAY8: any base alignment, any stride, ordered after the work queued
+ * on producer_stream.  A set that fails leaves the previous mask in force; one that succeeds replaces it and starts
+ * ENABLED.  fpm_mask_enable(0) keeps the mask resident but makes every tool behave as without one; fpm_mask_enable,
+ * fpm_mask_get and fpm_mask_count without a mask are FPM_E_INVALID_ARG.  fpm_mask_info reports 0 x 0, count 0, enabled 0
+ * when there is none; count = the used pixels of the whole mask.  fpm_mask_count: the used pixels inside a comparison
+ * rectangle (NULL = the whole template; the rectangle rules are fpm_compare_at's), whether or not the mask is enabled.
+ * Lifetime: the model's.  Dropped by fpm_learn, fpm_learn_device, fpm_learn_at, fpm_learn_hit, fpm_clear_pattern and
+ * fpm_destroy; kept by staging, searching, fpm_model_clear and fpm_align_*.  fpm_model_learn CROPS it to the model's
+ * rectangle, as it re-frames the model: the new template is that rectangle, so the mask keeps covering the same pixels
+ * (and keeps its enabled state).
+ * Who honours it.  With a mask set and enabled the entries below do; with none, or a disabled one, every byte of every
+ * output is what it is without this block.  M(x, y) is the mask byte at template pixel (x, y).
+ *   fpm_last_compare / fpm_compare_at: pixel (u, v) of the rectangle (x, y, w, h) is USED iff M(x + u, y + v) != 0.  n,
+ *     the five sums, sum_abs, max_abs, n_over and the box run over the used pixels only; n = fpm_mask_count(rect); zncc,
+ *     gain, offset and the table come from those sums by fpm_compare_derive's rule; the difference image is 0 at ignored
+ *     pixels.  With n == 0 the call is FPM_OK: all sums 0, zncc = 0, gain = 1, offset = 0, the identity table, the empty
+ *     box (w, h, -1, -1).
+ *   fpm_align_sums_at / fpm_align_at / fpm_align_last: a pixel is used iff it is used by the interior rule above AND its
+ *     own mask byte is non-zero.  Its four neighbours' mask bytes do not matter: the gradient is read from the template,
+ *     which is complete.  n_used counts those pixels; fewer than 3 is FPM_ALIGN_SINGULAR as before.  The normalising
+ *     table is the masked comparison's.
+ *   fpm_last_inspect / fpm_inspect_at: e = 0 at ignored pixels; n is the used count inside the model's rectangle; the
+ *     counts, the maximum, the sum, the box and the excess image follow, and gain / offset are the masked comparison's.
+ *     fpm_last_blobs / fpm_blobs_at label that excess image: an ignored pixel is background.
+ *   fpm_model_train_last / fpm_model_train_at: the planes accumulate EVERY pixel of the rectangle, masked or not -- the
+ *     mask applies when inspecting, so it may be drawn or changed after training.  Only the FPM_COMPARE_NORMALIZE table
+ *     is built from the masked sums.
+ * Who does not: the search, fpm_last_patches* and fpm_patches_at, the calipers, the fpm_learn_* entries, fpm_model_sums
+ * and fpm_model_images, fpm_op_blobs and fpm_blobs_host.
+ * Launches.  Setting a mask runs k_mask_stage once (normalisation and the count, in integers).  A masked call launches
+ * the MASK forms of k_patch_compare, k_patch_align and k_model_inspect: as many launches as the unmasked call, counted
+ * under the same profile entries, the mask bytes read added to `bytes`.  Exact integers throughout: the results do not
+ * depend on any schedule.  Additive entries: FPM_ABI_VERSION and FPM_K_COUNT are unchanged. */
+int fpm_mask_set(fpm_ctx* ctx, const uint8_t* mask, int32_t width, int32_t height, size_t stride);
+int fpm_mask_set_device(fpm_ctx* ctx, const void* d_mask, int32_t width, int32_t height, size_t stride,
+                        void* producer_stream);
+int fpm_mask_clear(fpm_ctx* ctx);
+int fpm_mask_enable(fpm_ctx* ctx, int32_t enable);
+int fpm_mask_info(const fpm_ctx* ctx, int32_t* width, int32_t* height, int64_t* count, int32_t* enabled);
+int fpm_mask_get(fpm_ctx* ctx, uint8_t* out, size_t stride);
+int fpm_mask_count(fpm_ctx* ctx, const fpm_patch_rect* rect, int64_t* n);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent

@@ -74,6 +74,13 @@ CALIPER_TRUNCATED, CALIPER_OUTSIDE = 1, 2
 CALIPER_MAX_LENGTH, CALIPER_MAX_WIDTH, CALIPER_MAX_HALF = 1024, 256, 16
 CALIPER_MAX_CALS, CALIPER_MAX_CAP, CALIPER_MAX_SLOTS = 64, 64, 1 << 22
 CALIPER_KERNEL_SYMBOL = "k_caliper"
+# gray-value tools (fpm_hist_derive / fpm_last_histogram / fpm_last_segment ..): flags, the Otsu threshold value, the
+# caps, and fpm_gray_profile's `which`
+HIST_EMPTY, HIST_FLAT, GRAY_OUTSIDE = 1, 2, 4
+SEG_OTSU = -1
+GRAY_MAX_RECTS, GRAY_MAX_JOBS = 64, 65536
+GRAY_HIST, GRAY_THRESHOLD = 0, 1
+GRAY_KERNEL_SYMBOLS = ["k_patch_hist", "k_patch_threshold"]
 
 
 class Params(C.Structure):
@@ -191,6 +198,20 @@ class CaliperSummary(C.Structure):
 
     _fields_ = [(n, C.c_int32) for n in ("n_edges", "n_returned", "strongest", "flags")] + \
                [("lt_x", C.c_float), ("lt_y", C.c_float), ("angle", C.c_double)]
+
+
+class HistStats(C.Structure):
+    """fpm_hist_stats -- what fpm_hist_derive makes of one 256-bin histogram."""
+
+    _fields_ = [(n, C.c_int64) for n in ("n", "sum", "sum_sq")] + \
+               [(n, C.c_int32) for n in ("min", "max", "median", "otsu")] + \
+               [("mean", C.c_double), ("stddev", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SegmentInfo(C.Structure):
+    """fpm_segment_info -- one hit of fpm_last_segment / fpm_segment_at: used pixels, the threshold used, flags."""
+
+    _fields_ = [("n", C.c_int64), ("threshold", C.c_int32), ("flags", C.c_int32)]
 
 
 class RoiRecord(C.Structure):
@@ -353,6 +374,19 @@ SIGNATURES = {
                                 C.POINTER(C.c_int32)]),
     "fpm_mask_get": (C.c_int, [_P, _U8P, C.c_size_t]),
     "fpm_mask_count": (C.c_int, [_P, C.POINTER(PatchRect), C.POINTER(C.c_int64)]),
+    "fpm_hist_derive": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(HistStats)]),
+    "fpm_last_histogram": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int32,
+                                     C.POINTER(C.c_int32)]),
+    "fpm_histogram_at": (C.c_int, [_P, C.POINTER(PatchRect), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_uint32)]),
+    "fpm_last_segment": (C.c_int, [_P, C.c_int32, C.POINTER(PatchRect), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(SegmentInfo), C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_int32), _U8P, C.c_size_t, C.c_size_t]),
+    "fpm_segment_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32,
+                                 C.POINTER(PatchRect), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SegmentInfo),
+                                 C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, _U8P, C.c_size_t, C.c_size_t]),
+    "fpm_gray_set_run": (C.c_int, [_P, C.c_int32]),
+    "fpm_gray_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

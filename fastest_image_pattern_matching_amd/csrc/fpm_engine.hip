@@ -153,10 +153,11 @@ struct KProf {
     int64_t launches = 0, bytes = 0;
 };
 // Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
-// alignment's one (fpm_align_profile), the blob labelling's five (fpm_blobs_profile) and the calipers' one
-// (fpm_caliper_profile), which have no FPM_K_* index: FPM_K_COUNT stays what it is.
+// alignment's one (fpm_align_profile), the blob labelling's five (fpm_blobs_profile), the calipers' one
+// (fpm_caliper_profile) and the gray-value tools' two (fpm_gray_profile), which have no FPM_K_* index: FPM_K_COUNT stays
+// what it is.
 enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfBlobTile, kProfBlobMerge,
-       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfSlots };
+       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfGrayHist, kProfGrayThreshold, kProfSlots };
 
 }  // namespace
 
@@ -250,6 +251,10 @@ struct fpm_ctx {
     // edge calipers (fpm_last_calipers / fpm_calipers_at): the raw records, counts and profiles of a call and their host copy
     DevBuf d_calout;
     PinBuf h_calout;
+    // gray-value tools (fpm_last_histogram / fpm_last_segment ..): the histograms of a call and their host copy
+    int gray_run = 0;         // fpm_gray_set_run: tiles per workgroup of k_patch_hist, 0 = the engine's choice
+    DevBuf d_gray;
+    PinBuf h_gray;
     // template mask (fpm_mask_*): one u8 plane of the template's level-0 size and row pitch, 0x00 /
     // 0xFF, zero behind a row's end; mask_host = its dense host copy (the counts, fpm_mask_get).  d_mask_in = the
     // staging buffer (a host mask's upload, the plane being staged, the count); a set that fails leaves d_mask alone.
@@ -3190,6 +3195,224 @@ int calipers_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fp
     return FPM_OK;
 }
 
+// ---- gray-value tools (fpm_last_histogram, fpm_histogram_at, fpm_last_segment, fpm_segment_at) ----
+static_assert(sizeof(fpm_hist_stats) == 64 && sizeof(fpm_segment_info) == 16, "the gray-value structs have no padding");
+static_assert(sizeof(GrayJob) % 8 == 0, "a table of GrayJob keeps its doubles aligned");
+
+// Tiles per workgroup of k_patch_hist for `tiles` tiles in all: k_model_accum's rule turned round -- as many tiles as
+// bring the grid down to kGrayWgPerCu workgroups per compute unit, so that a workgroup's 256 global adds are shared by a
+// run of tiles; fpm_gray_set_run overrides it.  k_model_accum's own 12 per compute unit was measured too (DESIGN.md
+// section 23): a compute unit holds 8 of these workgroups at once, so 12 is one full round and a half-empty one, and the
+// launch was 15 % slower than at 74.
+constexpr int kGrayWgPerCu = 64;
+int gray_run_for(fpm_ctx* ctx, int64_t tiles) {
+    if (ctx->gray_run > 0) return ctx->gray_run;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) cus = 256;
+    const int64_t want = (int64_t)kGrayWgPerCu * cus;
+    return (int)std::min<int64_t>(std::max<int64_t>(1, (tiles + want - 1) / want), 1 << 20);
+}
+
+// the rectangles of a histogram call, each under the comparison rectangle's rules
+int gray_rects(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, std::vector<fpm_patch_rect>& out) {
+    if (n_rects < 1 || n_rects > FPM_GRAY_MAX_RECTS || (!rects && n_rects != 1)) {
+        ctx->err = "1 .. 64 rectangles expected (NULL with one: the whole template)";
+        return FPM_E_INVALID_ARG;
+    }
+    out.resize((size_t)n_rects);
+    for (int k = 0; k < n_rects; ++k) {
+        const int rc = compare_rect(ctx, rects ? rects + k : nullptr, &out[(size_t)k]);
+        if (rc != FPM_OK) return rc;
+    }
+    return FPM_OK;
+}
+
+struct GrayCall {
+    int njobs = 0, run = 1, grid = 0;
+    size_t tab = 0;          // bytes of the job table
+    int64_t px = 0;          // pixels of all jobs
+};
+
+// The GrayJob table of poses x rects ([pose][rect]) in the pinned patch table, every pose checked; nothing is sent.
+// Job j's histogram is words 256 j .., its e image (one rectangle) patch_stride bytes behind the one before.  outside
+// (optional, [njobs]): FPM_GRAY_OUTSIDE or 0 by the calipers' four-corner rule.
+int gray_jobs(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const std::vector<PatchPose>& poses,
+              size_t patch_stride, int t, int polarity, GrayCall* g, std::vector<int32_t>* outside) {
+    const int K = (int)rects.size();
+    g->njobs = (int)poses.size() * K;
+    g->tab = round_up(sizeof(GrayJob) * (size_t)g->njobs, (size_t)256);
+    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
+    HIP_TRY(ctx->h_patchtab.ensure(g->tab));
+    HIP_TRY(ctx->d_patchtab.ensure(g->tab));
+    int64_t tiles = 0;
+    g->px = 0;
+    for (const fpm_patch_rect& r : rects) {
+        tiles += (int64_t)poses.size() * ((r.w + 63) / 64) * ((r.h + 15) / 16);
+        g->px += (int64_t)poses.size() * r.w * r.h;
+    }
+    g->run = gray_run_for(ctx, tiles);
+    if (outside) outside->assign((size_t)g->njobs, 0);
+    GrayJob* jobs = ctx->h_patchtab.as<GrayJob>();
+    int64_t wg = 0;
+    for (int i = 0, j = 0; i < (int)poses.size(); ++i)
+        for (int k = 0; k < K; ++k, ++j) {
+            const fpm_patch_rect& r = rects[(size_t)k];
+            GrayJob& job = jobs[j];
+            const int rc = patch_pose_matrix(ctx, r, poses[(size_t)i], i, nullptr, job.p.M);
+            if (rc != FPM_OK) return rc;
+            job.p.out_off = (int64_t)((size_t)j * patch_stride);
+            job.p.src = poses[(size_t)i].src;
+            job.p.pad = 0;
+            job.pw = r.w; job.ph = r.h; job.rx = r.x; job.ry = r.y;
+            job.hist_off = (int64_t)j * 256;
+            job.wg0 = (int32_t)wg;
+            job.t = t; job.polarity = polarity; job.pad = 0;
+            const int64_t jt = (int64_t)((r.w + 63) / 64) * ((r.h + 15) / 16);
+            wg += (jt + g->run - 1) / g->run;
+            if (wg > INT_MAX) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
+            if (outside) {   // border zeros in the region: a corner sample outside the source, through the sampler's matrix
+                bool o = false;
+                for (int e = 0; e < 4; ++e) {
+                    const double x = (e & 1) ? r.w - 1 : 0, y = (e & 2) ? r.h - 1 : 0;
+                    const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
+                    o = o || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
+                }
+                (*outside)[(size_t)j] = o ? FPM_GRAY_OUTSIDE : 0;
+            }
+        }
+    g->grid = (int)wg;
+    return FPM_OK;
+}
+
+// the pinned job table to the device, on the stream (no wait)
+int gray_send_jobs(fpm_ctx* ctx, const GrayCall& g) {
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, g.tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    return FPM_OK;
+}
+
+GrayArgs gray_args(fpm_ctx* ctx, const GrayCall& g) {
+    const SrcLevel& l0 = ctx->src[0];
+    GrayArgs a{};
+    a.jobs = ctx->d_patchtab.as<GrayJob>();
+    a.njobs = g.njobs;
+    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    a.img_stride = l0.img_bytes;
+    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    a.mask = mask_plane(ctx);
+    a.mkp = ctx->tmpl[0].pitch;
+    a.run = g.run;
+    a.grid = g.grid;
+    return a;
+}
+
+// The histograms of a staged job table into h_gray: d_gray cleared on the stream, one launch of k_patch_hist, the words
+// to pinned memory, the stream synchronised, then every histogram checked against its job's used count (used: one per
+// rectangle).  d_gray and h_gray are sized by the caller.
+int gray_hist_run(fpm_ctx* ctx, const GrayCall& g, const std::vector<int64_t>& used) {
+    const size_t hb = sizeof(uint32_t) * 256 * (size_t)g.njobs;
+    HIP_TRY(hipMemsetAsync(ctx->d_gray.p, 0, hb, ctx->stream));
+    GrayArgs a = gray_args(ctx, g);
+    a.hist = ctx->d_gray.as<uint32_t>();
+    {
+        // bytes: source pixels read (+ mask bytes read) + the histogram words
+        ProfScope ps(ctx, kProfGrayHist, (1 + (a.mask ? 1 : 0)) * g.px + (int64_t)hb);
+        if (!launch_patch_hist(a, ctx->stream)) { ctx->err = "bad histogram launch"; return FPM_E_INTERNAL; }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_gray.p, ctx->d_gray.p, hb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const uint32_t* h = ctx->h_gray.as<uint32_t>();
+    const size_t K = used.size();
+    for (int j = 0; j < g.njobs; ++j) {   // what the device wrote is checked before anything of it reaches the caller
+        int64_t s = 0;
+        for (int b = 0; b < 256; ++b) s += (int64_t)h[(size_t)j * 256 + b];
+        if (s != used[(size_t)j % K]) { ctx->err = "k_patch_hist returned a histogram that misses its pixel count"; return FPM_E_INTERNAL; }
+    }
+    return FPM_OK;
+}
+
+// The histograms of poses x rects (both non-empty), every argument checked before the one launch; caller memory is
+// written only after the device pass has succeeded.
+int gray_to_host(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const std::vector<PatchPose>& poses, uint32_t* hist) {
+    GrayCall g;
+    int rc = gray_jobs(ctx, rects, poses, 0, 0, 0, &g, nullptr);
+    if (rc != FPM_OK) return rc;
+    const size_t hb = sizeof(uint32_t) * 256 * (size_t)g.njobs;
+    HIP_TRY(ctx->d_gray.ensure(hb));
+    HIP_TRY(ctx->h_gray.ensure(hb));
+    std::vector<int64_t> used(rects.size());
+    for (size_t k = 0; k < rects.size(); ++k) used[k] = mask_used(ctx, rects[k]);
+    rc = gray_send_jobs(ctx, g);
+    if (rc == FPM_OK) rc = gray_hist_run(ctx, g, used);
+    if (rc != FPM_OK) return rc;
+    std::memcpy(hist, ctx->h_gray.p, hb);
+    return FPM_OK;
+}
+
+// The segmentation of `poses` (n >= 1) inside r: with a fixed threshold one launch of k_patch_threshold into the pitched
+// patch buffer and the labelling of those images; under FPM_SEG_OTSU the histogram launch, one copy to the host,
+// hist_derive per hit and the thresholds into the job table come first.  blobs_reserve comes before the first launch.
+int segment_of_poses(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<PatchPose>& poses, int threshold, int polarity,
+                     int connectivity, int min_area, int cap_per_hit, fpm_segment_info* info, fpm_blob_summary* summary,
+                     fpm_blob* out, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    const int n = (int)poses.size();
+    const bool otsu = threshold == FPM_SEG_OTSU;
+    BlobRun b;
+    int rc = blobs_reserve(ctx, n, r.w, r.h, min_area, cap_per_hit, false, &b);
+    if (rc != FPM_OK) return rc;
+    const size_t pitch = round_up((size_t)r.w, (size_t)64), pbytes = pitch * (size_t)r.h;
+    HIP_TRY(ctx->d_patch.ensure(pbytes * (size_t)n));
+    if (otsu) {
+        HIP_TRY(ctx->d_gray.ensure(sizeof(uint32_t) * 256 * (size_t)n));
+        HIP_TRY(ctx->h_gray.ensure(sizeof(uint32_t) * 256 * (size_t)n));
+    }
+    GrayCall g;
+    std::vector<int32_t> flags;
+    rc = gray_jobs(ctx, {r}, poses, pbytes, otsu ? 0 : threshold, polarity, &g, &flags);
+    if (rc == FPM_OK) rc = gray_send_jobs(ctx, g);
+    if (rc != FPM_OK) return rc;
+    const int64_t used = mask_used(ctx, r);
+    std::vector<int32_t> ts((size_t)n, threshold);
+    if (otsu) {
+        rc = gray_hist_run(ctx, g, {used});
+        if (rc != FPM_OK) return rc;
+        // the stream is idle: the table has left the pinned buffer, which takes the thresholds and goes again
+        GrayJob* jobs = ctx->h_patchtab.as<GrayJob>();
+        for (int i = 0; i < n; ++i) {
+            fpm_hist_stats s;
+            if (!hist_derive(ctx->h_gray.as<uint32_t>() + (size_t)i * 256, &s)) { ctx->err = "histogram beyond 2^22 pixels"; return FPM_E_INTERNAL; }
+            ts[(size_t)i] = polarity > 0 ? s.otsu : s.otsu + 1;
+            flags[(size_t)i] |= s.flags;
+            jobs[i].t = ts[(size_t)i];
+            jobs[i].polarity = s.flags ? 0 : polarity;   // empty or flat: no foreground
+        }
+        rc = gray_send_jobs(ctx, g);
+        if (rc != FPM_OK) return rc;
+    }
+    GrayArgs a = gray_args(ctx, g);
+    a.out = ctx->d_patch.as<uint8_t>();
+    a.row_stride = pitch;
+    a.pw = r.w; a.ph = r.h;
+    a.dword = 1;   // the buffer's base, the pitch and every image offset are multiples of 64
+    {
+        // bytes: source pixels read (+ mask bytes read) + e pixels written
+        ProfScope ps(ctx, kProfGrayThreshold, (2 + (a.mask ? 1 : 0)) * g.px);
+        if (!launch_patch_threshold(a, ctx->stream)) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
+    }
+    HIP_TRY(hipGetLastError());
+    if (img) {
+        rc = copy_patches_out(ctx, r, (size_t)n, a.out, pitch, pbytes, img, row_stride, patch_stride);
+        if (rc != FPM_OK) return rc;
+    }
+    rc = blobs_run(ctx, b, a.out, pitch, pbytes, 0, connectivity, min_area, cap_per_hit, summary, out, nullptr);
+    if (rc != FPM_OK) return rc;
+    for (int i = 0; i < n; ++i) info[i] = fpm_segment_info{used, ts[(size_t)i], flags[(size_t)i]};
+    return FPM_OK;
+}
+
 // fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
 // the device learn's second half
 int learn_from_model(fpm_ctx* ctx) {
@@ -3281,6 +3504,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_blobplanes.release(); ctx->d_blobrec.release(); ctx->d_blobimg.release();
     ctx->h_blobrec.release(); ctx->h_bloblab.release();
     ctx->d_calout.release(); ctx->h_calout.release();
+    ctx->d_gray.release(); ctx->h_gray.release();
     ctx->d_mask.release(); ctx->d_mask_in.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
@@ -4230,6 +4454,116 @@ int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int
 int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
     if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
     const KProf& p = ctx->kp[kProfCaliper];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
+}
+
+// --- gray-value tools (fpm_hist_derive: fpm_host.cpp) ------------------------------------------
+int fpm_histogram_at(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, const int32_t* src_index, const float* lt,
+                     const double* angles, int32_t n_poses, uint32_t* hist) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    std::vector<fpm_patch_rect> rs;
+    int rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = gray_rects(ctx, rects, n_rects, rs);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!hist) { ctx->err = "null histogram buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)n_poses * n_rects > FPM_GRAY_MAX_JOBS) { ctx->err = "hits x rectangles above 65536"; return FPM_E_INVALID_ARG; }
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return gray_to_host(ctx, rs, poses, hist);
+}
+
+int fpm_last_histogram(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, int32_t source, uint32_t* hist,
+                       int32_t cap, int32_t* n) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    std::vector<fpm_patch_rect> rs;
+    std::vector<PatchPose> poses;
+    int rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = gray_rects(ctx, rects, n_rects, rs);
+    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
+    if (rc != FPM_OK) return rc;
+    *n = (int32_t)poses.size();
+    if ((int)poses.size() > cap) { ctx->err = "histogram buffer too small"; return FPM_E_CAPACITY; }
+    if (poses.empty()) return FPM_OK;
+    if (!hist) { ctx->err = "null histogram buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)poses.size() * n_rects > FPM_GRAY_MAX_JOBS) { ctx->err = "hits x rectangles above 65536"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    return gray_to_host(ctx, rs, poses, hist);
+}
+
+static int segment_args(fpm_ctx* ctx, int32_t threshold, int32_t polarity) {
+    if (threshold < FPM_SEG_OTSU || threshold > 255) { ctx->err = "threshold must be 0 .. 255 or FPM_SEG_OTSU"; return FPM_E_INVALID_ARG; }
+    if (polarity != 1 && polarity != -1) { ctx->err = "polarity must be +1 or -1"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+static int segment_outputs(fpm_ctx* ctx, int64_t hits, const fpm_patch_rect& r, int32_t connectivity, int32_t min_area,
+                           int32_t cap_per_hit, const fpm_segment_info* info, const fpm_blob_summary* summary,
+                           const fpm_blob* out, const uint8_t* img, size_t row_stride, size_t patch_stride) {
+    int rc = blob_args(ctx, hits, 0, connectivity, min_area, cap_per_hit, summary, out);
+    if (rc != FPM_OK) return rc;
+    if (!info) { ctx->err = "null segment info buffer"; return FPM_E_INVALID_ARG; }
+    if (img) return check_patch_out(ctx, img, r, row_stride, patch_stride);
+    return FPM_OK;
+}
+
+int fpm_last_segment(fpm_ctx* ctx, int32_t source, const fpm_patch_rect* rect, int32_t threshold, int32_t polarity,
+                     int32_t connectivity, int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary,
+                     fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n, uint8_t* img, size_t row_stride,
+                     size_t patch_stride) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int rc = segment_args(ctx, threshold, polarity);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    rc = last_patches_begin(ctx, rect, source, cap, n, &r, poses, true);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    rc = segment_outputs(ctx, (int64_t)poses.size(), r, connectivity, min_area, cap_per_hit, info, summary, out, img,
+                         row_stride, patch_stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return segment_of_poses(ctx, r, poses, threshold, polarity, connectivity, min_area, cap_per_hit, info, summary, out,
+                            img, row_stride, patch_stride);
+}
+
+int fpm_segment_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                   const fpm_patch_rect* rect, int32_t threshold, int32_t polarity, int32_t connectivity,
+                   int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary, fpm_blob* out,
+                   int32_t cap_per_hit, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int rc = segment_args(ctx, threshold, polarity);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    rc = segment_outputs(ctx, n_poses, r, connectivity, min_area, cap_per_hit, info, summary, out, img, row_stride,
+                         patch_stride);
+    if (rc != FPM_OK) return rc;
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return segment_of_poses(ctx, r, poses, threshold, polarity, connectivity, min_area, cap_per_hit, info, summary, out,
+                            img, row_stride, patch_stride);
+}
+
+int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (tiles < 0) { ctx->err = "tiles per workgroup must be >= 0"; return FPM_E_INVALID_ARG; }
+    ctx->gray_run = tiles;
+    return FPM_OK;
+}
+
+int fpm_gray_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || which < 0 || which > 1 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfGrayHist + which];
     *ms = p.ms;
     *launches = p.launches;
     *bytes = p.bytes;

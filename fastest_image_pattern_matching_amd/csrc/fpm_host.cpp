@@ -708,7 +708,63 @@ int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n) {
     return best;
 }
 
+// ---- gray-value tools (include/fpm.h, "gray-value tools"): integers first, then f64 in the header's order; the file is
+// built with -ffp-contract=off, so B's two products and its quotient are three roundings.
+bool hist_derive(const uint32_t hist[256], fpm_hist_stats* out) {
+    int64_t n = 0, sum = 0, sum_sq = 0;
+    for (int b = 0; b < 256; ++b) n += (int64_t)hist[b];   // at most 256 * (2^32 - 1)
+    if (n > ((int64_t)1 << 22)) return false;
+    fpm_hist_stats s{};
+    if (n == 0) {
+        s.flags = FPM_HIST_EMPTY;
+        *out = s;
+        return true;
+    }
+    int32_t mn = -1, mx = -1;
+    for (int b = 0; b < 256; ++b) {
+        const int64_t h = (int64_t)hist[b];
+        if (h == 0) continue;
+        if (mn < 0) mn = b;
+        mx = b;
+        sum += h * b;
+        sum_sq += h * b * b;
+    }
+    s.n = n; s.sum = sum; s.sum_sq = sum_sq;
+    s.min = mn; s.max = mx;
+    int64_t cum = 0;
+    for (int v = 0; v < 256; ++v) {
+        cum += (int64_t)hist[v];
+        if (2 * cum >= n) { s.median = v; break; }
+    }
+    s.mean = (double)sum / (double)n;
+    s.stddev = std::sqrt((double)(n * sum_sq - sum * sum)) / (double)n;
+    if (mn == mx) {
+        s.otsu = mn;
+        s.flags = FPM_HIST_FLAT;
+    } else {
+        int64_t n0 = 0, s0 = 0;
+        double best = -1.0;   // B >= 0 for every admissible t, and there is one: the first replaces this
+        for (int t = 0; t < 255; ++t) {
+            n0 += (int64_t)hist[t];
+            s0 += (int64_t)hist[t] * t;
+            if (n0 <= 0 || n0 >= n) continue;
+            const int64_t N = n * s0 - n0 * sum;
+            const double NN = (double)N * (double)N;
+            const double dd = (double)n0 * (double)(n - n0);
+            const double B = NN / dd;
+            if (B > best) { best = B; s.otsu = t; }
+        }
+    }
+    *out = s;
+    return true;
+}
+
 }  // namespace fpm
+
+int fpm_hist_derive(const uint32_t hist[256], fpm_hist_stats* out) {
+    if (!hist || !out || !fpm::hist_derive(hist, out)) return FPM_E_INVALID_ARG;
+    return FPM_OK;
+}
 
 int fpm_caliper_pose(float lt_x, float lt_y, double angle, const fpm_caliper* cal, float* ltk_x, float* ltk_y,
                      double* angle_k) {

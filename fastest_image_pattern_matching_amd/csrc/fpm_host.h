@@ -77,5 +77,9 @@ int32_t caliper_edges(const int32_t* profile, const fpm_caliper& k, int32_t cap,
 bool caliper_derive(const fpm_caliper& k, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw& r, fpm_edge* e);
 // the returned record with the largest |d|, the earliest on ties; -1 for n = 0
 int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n);
+// ---- gray-value tools (include/fpm.h, "gray-value tools") ----
+// the statistics and Otsu's threshold of one histogram by the header's rule; false (nothing written) when its total
+// exceeds 2^22
+bool hist_derive(const uint32_t hist[256], fpm_hist_stats* out);
 
 }  // namespace fpm

@@ -356,6 +356,41 @@ struct CaliperArgs {
 };
 // k_caliper: one workgroup per job.  Returns false, launching nothing, for a capacity outside its range.
 bool launch_caliper(const CaliperArgs& a, hipStream_t st);
+// ---- gray-value tools (fpm_last_histogram / fpm_histogram_at / fpm_last_segment / fpm_segment_at, DESIGN.md section
+// 23): the 256-bin histogram of a (hit, rectangle) patch that is never written, and the patch thresholded into the u8
+// image e that the labelling kernels take.  One descriptor per job serves both kernels, built on the host.
+struct GrayJob {
+    PatchJob p;              // the inverted matrix and the source, as for k_patch_warp; out_off = byte offset of the job's
+                             // e image from GrayArgs::out (k_patch_threshold)
+    int32_t pw, ph;          // the rectangle's size
+    int32_t rx, ry;          // and its origin in the template, where the mask lives
+    int64_t hist_off;        // the job's first histogram word (in words) from GrayArgs::hist
+    int32_t wg0;             // k_patch_hist: the job's first workgroup; ascending over the table, jobs[0].wg0 = 0
+    int32_t t;               // k_patch_threshold: the threshold 0 .. 255
+    int32_t polarity;        // +1: e = I - t where I > t; -1: e = t - I where I < t; 0: e = 0 (no foreground)
+    int32_t pad;
+};
+struct GrayArgs {
+    const GrayJob* jobs;
+    int32_t njobs;
+    const uint8_t* level0;   // as PatchArgs
+    size_t img_stride;
+    int32_t sw, sh, sp;
+    const uint8_t* mask;     // the template mask plane (0x00 / 0xFF, row pitch mkp, a multiple of 64) or null: the MASK forms
+    int32_t mkp;
+    uint32_t* hist;          // k_patch_hist: [..][256], zero-filled before the launch
+    int32_t run;             // k_patch_hist: consecutive tiles of one job per workgroup, >= 1
+    int32_t grid;            // k_patch_hist: workgroups = the sum over the jobs of ceil(tiles / run)
+    uint8_t* out;            // k_patch_threshold: the e images, rows row_stride apart, all of pw x ph
+    size_t row_stride;
+    int32_t pw, ph;
+    int32_t dword;           // as PatchArgs
+    int32_t tiles_x, tiles_y;   // set by launch_patch_threshold
+};
+// k_patch_hist: one workgroup per run of tiles of one job.  Returns false, launching nothing, for a run or grid below 1.
+bool launch_patch_hist(const GrayArgs& a, hipStream_t st);
+// k_patch_threshold: k_patch_warp's grid over jobs of one size.  Returns false for a grid past 2^31 - 1.
+bool launch_patch_threshold(GrayArgs a, hipStream_t st);
 // ---- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): connected
 // components of n pitched u8 images of one size, by a union-find per 64 x 16 tile in LDS and a merge of the tile pieces
 // in device memory.  A label is the row-major index v * w + u, within its image, of a pixel of the same component that is

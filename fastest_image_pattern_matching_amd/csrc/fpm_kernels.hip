@@ -3359,6 +3359,173 @@ bool launch_caliper(const CaliperArgs& a, hipStream_t st) {
     return true;
 }
 
+// ============================================================================================== gray-value tools
+// k_patch_hist (fpm_last_histogram / fpm_histogram_at and the Otsu half of fpm_last_segment / fpm_segment_at, DESIGN.md
+// section 23): the 256-bin histogram of every (hit, rectangle) job's patch, none of them written.  A job has its own
+// size; it is sampled in k_patch_warp's 64 x 16 tiles with the patch family's staging and sampler (patch_tile_stage_at
+// / patch_sample4 through a local PatchArgs, as k_caliper), so the bytes are k_patch_warp's by construction.  A
+// workgroup walks `run` consecutive tiles (row-major) of ONE job and counts them into four private histograms in LDS,
+// one per wave (4 x 256 x u32, LDS atomic adds: 32-bit throughout, no narrower counter anywhere); at the end lane b adds
+// the four copies of bin b and issues one global u32 atomic add where the total is not 0 -- at most 256 per run, not
+// per tile.  The workgroup finds its job by bisection over GrayJob::wg0 (scalar loads: blockIdx is uniform).
+// What enters a bin: byte u of the lane's word iff u < nu (patch_sample4's bytes from nu on are 0 and are no pixels)
+// and, MASK, iff its mask byte is not 0 -- `vm` below has one bit per such byte.  Contention: equal bytes of a lane's
+// four go in one add; and when every lane of a wave holds the same word and the same vm (a flat region) one lane adds
+// for all 64.  Lanes past the patch's right or bottom edge take part in every barrier with vm = 0.  The loop bounds come
+// from the job and blockIdx: every barrier is workgroup-uniform.
+__device__ __forceinline__ uint32_t gray_mask4(const uint8_t* mask, int pitch, int tx, int ty, int nu) {
+    // the dword pair of k_patch_compare's template read: the plane's pitch is a multiple of 64 and (tx, ty) lies inside
+    // the template, so the first dword is inside the row and the second is read only where it is too
+    const uint8_t* mrow = mask + (size_t)ty * pitch;
+    const int c0 = tx & ~3;
+    const uint32_t lo = *(const uint32_t*)(mrow + c0);
+    const uint32_t hi = (tx & 3) && c0 + 4 < pitch ? *(const uint32_t*)(mrow + c0 + 4) : 0u;
+    uint32_t mw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)tx);
+    if (nu < 4) mw &= (1u << (8 * nu)) - 1u;
+    return mw;
+}
+
+// `mul` times the bytes of w that vm names into the bins at h, equal bytes in one add
+__device__ __forceinline__ void hist_add4(uint32_t* h, uint32_t w, uint32_t vm, uint32_t mul) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (!((vm >> u) & 1u)) continue;
+        const uint32_t b = (w >> (8 * u)) & 255u;
+        uint32_t cnt = 1;
+#pragma unroll
+        for (int v = u + 1; v < 4; ++v)
+            if (((vm >> v) & 1u) && ((w >> (8 * v)) & 255u) == b) {
+                ++cnt;
+                vm &= ~(1u << v);
+            }
+        atomicAdd(h + b, cnt * mul);
+    }
+}
+
+template <bool MASK>
+__device__ __forceinline__ void patch_hist_body(const GrayArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    __shared__ uint32_t H[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    int lo = 0, hi = c.njobs - 1;
+    while (lo < hi) {   // the last job with wg0 <= blockIdx.x
+        const int mid = (lo + hi + 1) >> 1;
+        if (c.jobs[mid].wg0 <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const GrayJob& J = c.jobs[lo];
+    const int pw = __builtin_amdgcn_readfirstlane(J.pw), ph = __builtin_amdgcn_readfirstlane(J.ph);
+    const int rx = __builtin_amdgcn_readfirstlane(J.rx), ry = __builtin_amdgcn_readfirstlane(J.ry);
+    PatchArgs a{};
+    a.jobs = &J.p;
+    a.njobs = 1;
+    a.level0 = c.level0;
+    a.img_stride = c.img_stride;
+    a.sw = c.sw; a.sh = c.sh; a.sp = c.sp;
+    a.pw = pw; a.ph = ph;
+    const int ntx = (pw + kPatchTw - 1) / kPatchTw, nty = (ph + kPatchTh - 1) / kPatchTh;
+    const int t0 = ((int)blockIdx.x - __builtin_amdgcn_readfirstlane(J.wg0)) * c.run;
+    const int t1 = t0 + c.run < ntx * nty ? t0 + c.run : ntx * nty;
+    // lane b clears the words it sums at the end; the first barrier of patch_tile_stage_at orders them before any add
+#pragma unroll
+    for (int k = 0; k < 4; ++k) H[k][tid] = 0;
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        const int ty = t / ntx, tx = t - ty * ntx;
+        const int x = tx * kPatchTw + gx, y = ty * kPatchTh + r;
+        const int left = pw - x;
+        const int nu = y >= ph || left <= 0 ? 0 : (left < 4 ? left : 4);
+        const PatchTile T = patch_tile_stage_at(a, tab, FT, tid, 0, tx, ty);
+        const uint32_t w = patch_sample4(a, T, tab, FT, r, gx, nu);
+        uint32_t vm = (1u << nu) - 1u;
+        if (MASK && nu > 0) {
+            const uint32_t mw = gray_mask4(c.mask, c.mkp, rx + x, ry + y, nu);
+            vm = (mw & 1u) | ((mw >> 7) & 2u) | ((mw >> 14) & 4u) | ((mw >> 21) & 8u);
+        }
+        const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
+        const uint32_t vm0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)vm);
+        if (__ballot(w != w0 || vm != vm0) == 0) {   // a flat wave: 64 equal contributions, added by one lane
+            if ((tid & 63) == 0) hist_add4(H[wave], w, vm, 64u);
+        } else {
+            hist_add4(H[wave], w, vm, 1u);
+        }
+        __syncthreads();   // the next tile's tables and footprint overwrite what a slower wave still samples
+    }
+    // the last barrier of the loop (t1 > t0 by the grid's construction) has every wave's adds in H
+    const uint32_t s = H[0][tid] + H[1][tid] + H[2][tid] + H[3][tid];
+    if (s) atomicAdd(c.hist + J.hist_off + tid, s);
+}
+
+// The kernels: the form without a mask and the MASK form beside it, as k_patch_compare's.
+__global__ __launch_bounds__(256) void k_patch_hist(const GrayArgs c) { patch_hist_body<false>(c); }
+__global__ __launch_bounds__(256) void k_patch_hist_masked(const GrayArgs c) { patch_hist_body<true>(c); }
+
+bool launch_patch_hist(const GrayArgs& a, hipStream_t st) {
+    if (a.njobs <= 0) return true;
+    if (a.run < 1 || a.grid < 1 || !a.hist) return false;
+    if (a.mask) hipLaunchKernelGGL(k_patch_hist_masked, dim3((unsigned)a.grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_patch_hist, dim3((unsigned)a.grid), dim3(256), 0, st, a);
+    return true;
+}
+
+// k_patch_threshold (fpm_last_segment / fpm_segment_at): k_patch_warp's grid, tile and sampling over jobs of one size;
+// instead of the pixel I it stores e = I - t where I > t (polarity +1), e = t - I where I < t (polarity -1), 0 elsewhere,
+// 0 everywhere for polarity 0 (a hit without foreground) and, MASK, 0 at ignored pixels, into the pitched patch buffer
+// where the labelling kernels take it.  t and the polarity come from the job: under Otsu they differ from hit to hit.
+template <bool MASK>
+__device__ __forceinline__ void patch_threshold_body(const GrayArgs c) {
+    __shared__ __attribute__((aligned(16))) int32_t tab[kPatchTabWords];
+    __shared__ __attribute__((aligned(16))) uint8_t FT[kPatchFtBytes];
+    const int tid = threadIdx.x;
+    // neighbouring tiles share footprint lines and output lines: keep them on one XCD's L2 (speed only)
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = c.tiles_x * c.tiles_y;
+    const int p = b / tiles, tl = b - p * tiles;
+    const int ty = tl / c.tiles_x, tx = tl - ty * c.tiles_x;
+    const GrayJob& J = c.jobs[p];
+    const int thr = __builtin_amdgcn_readfirstlane(J.t), pol = __builtin_amdgcn_readfirstlane(J.polarity);
+    PatchArgs a{};
+    a.jobs = &J.p;
+    a.njobs = 1;
+    a.level0 = c.level0;
+    a.img_stride = c.img_stride;
+    a.sw = c.sw; a.sh = c.sh; a.sp = c.sp;
+    a.pw = c.pw; a.ph = c.ph;
+    const PatchTile T = patch_tile_stage_at(a, tab, FT, tid, 0, tx, ty);
+    const int r = tid >> 4, gx = (tid & 15) * 4;
+    const int x = T.x0 + gx, y = T.y0 + r;
+    if (x >= c.pw || y >= c.ph) return;
+    const int nu = c.pw - x < 4 ? c.pw - x : 4;
+    const uint32_t w = patch_sample4(a, T, tab, FT, r, gx, nu);
+    uint32_t mw = 0xffffffffu;
+    if (MASK) mw = gray_mask4(c.mask, c.mkp, J.rx + x, J.ry + y, nu);
+    uint32_t ew = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)((w >> (8 * u)) & 255u);
+        const int d = pol > 0 ? i - thr : (pol < 0 ? thr - i : 0);
+        const bool in = ((mw >> (8 * u)) & 1u) != 0;
+        ew |= (uint32_t)(in && d > 0 ? d : 0) << (8 * u);
+    }
+    patch_store4(c.out + J.p.out_off + (size_t)y * c.row_stride + x, ew, nu, c.dword != 0);
+}
+
+__global__ __launch_bounds__(256) void k_patch_threshold(const GrayArgs c) { patch_threshold_body<false>(c); }
+__global__ __launch_bounds__(256) void k_patch_threshold_masked(const GrayArgs c) { patch_threshold_body<true>(c); }
+
+bool launch_patch_threshold(GrayArgs a, hipStream_t st) {
+    if (a.njobs <= 0 || a.pw <= 0 || a.ph <= 0) return true;
+    a.tiles_x = (a.pw + kPatchTw - 1) / kPatchTw;
+    a.tiles_y = (a.ph + kPatchTh - 1) / kPatchTh;
+    const int64_t grid = (int64_t)a.njobs * a.tiles_x * a.tiles_y;
+    if (grid > INT_MAX || !a.out) return false;
+    if (a.mask) hipLaunchKernelGGL(k_patch_threshold_masked, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_patch_threshold, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return true;
+}
+
 // ============================================================================================== variation model
 // k_model_accum (fpm_model_train_last / fpm_model_train_at): the per-pixel sum and sum of squares
 // of the patches of a job table, none of them written.  k_patch_warp's tile and 4 pixels per lane; a workgroup owns one

@@ -583,6 +583,43 @@ def caliper_derive(cal, lt_k, angle_k: float, raw) -> np.ndarray:
     return out
 
 
+# -- gray-value tools (fpm_hist_derive / fpm_last_histogram / fpm_last_segment ..): the hit's own gray values ---------
+# fpm_hist_stats and fpm_segment_info, field for field
+HIST_STATS_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.HistStats._fields_], align=True)
+SEGMENT_INFO_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.SegmentInfo._fields_], align=True)
+assert HIST_STATS_DTYPE.itemsize == C.sizeof(L.HistStats) == 64
+assert SEGMENT_INFO_DTYPE.itemsize == C.sizeof(L.SegmentInfo) == 16
+
+
+def hist_derive(hist) -> np.ndarray:
+    """fpm_hist_derive: the statistics of 256-bin histograms (uint32, shape (256,) or (..., 256), as last_histogram
+    returns them) as a HIST_STATS_DTYPE array of shape ``hist.shape[:-1]``: n, sum, sum_sq, min, max, median, mean,
+    stddev, Otsu's threshold (class 0 is I <= otsu) and flags (L.HIST_EMPTY: no pixel, every field 0; L.HIST_FLAT: one
+    occupied bin, otsu = min).  Raises ValueError for a histogram of more than 2^22 pixels.  Host only (no device)."""
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.ndim < 1 or h.shape[-1] != 256 or not np.array_equal(h, np.asarray(hist)):
+        raise ValueError("hist: uint32 values, 256 in the last dimension, expected")
+    flat = h.reshape(-1, 256)
+    out = np.zeros(len(flat), HIST_STATS_DTYPE)
+    lib = L.load()
+    for i in range(len(flat)):
+        rc = lib.fpm_hist_derive(flat[i].ctypes.data_as(C.POINTER(C.c_uint32)),
+                                 out[i:i + 1].ctypes.data_as(C.POINTER(L.HistStats)))
+        if rc != L.FPM_OK:
+            raise ValueError(f"fpm_hist_derive failed with {rc}")
+    return out.reshape(h.shape[:-1])
+
+
+def _segment_threshold(threshold) -> int:
+    if isinstance(threshold, str):
+        if threshold != "otsu":
+            raise ValueError(f"threshold {threshold!r}: 0 .. 255 or 'otsu' expected")
+        return L.SEG_OTSU
+    if int(threshold) != threshold or not 0 <= int(threshold) <= 255:
+        raise ValueError(f"threshold {threshold!r}: 0 .. 255 or 'otsu' expected")
+    return int(threshold)
+
+
 class TemplateMatcher:
     """Drop-in for the reference TemplateMatcher, one context (one HIP stream) per instance."""
 
@@ -1621,6 +1658,122 @@ class TemplateMatcher:
         ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
         if self._lib.fpm_caliper_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
             raise ValueError("fpm_caliper_profile failed")
+        return ms.value, n.value, b.value
+
+    # -- gray-value tools: histograms, Otsu and threshold blobs of every hit (fpm_*histogram* / fpm_*segment*) --------
+    def _gray_rects(self, rects):
+        """(array of fpm_patch_rect or None, K) of a histogram call: ``rects`` a list of (x, y, w, h) inside the
+        template (one such tuple also does); None = one rectangle, chosen as last_compare chooses its own."""
+        if rects is None:
+            r, _, _ = self._compare_rect(None)
+            return (None, 1) if r is None else ((L.PatchRect * 1)(r), 1)
+        tw, th = self._template_size()
+        rl = list(rects)
+        if len(rl) == 4 and all(np.ndim(v) == 0 for v in rl):
+            rl = [tuple(rl)]
+        if not 1 <= len(rl) <= L.GRAY_MAX_RECTS:
+            raise ValueError(f"1 .. {L.GRAY_MAX_RECTS} rectangles expected, got {len(rl)}")
+        arr = (L.PatchRect * len(rl))(*[L.PatchRect(*compare_rect(r, tw, th)) for r in rl])
+        return arr, len(rl)
+
+    def last_histogram(self, rects=None, source: int = 0) -> np.ndarray:
+        """The 256-bin gray-value histograms of the rectangles ``rects`` (template coordinates) on every result of the
+        last search, counted where the pixels are by one launch of k_patch_hist (fpm_last_histogram): uint32
+        (n_hits, K, 256), the pixels those of last_patches for that rectangle, under an enabled template mask the used
+        ones only.  Hits come in result order of ``source`` (``source=-1``: all sources), at the raw poses, or the aligned
+        ones after align_last(adopt=True).  hist_derive turns them into mean, median, Otsu's threshold and so on."""
+        arr, K = self._gray_rects(rects)
+        n = C.c_int32()
+        rc = self._lib.fpm_last_histogram(self._ctx, arr, K, int(source), None, 0, C.byref(n))
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_histogram")
+        hist = np.zeros((n.value, K, 256), np.uint32)
+        if n.value:
+            rc = self._lib.fpm_last_histogram(self._ctx, arr, K, int(source), hist.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              n.value, C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_histogram")
+        return hist
+
+    def histogram_at(self, src_index, lts, angles, rects=None) -> np.ndarray:
+        """last_histogram at poses the caller supplies, on the staged sources (fpm_histogram_at); poses as patches_at.
+        Needs staged sources and a template, not a search."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        arr, K = self._gray_rects(rects)
+        hist = np.zeros((len(idx), K, 256), np.uint32)
+        rc = self._lib.fpm_histogram_at(self._ctx, arr, K, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                        len(idx), hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "histogram_at")
+        return hist
+
+    def last_segment(self, rect=None, source: int = 0, threshold="otsu", polarity: int = -1, min_area: int = 4,
+                     connectivity: int = 8, cap: int = 64, image: bool = False):
+        """Every result of the last search thresholded inside ``rect`` and cut into connected regions, on the device
+        (fpm_last_segment).  ``polarity`` -1 takes the dark pixels (I < t, e = t - I), +1 the bright ones (I > t, e =
+        I - t); ``threshold`` is 0 .. 255 or "otsu": each hit's own Otsu threshold of the rectangle (t = otsu for
+        bright, otsu + 1 for dark).  Returns ``(info, summary, blobs)``: a SEGMENT_INFO_DTYPE array (n, the threshold
+        used, flags L.HIST_EMPTY / L.HIST_FLAT -- such a hit has no foreground -- and L.GRAY_OUTSIDE: the rectangle
+        leaves the source, border zeros are in it), and what ``blobs_host(e, 0, min_area, connectivity, cap)`` gives for
+        the images e; of a truncated hit any ``cap`` of its qualifying regions come back.  ``image=True``: also e as
+        uint8 (n_hits, h, w).  Under an enabled template mask ignored pixels are background."""
+        r, w, h = self._compare_rect(rect)
+        pr = C.byref(r) if r is not None else None
+        t = _segment_threshold(threshold)
+        args = (t, int(polarity), int(connectivity), int(min_area))
+        n = C.c_int32()
+        rc = self._lib.fpm_last_segment(self._ctx, int(source), pr, *args, None, None, None, int(cap), 0, C.byref(n),
+                                        None, 0, 0)
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_segment")
+        info = np.zeros(n.value, SEGMENT_INFO_DTYPE)
+        summary, recs, _, _ = _blob_buffers(n.value, 0, 0, cap, False)
+        img, pimg, row, patch = self._compare_diff(image, n.value, h, w)
+        if n.value:
+            rc = self._lib.fpm_last_segment(self._ctx, int(source), pr, *args,
+                                            info.ctypes.data_as(C.POINTER(L.SegmentInfo)),
+                                            summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                            recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), n.value, C.byref(n), pimg,
+                                            row, patch)
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_segment")
+        out = (info,) + _blob_result(summary, recs, None, False)
+        return out + (img,) if image else out
+
+    def segment_at(self, src_index, lts, angles, rect=None, threshold="otsu", polarity: int = -1, min_area: int = 4,
+                   connectivity: int = 8, cap: int = 64, image: bool = False):
+        """last_segment at poses the caller supplies, on the staged sources (fpm_segment_at); poses as patches_at."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        r, w, h = self._compare_rect(rect)
+        n = len(idx)
+        info = np.zeros(n, SEGMENT_INFO_DTYPE)
+        summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
+        img, pimg, row, patch = self._compare_diff(image, n, h, w)
+        rc = self._lib.fpm_segment_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                      n, C.byref(r) if r is not None else None, _segment_threshold(threshold),
+                                      int(polarity), int(connectivity), int(min_area),
+                                      info.ctypes.data_as(C.POINTER(L.SegmentInfo)),
+                                      summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
+                                      recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), pimg, row, patch)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "segment_at")
+        out = (info,) + _blob_result(summary, recs, None, False)
+        return out + (img,) if image else out
+
+    def gray_set_run(self, tiles: int = 0):
+        """Tiles per workgroup of k_patch_hist; 0 = the engine's choice.  For tests and measurements: results never
+        depend on it (fpm_gray_set_run)."""
+        if self._lib.fpm_gray_set_run(self._ctx, int(tiles)) != L.FPM_OK:
+            raise ValueError(f"gray_set_run({tiles!r}): {self.last_error()}")
+
+    def gray_profile(self, which: int):
+        """``(ms, launches, bytes)`` of one gray-value kernel (L.GRAY_HIST, L.GRAY_THRESHOLD), collected under
+        profile(True) and cleared by profile_reset (fpm_gray_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_gray_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError(f"gray_profile({which!r}) failed")
         return ms.value, n.value, b.value
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------

@@ -779,6 +779,9 @@ int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64
  *   fpm_last_inspect / fpm_inspect_at: e = 0 at ignored pixels; n is the used count inside the model's rectangle; the
  *     counts, the maximum, the sum, the box and the excess image follow, and gain / offset are the masked comparison's.
  *     fpm_last_blobs / fpm_blobs_at label that excess image: an ignored pixel is background.
+ *   fpm_last_histogram / fpm_histogram_at / fpm_last_segment / fpm_segment_at ("gray-value tools" below): pixel (u, v) of
+ *     a rectangle (x, y, w, h) is USED iff M(x + u, y + v) != 0.  A histogram counts the used pixels only, n =
+ *     fpm_mask_count(rect); Otsu's threshold comes from that histogram; e = 0 at ignored pixels, which are background.
  *   fpm_model_train_last / fpm_model_train_at: the planes accumulate EVERY pixel of the rectangle, masked or not -- the
  *     mask applies when inspecting, so it may be drawn or changed after training.  Only the FPM_COMPARE_NORMALIZE table
  *     is built from the masked sums.
@@ -796,6 +799,111 @@ int fpm_mask_enable(fpm_ctx* ctx, int32_t enable);
 int fpm_mask_info(const fpm_ctx* ctx, int32_t* width, int32_t* height, int64_t* count, int32_t* enabled);
 int fpm_mask_get(fpm_ctx* ctx, uint8_t* out, size_t stride);
 int fpm_mask_count(fpm_ctx* ctx, const fpm_patch_rect* rect, int64_t* n);
+
+/* --- gray-value tools: histograms, Otsu and threshold blobs of every hit (no reference equivalent) -------
+ * The tools above hold a hit against the template or a trained model.  These look at the hit's OWN gray values inside a
+ * region of the taught image: "is the cap present" (mean or median of a region), "is the print dark enough" (histogram,
+ * percentile), "how many pins or holes, and how big" (threshold, then connected regions).  They need no model.
+ * Rectangles.  A region is a comparison rectangle (x, y, w, h) in template coordinates under fpm_compare_at's rules:
+ * inside the template, 1 <= w * h <= 2^22, NULL = the whole template.  A learned template is required
+ * (FPM_E_NOT_LEARNED).  State, source, cap (hits), *n and the count-only call (cap = 0 with null outputs) are
+ * fpm_last_compare's for the _last entries, which sample at the context's last poses (the raw ones, or the aligned ones
+ * after FPM_ALIGN_ADOPT); pose and state rules are fpm_compare_at's for the _at entries.
+ * Pixels.  I(u, v) is pixel (u, v) of the patch fpm_patches_at gives for that rectangle and pose: same matrix, same
+ * fixed-point bilinear arithmetic, border 0, the inverted plane under bitwise_not.  With a template mask set and enabled
+ * pixel (u, v) is USED iff M(x + u, y + v) != 0 (the block above); without one every pixel of the rectangle is used.
+ * The used count is n = fpm_mask_count(rect), or w * h.
+ * Histogram.  H[b] = the number of used pixels with I == b, b = 0 .. 255, as uint32 (n <= 2^22 fits); the sum of H is n.
+ * Pixels outside the source are 0 and land in bin 0, as in a patch.  One call takes n_rects = 1 .. 64 rectangles, which
+ * may differ in size and are each checked as above; the output is uint32 [hit][rect][256] with hits * n_rects <= 65536.
+ * Derivation (fpm_hist_derive; host only, no context).  fpm_hist_stats, 64 bytes, no padding.  Integers first, then f64
+ * in the order written, every operation rounded on its own (no fused multiply-add).  With cum(v) = H[0] + .. + H[v]:
+ *     n = cum(255);  sum = sum of b H[b];  sum_sq = sum of b^2 H[b]                       (int64, exact)
+ *     min, max = the smallest and largest b with H[b] != 0;  median = the smallest v with 2 cum(v) >= n
+ *     mean = (double)sum / (double)n;  stddev = sqrt((double)(n sum_sq - sum sum)) / (double)n
+ *   Otsu.  For t = 0 .. 254 let n0 = cum(t) and s0 = sum over b <= t of b H[b].  t is ADMISSIBLE iff 0 < n0 < n.  N = n
+ *   s0 - n0 sum, exact in int64 (|N| < 2^53: exact as a double too);
+ *     B(t) = ((double)N * (double)N) / ((double)n0 * (double)(n - n0))
+ *   otsu = the admissible t with the largest B, the smallest such t on ties (t rising, replaced only on strictly
+ *   greater).  Class 0 is I <= otsu.
+ *   Degenerate.  n == 0: every field 0 and flags = FPM_HIST_EMPTY.  min == max (no admissible t): otsu = min and
+ *   FPM_HIST_FLAT is set.  A histogram whose total exceeds 2^22, or a null pointer: FPM_E_INVALID_ARG, *out untouched.
+ * Segmentation (one rectangle per call).  polarity = +1 (bright: foreground iff I > t, e = I - t) or -1 (dark: foreground
+ * iff I < t, e = t - I): e is 1 .. 255 on the foreground, 0 elsewhere and 0 at ignored pixels.  threshold = 0 .. 255, or
+ * FPM_SEG_OTSU: each hit then takes t from its own histogram of the rectangle, t = otsu for bright, t = otsu + 1 for
+ * dark (so both polarities cut between the same two classes).  A hit whose histogram is empty or flat has NO foreground
+ * under FPM_SEG_OTSU (e = 0 everywhere) and carries the flag; with a fixed threshold the histogram is not taken and
+ * those two flags stay 0.  The image e is labelled by the blob contract ("defect blobs") unchanged, with level 0:
+ * connectivity 4 or 8, seeds, min_area, cap_per_hit, FPM_BLOBS_TRUNCATED and the rule for truncated images of "defect
+ * blobs on the device".  In a record max_value and sum_value are the peak and the integrated contrast beyond the
+ * threshold.  Per hit the call returns fpm_segment_info (16 bytes, no padding): n = the used count, threshold = the t
+ * used, flags = FPM_HIST_EMPTY | FPM_HIST_FLAT | FPM_GRAY_OUTSIDE -- the last set on the host, in f64, by the calipers'
+ * four-corner rule on the rectangle's corner pixels (0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1): border zeros are in
+ * the region --; one fpm_blob_summary; cap_per_hit fpm_blob records; and, when img is not NULL, e as u8 images under
+ * fpm_last_inspect's image-buffer rules (row_stride >= w, patch_stride >= row_stride * h).
+ * Errors.  n_rects outside 1 .. 64, hits * n_rects > 65536, a bad rectangle, polarity other than +1 / -1, threshold
+ * outside -1 .. 255, the blob entries' argument rules, a null output, a pose beyond the samplers' range:
+ * FPM_E_INVALID_ARG, nothing launched, nothing written.  The calls change no search state: results, poses, candidates,
+ * staged sources, template, model and mask stay as they were.
+ * Launches, none part of a search or of a captured graph.  A histogram call: the output cleared on the stream, one
+ * k_patch_hist (k_patch_hist_masked under a mask) over all (hit, rectangle) jobs, the words back to a pinned buffer of
+ * the context, each histogram checked against its n, then copied to the caller.  A segmentation with a fixed threshold:
+ * one k_patch_threshold (or _masked), then the five labelling kernels per round.  Under FPM_SEG_OTSU the histogram
+ * launch and one copy to the host come first, fpm_hist_derive's rule per hit gives t, and the thresholds go back with
+ * the job table.  Integer arithmetic throughout: the results do not depend on any schedule, nor on fpm_gray_set_run.
+ * Out of scope: FPM_COMPARE_NORMALIZE tables (Otsu is the lighting-robust form), a band lo .. hi, hysteresis, more than
+ * one rectangle (size) inside one segmentation call, results left in device memory.
+ * Additive entries: FPM_ABI_VERSION and FPM_K_COUNT are unchanged. */
+typedef struct fpm_hist_stats {
+    int64_t n;                   /* pixels counted                                                    */
+    int64_t sum, sum_sq;         /* sum b H[b], sum b^2 H[b]                                          */
+    int32_t min, max;            /* smallest and largest occupied bin                                 */
+    int32_t median;              /* smallest v with 2 cum(v) >= n                                     */
+    int32_t otsu;                /* class 0 is I <= otsu                                              */
+    double mean, stddev;
+    int32_t flags;               /* FPM_HIST_EMPTY | FPM_HIST_FLAT                                    */
+    int32_t reserved;            /* 0 */
+} fpm_hist_stats;
+typedef struct fpm_segment_info {
+    int64_t n;                   /* used pixels of the rectangle                                      */
+    int32_t threshold;           /* the t used                                                        */
+    int32_t flags;               /* FPM_HIST_EMPTY | FPM_HIST_FLAT | FPM_GRAY_OUTSIDE                 */
+} fpm_segment_info;
+#define FPM_HIST_EMPTY 1
+#define FPM_HIST_FLAT 2
+#define FPM_GRAY_OUTSIDE 4
+#define FPM_SEG_OTSU (-1)                /* threshold: per hit, from its own histogram */
+#define FPM_GRAY_MAX_RECTS 64            /* n_rects */
+#define FPM_GRAY_MAX_JOBS 65536          /* hits * n_rects */
+
+/* host only, no context: the statistics and Otsu's threshold of one histogram, by the rule above */
+int fpm_hist_derive(const uint32_t hist[256], fpm_hist_stats* out);
+/* the histograms of n_rects rectangles over the hits of the last search in result order (source = -1: of all sources);
+ * hist: uint32 [hit][rect][256] */
+int fpm_last_histogram(fpm_ctx* ctx, const fpm_patch_rect* rects /* NULL with n_rects = 1: the whole template */,
+                       int32_t n_rects, int32_t source, uint32_t* hist, int32_t cap /* hits */, int32_t* n);
+/* the same at caller-supplied poses on the staged sources */
+int fpm_histogram_at(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, const int32_t* src_index,
+                     const float* lt, const double* angles, int32_t n_poses, uint32_t* hist);
+/* the hits of the last search thresholded inside rect and cut into blobs; info, summary: one per hit; out: cap_per_hit
+ * records per hit; img (may be NULL): the e images */
+int fpm_last_segment(fpm_ctx* ctx, int32_t source, const fpm_patch_rect* rect, int32_t threshold, int32_t polarity,
+                     int32_t connectivity, int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary,
+                     fpm_blob* out, int32_t cap_per_hit, int32_t cap /* hits */, int32_t* n, uint8_t* img,
+                     size_t row_stride, size_t patch_stride);
+/* the same at caller-supplied poses on the staged sources */
+int fpm_segment_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                   const fpm_patch_rect* rect, int32_t threshold, int32_t polarity, int32_t connectivity,
+                   int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary, fpm_blob* out,
+                   int32_t cap_per_hit, uint8_t* img, size_t row_stride, size_t patch_stride);
+/* tiles per workgroup of k_patch_hist (a workgroup walks that many consecutive 64 x 16 tiles of one job before it adds
+ * its 256 counts to the job's histogram); 0 = the engine's choice.  For tests and measurements: results never depend
+ * on it. */
+int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles);
+/* Timing of the two kernels, collected under fpm_profile_enable and cleared by fpm_profile_reset as
+ * fpm_caliper_profile's (no FPM_K_* index).  which: 0 = k_patch_hist, 1 = k_patch_threshold; bytes = source pixels
+ * read (+ mask bytes read) + histogram words or e pixels written. */
+int fpm_gray_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
 
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------

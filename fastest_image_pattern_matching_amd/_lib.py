@@ -81,6 +81,10 @@ SEG_OTSU = -1
 GRAY_MAX_RECTS, GRAY_MAX_JOBS = 64, 65536
 GRAY_HIST, GRAY_THRESHOLD = 0, 1
 GRAY_KERNEL_SYMBOLS = ["k_patch_hist", "k_patch_threshold"]
+# sub-pattern locators (fpm_locate_host / fpm_locate_derive / fpm_last_locate / fpm_locate_at): flags and caps
+LOCATE_EDGE_X, LOCATE_EDGE_Y, LOCATE_FLAT, LOCATE_OUTSIDE = 1, 2, 4, 8
+LOCATE_MAX_SIDE, LOCATE_MAX_RADIUS, LOCATE_MAX_FEATURES, LOCATE_MAX_JOBS = 128, 16, 64, 65536
+LOCATE_KERNEL_SYMBOL = "k_patch_locate"
 
 
 class Params(C.Structure):
@@ -212,6 +216,28 @@ class SegmentInfo(C.Structure):
     """fpm_segment_info -- one hit of fpm_last_segment / fpm_segment_at: used pixels, the threshold used, flags."""
 
     _fields_ = [("n", C.c_int64), ("threshold", C.c_int32), ("flags", C.c_int32)]
+
+
+class Feature(C.Structure):
+    """fpm_feature -- a region of the template to find again on a hit, with its search radii."""
+
+    _fields_ = [(n, C.c_int32) for n in ("x", "y", "w", "h", "rx", "ry")] + [("reserved", C.c_int32 * 2)]
+
+
+class LocateRaw(C.Structure):
+    """fpm_locate_raw -- what k_patch_locate writes per (hit, feature): the peak and the integer sums around it."""
+
+    _fields_ = [(n, C.c_int32) for n in ("dx", "dy", "flags", "reserved")] + \
+               [(n, C.c_int64) for n in ("n", "sum_t", "sum_tt")] + \
+               [(n, C.c_int32 * 9) for n in ("s_i", "s_ii", "s_it")] + \
+               [(n, C.c_int32) for n in ("c_i", "c_ii", "c_it")]
+
+
+class LocateResult(C.Structure):
+    """fpm_locate_result -- what fpm_locate_derive makes of one raw record."""
+
+    _fields_ = [(n, C.c_int32) for n in ("dx", "dy", "flags", "reserved")] + \
+               [(n, C.c_double) for n in ("score", "score_nominal", "ox", "oy", "tx", "ty", "sx", "sy")]
 
 
 class RoiRecord(C.Structure):
@@ -387,6 +413,16 @@ SIGNATURES = {
                                  C.POINTER(BlobSummary), C.POINTER(Blob), C.c_int32, _U8P, C.c_size_t, C.c_size_t]),
     "fpm_gray_set_run": (C.c_int, [_P, C.c_int32]),
     "fpm_gray_profile": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_locate_host": (C.c_int, [_U8P, C.c_size_t, _U8P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(LocateRaw), C.POINTER(C.c_int32)]),
+    "fpm_locate_derive": (C.c_int, [C.POINTER(Feature), C.c_float, C.c_float, C.c_double, C.POINTER(LocateRaw),
+                                    C.POINTER(LocateResult)]),
+    "fpm_locate_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32,
+                                C.POINTER(Feature), C.c_int32, C.POINTER(LocateResult), C.POINTER(LocateRaw),
+                                C.POINTER(C.c_int32), C.c_int32]),
+    "fpm_last_locate": (C.c_int, [_P, C.c_int32, C.POINTER(Feature), C.c_int32, C.POINTER(LocateResult),
+                                  C.POINTER(LocateRaw), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_locate_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

@@ -154,10 +154,11 @@ struct KProf {
 };
 // Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
 // alignment's one (fpm_align_profile), the blob labelling's five (fpm_blobs_profile), the calipers' one
-// (fpm_caliper_profile) and the gray-value tools' two (fpm_gray_profile), which have no FPM_K_* index: FPM_K_COUNT stays
-// what it is.
+// (fpm_caliper_profile), the gray-value tools' two (fpm_gray_profile) and the locators' one (fpm_locate_profile), which
+// have no FPM_K_* index: FPM_K_COUNT stays what it is.
 enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfBlobTile, kProfBlobMerge,
-       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfGrayHist, kProfGrayThreshold, kProfSlots };
+       kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfGrayHist, kProfGrayThreshold, kProfLocate,
+       kProfSlots };
 
 }  // namespace
 
@@ -255,6 +256,9 @@ struct fpm_ctx {
     int gray_run = 0;         // fpm_gray_set_run: tiles per workgroup of k_patch_hist, 0 = the engine's choice
     DevBuf d_gray;
     PinBuf h_gray;
+    // sub-pattern locators (fpm_last_locate / fpm_locate_at): the raw records and maps of a call and their host copy
+    DevBuf d_locout;
+    PinBuf h_locout;
     // template mask (fpm_mask_*): one u8 plane of the template's level-0 size and row pitch, 0x00 /
     // 0xFF, zero behind a row's end; mask_host = its dense host copy (the counts, fpm_mask_get).  d_mask_in = the
     // staging buffer (a host mask's upload, the plane being staged, the count); a set that fails leaves d_mask alone.
@@ -3413,6 +3417,132 @@ int segment_of_poses(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pa
     return FPM_OK;
 }
 
+// ---- sub-pattern locators (fpm_last_locate, fpm_locate_at) ----
+static_assert(sizeof(fpm_feature) == 32 && sizeof(fpm_locate_raw) == 160 && sizeof(fpm_locate_result) == 80,
+              "the locator structs have no padding");
+static_assert(sizeof(fpm_locate_raw) == sizeof(int32_t) * kLocateWords, "k_patch_locate writes the record as dwords");
+static_assert(sizeof(LocateJob) % 8 == 0, "a table of LocateJob keeps its doubles aligned");
+static_assert(kLocateMaxSide == FPM_LOCATE_MAX_SIDE && kLocateMaxRadius == FPM_LOCATE_MAX_RADIUS, "one set of caps");
+
+// the rules of a call's features that do not depend on the number of hits; *max_off = the largest offset count
+int locate_args(fpm_ctx* ctx, const fpm_feature* feats, int32_t n_feats, const int32_t* maps, int32_t map_stride, int* max_off) {
+    if (!feats || n_feats < 1 || n_feats > FPM_LOCATE_MAX_FEATURES) { ctx->err = "1 .. 64 features expected"; return FPM_E_INVALID_ARG; }
+    const int tw = ctx->tmpl[0].w, th = ctx->tmpl[0].h;
+    *max_off = 0;
+    for (int k = 0; k < n_feats; ++k) {
+        const fpm_feature& f = feats[k];
+        if (const char* bad = feature_bad(f)) { ctx->err = bad; return FPM_E_INVALID_ARG; }
+        if (f.x < 0 || f.y < 0 || f.w > tw - f.x || f.h > th - f.y) {
+            ctx->err = "feature: the rectangle must lie inside the template";
+            return FPM_E_INVALID_ARG;
+        }
+        *max_off = std::max(*max_off, (2 * f.rx + 1) * (2 * f.ry + 1));
+    }
+    if (maps && map_stride < *max_off) { ctx->err = "map_stride below the largest (2 rx + 1)(2 ry + 1)"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+// Row bands of one offset's S_it (LocateJob::bands): the count, up to 16, that leaves the 256 lanes the fewest rows to
+// walk, rounds x rows per band; the smallest such count.  Speed only: the sums are integers.
+int locate_bands(int noff, int h) {
+    int best = 1;
+    int64_t cost = INT64_MAX;
+    for (int nb = 1; nb <= std::min(h, 16); ++nb) {
+        const int64_t c = (int64_t)((noff * nb + 255) / 256) * ((h + nb - 1) / nb);
+        if (c < cost) { cost = c; best = nb; }
+    }
+    return best;
+}
+
+// The features of `poses` (n >= 1), every argument checked: the job table, one launch of k_patch_locate, the raw records
+// and maps to pinned memory, the records checked, then the derivation into the caller's buffers.  Caller memory is
+// written only after the device pass has succeeded.
+int locate_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_feature* feats, int n_feats, int max_off,
+                   fpm_locate_result* results, fpm_locate_raw* raw, int32_t* maps, int32_t map_stride) {
+    const int njobs = (int)poses.size() * n_feats;
+    const SrcLevel& l0 = ctx->src[0];
+    const TmplLevel& t0 = ctx->tmpl[0];
+    const size_t tab = round_up(sizeof(LocateJob) * (size_t)njobs, (size_t)256);
+    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
+    HIP_TRY(ctx->h_patchtab.ensure(tab));
+    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    // the device output: records, then the maps at the largest offset count (the caller's stride is the host's)
+    const size_t rec_b = sizeof(fpm_locate_raw) * (size_t)njobs;
+    const size_t map_b = maps ? sizeof(int32_t) * 3 * (size_t)max_off * (size_t)njobs : 0;
+    HIP_TRY(ctx->d_locout.ensure(rec_b + map_b));
+    HIP_TRY(ctx->h_locout.ensure(rec_b + map_b));
+    std::vector<int32_t> outside((size_t)njobs, 0);
+    int64_t bytes = (int64_t)(rec_b + map_b);
+    LocateJob* jobs = ctx->h_patchtab.as<LocateJob>();
+    for (int i = 0, j = 0; i < (int)poses.size(); ++i)
+        for (int k = 0; k < n_feats; ++k, ++j) {
+            const fpm_feature& f = feats[k];
+            const fpm_patch_rect r{f.x - f.rx, f.y - f.ry, f.w + 2 * f.rx, f.h + 2 * f.ry};   // the window
+            LocateJob& job = jobs[j];
+            const int rc = patch_pose_matrix(ctx, r, poses[(size_t)i], i, nullptr, job.p.M);
+            if (rc != FPM_OK) return rc;
+            job.p.out_off = 0;
+            job.p.src = poses[(size_t)i].src;
+            job.p.pad = 0;
+            job.x = f.x; job.y = f.y; job.w = f.w; job.h = f.h; job.rx = f.rx; job.ry = f.ry;
+            job.bands = locate_bands((2 * f.rx + 1) * (2 * f.ry + 1), f.h);
+            job.pad = 0;
+            bytes += (int64_t)r.w * r.h + (int64_t)f.w * f.h;
+            // border zeros in the window: a corner sample outside the source, through the matrix the sampler takes
+            bool o = false;
+            for (int e = 0; e < 4; ++e) {
+                const double x = (e & 1) ? r.w - 1 : 0, y = (e & 2) ? r.h - 1 : 0;
+                const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
+                o = o || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
+            }
+            outside[(size_t)j] = o ? FPM_LOCATE_OUTSIDE : 0;
+        }
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    LocateArgs a{};
+    a.jobs = ctx->d_patchtab.as<LocateJob>();
+    a.njobs = njobs;
+    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    a.img_stride = l0.img_bytes;
+    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    a.tmpl = ctx->d_tmpl.as<uint8_t>() + t0.off;
+    a.tp = t0.pitch;
+    a.raw = ctx->d_locout.as<int32_t>();
+    a.maps = maps ? ctx->d_locout.as<int32_t>(rec_b) : nullptr;
+    a.map_stride = max_off;
+    {
+        ProfScope ps(ctx, kProfLocate, bytes);   // window pixels sampled + template pixels read + records and maps written
+        if (!launch_patch_locate(a, ctx->stream)) { ctx->err = "bad locate launch"; return FPM_E_INTERNAL; }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_locout.p, ctx->d_locout.p, rec_b + map_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    fpm_locate_raw* hr = ctx->h_locout.as<fpm_locate_raw>();
+    std::vector<fpm_locate_result> res((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) {   // what the device wrote is checked before anything of it reaches the caller
+        const RawPose& p = poses[(size_t)(j / n_feats)].pose;
+        if (hr[j].flags != 0 || hr[j].reserved != 0) { ctx->err = "k_patch_locate returned a record with flags"; return FPM_E_INTERNAL; }
+        hr[j].flags = outside[(size_t)j];
+        if (!locate_derive(feats[j % n_feats], p.x, p.y, p.angle, hr[j], &res[(size_t)j])) {
+            ctx->err = "k_patch_locate returned a record that is no peak of its feature";
+            return FPM_E_INTERNAL;
+        }
+    }
+    std::memcpy(results, res.data(), sizeof(fpm_locate_result) * (size_t)njobs);
+    if (raw) std::memcpy(raw, hr, rec_b);
+    if (maps) {
+        const int32_t* hm = ctx->h_locout.as<int32_t>(rec_b);
+        for (size_t q = 0; q < (size_t)njobs * 3; ++q) {
+            int32_t* mq = maps + q * (size_t)map_stride;
+            std::memcpy(mq, hm + q * (size_t)max_off, sizeof(int32_t) * (size_t)max_off);
+            if (map_stride > max_off) std::memset(mq + max_off, 0, sizeof(int32_t) * (size_t)(map_stride - max_off));
+        }
+    }
+    return FPM_OK;
+}
+
 // fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
 // the device learn's second half
 int learn_from_model(fpm_ctx* ctx) {
@@ -3505,6 +3635,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->h_blobrec.release(); ctx->h_bloblab.release();
     ctx->d_calout.release(); ctx->h_calout.release();
     ctx->d_gray.release(); ctx->h_gray.release();
+    ctx->d_locout.release(); ctx->h_locout.release();
     ctx->d_mask.release(); ctx->d_mask_in.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
@@ -4564,6 +4695,52 @@ int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles) {
 int fpm_gray_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
     if (!ctx || which < 0 || which > 1 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
     const KProf& p = ctx->kp[kProfGrayHist + which];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
+}
+
+// --- sub-pattern locators (fpm_locate_host and fpm_locate_derive: fpm_host.cpp) --------------------
+int fpm_locate_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                  const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results, fpm_locate_raw* raw, int32_t* maps,
+                  int32_t map_stride) {
+    if (!ctx) return FPM_E_INVALID_ARG;
+    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    int max_off = 0;
+    int rc = patch_state(ctx, false);
+    if (rc == FPM_OK) rc = locate_args(ctx, feats, n_feats, maps, map_stride, &max_off);
+    if (rc != FPM_OK || n_poses == 0) return rc;
+    if (!results) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)n_poses * n_feats > FPM_LOCATE_MAX_JOBS) { ctx->err = "hits x features above 65536"; return FPM_E_INVALID_ARG; }
+    std::vector<PatchPose> poses((size_t)n_poses);
+    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return locate_to_host(ctx, poses, feats, n_feats, max_off, results, raw, maps, map_stride);
+}
+
+int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results,
+                    fpm_locate_raw* raw, int32_t* maps, int32_t map_stride, int32_t cap, int32_t* n) {
+    if (!ctx || !n) return FPM_E_INVALID_ARG;
+    *n = 0;
+    int max_off = 0;
+    std::vector<PatchPose> poses;
+    int rc = patch_state(ctx, true);
+    if (rc == FPM_OK) rc = locate_args(ctx, feats, n_feats, maps, map_stride, &max_off);
+    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
+    if (rc != FPM_OK) return rc;
+    *n = (int32_t)poses.size();
+    if ((int)poses.size() > cap) { ctx->err = "locate buffers too small"; return FPM_E_CAPACITY; }
+    if (poses.empty()) return FPM_OK;
+    if (!results) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)poses.size() * n_feats > FPM_LOCATE_MAX_JOBS) { ctx->err = "hits x features above 65536"; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    return locate_to_host(ctx, poses, feats, n_feats, max_off, results, raw, maps, map_stride);
+}
+
+int fpm_locate_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[kProfLocate];
     *ms = p.ms;
     *launches = p.launches;
     *bytes = p.bytes;

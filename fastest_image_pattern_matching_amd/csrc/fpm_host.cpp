@@ -759,7 +759,119 @@ bool hist_derive(const uint32_t hist[256], fpm_hist_stats* out) {
     return true;
 }
 
+// ---- sub-pattern locators (include/fpm.h, "sub-pattern locators"): integers first, then f64 in the header's order.
+const char* feature_bad(const fpm_feature& f) {
+    if (f.w < 1 || f.w > FPM_LOCATE_MAX_SIDE || f.h < 1 || f.h > FPM_LOCATE_MAX_SIDE) return "feature: w and h must be 1 .. 128";
+    if (f.rx < 0 || f.rx > FPM_LOCATE_MAX_RADIUS || f.ry < 0 || f.ry > FPM_LOCATE_MAX_RADIUS) return "feature: rx and ry must be 0 .. 16";
+    if (f.reserved[0] != 0 || f.reserved[1] != 0) return "feature: reserved must be 0";
+    return nullptr;
+}
+
+double locate_zncc(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt, int64_t sit) {
+    const int64_t Di = n * sii - si * si, Dt = n * stt - st * st, N = n * sit - si * st;
+    const double sdi = std::sqrt((double)Di), sdt = std::sqrt((double)Dt);
+    return Di == 0 || Dt == 0 ? 0.0 : (double)N / (sdi * sdt);
+}
+
+void locate_host(const uint8_t* window, size_t ws, const uint8_t* tmpl, size_t ts, int w, int h, int rx, int ry,
+                 fpm_locate_raw* raw, int32_t* maps) {
+    const int nx = 2 * rx + 1, ny = 2 * ry + 1, noff = nx * ny;
+    std::vector<int32_t> own;
+    if (!maps) { own.resize((size_t)3 * noff); maps = own.data(); }
+    int32_t *mi = maps, *mii = maps + noff, *mit = maps + 2 * noff;
+    int64_t st = 0, stt = 0;
+    for (int b = 0; b < h; ++b)
+        for (int a = 0; a < w; ++a) {
+            const int64_t t = tmpl[(size_t)b * ts + a];
+            st += t; stt += t * t;
+        }
+    const int64_t n = (int64_t)w * h;
+    int best = -1;
+    double bz = 0.0;
+    int bd = 0;
+    for (int j = 0; j < ny; ++j)
+        for (int i = 0; i < nx; ++i) {
+            int64_t si = 0, sii = 0, sit = 0;
+            for (int b = 0; b < h; ++b) {
+                const uint8_t* wr = window + (size_t)(b + j) * ws + i;
+                const uint8_t* tr = tmpl + (size_t)b * ts;
+                for (int a = 0; a < w; ++a) {
+                    const int64_t v = wr[a];
+                    si += v; sii += v * v; sit += v * tr[a];
+                }
+            }
+            const int o = j * nx + i;
+            mi[o] = (int32_t)si; mii[o] = (int32_t)sii; mit[o] = (int32_t)sit;
+            const double z = locate_zncc(n, si, sii, st, stt, sit);
+            const int dx = i - rx, dy = j - ry, d = dx * dx + dy * dy;
+            // row-major order: among equal z and equal distance the earlier offset has the smaller dy, then dx
+            if (best < 0 || z > bz || (z == bz && d < bd)) { best = o; bz = z; bd = d; }
+        }
+    fpm_locate_raw r{};
+    const int pj = best / nx, pi = best - pj * nx;
+    r.dx = pi - rx; r.dy = pj - ry;
+    r.n = n; r.sum_t = st; r.sum_tt = stt;
+    for (int j = -1; j <= 1; ++j)
+        for (int i = -1; i <= 1; ++i) {
+            const int qi = pi + i, qj = pj + j, e = (j + 1) * 3 + (i + 1);
+            if (qi < 0 || qi >= nx || qj < 0 || qj >= ny) continue;
+            r.s_i[e] = mi[qj * nx + qi]; r.s_ii[e] = mii[qj * nx + qi]; r.s_it[e] = mit[qj * nx + qi];
+        }
+    const int c = ry * nx + rx;
+    r.c_i = mi[c]; r.c_ii = mii[c]; r.c_it = mit[c];
+    *raw = r;
+}
+
+bool locate_derive(const fpm_feature& f, float lt_x, float lt_y, double angle, const fpm_locate_raw& r, fpm_locate_result* out) {
+    if (r.n != (int64_t)f.w * f.h || r.dx < -f.rx || r.dx > f.rx || r.dy < -f.ry || r.dy > f.ry) return false;
+    auto z = [&](int e) { return locate_zncc(r.n, r.s_i[e], r.s_ii[e], r.sum_t, r.sum_tt, r.s_it[e]); };
+    fpm_locate_result o{};
+    o.dx = r.dx; o.dy = r.dy;
+    o.flags = r.flags & FPM_LOCATE_OUTSIDE;
+    const double z0 = z(4);
+    o.score = z0;
+    o.score_nominal = locate_zncc(r.n, r.c_i, r.c_ii, r.sum_t, r.sum_tt, r.c_it);
+    const int64_t Di = r.n * (int64_t)r.s_ii[4] - (int64_t)r.s_i[4] * r.s_i[4], Dt = r.n * r.sum_tt - r.sum_t * r.sum_t;
+    if (Di == 0 || Dt == 0) o.flags |= FPM_LOCATE_FLAT;
+    auto sub = [&](int em, int ep) {
+        const double zm = z(em), zp = z(ep);
+        const double den = (zm - z0) + (zp - z0);
+        return den < 0.0 ? 0.5 * (zm - zp) / den : 0.0;
+    };
+    double ddx = 0.0, ddy = 0.0;
+    if (r.dx == -f.rx || r.dx == f.rx) o.flags |= FPM_LOCATE_EDGE_X;
+    else ddx = sub(3, 5);
+    if (r.dy == -f.ry || r.dy == f.ry) o.flags |= FPM_LOCATE_EDGE_Y;
+    else ddy = sub(1, 7);
+    o.ox = (double)r.dx + ddx;
+    o.oy = (double)r.dy + ddy;
+    o.tx = ((double)f.x + (double)(f.w - 1) / 2.0) + o.ox;
+    o.ty = ((double)f.y + (double)(f.h - 1) / 2.0) + o.oy;
+    const double ra = angle * kD2R, c = std::cos(ra), s = std::sin(ra);
+    o.sx = (double)lt_x + (o.tx * c - o.ty * s);
+    o.sy = (double)lt_y + (o.tx * s + o.ty * c);
+    *out = o;
+    return true;
+}
+
 }  // namespace fpm
+
+int fpm_locate_host(const uint8_t* window, size_t window_stride, const uint8_t* tmpl, size_t tmpl_stride, int32_t w,
+                    int32_t h, int32_t rx, int32_t ry, fpm_locate_raw* raw, int32_t* maps) {
+    const fpm_feature f{0, 0, w, h, rx, ry, {0, 0}};
+    if (!window || !tmpl || !raw || fpm::feature_bad(f) || window_stride < (size_t)(w + 2 * rx) || tmpl_stride < (size_t)w)
+        return FPM_E_INVALID_ARG;
+    fpm::locate_host(window, window_stride, tmpl, tmpl_stride, w, h, rx, ry, raw, maps);
+    return FPM_OK;
+}
+
+int fpm_locate_derive(const fpm_feature* feat, float lt_x, float lt_y, double angle, const fpm_locate_raw* raw,
+                      fpm_locate_result* out) {
+    if (!feat || !raw || !out || fpm::feature_bad(*feat) || !std::isfinite(lt_x) || !std::isfinite(lt_y) ||
+        !std::isfinite(angle) || !fpm::locate_derive(*feat, lt_x, lt_y, angle, *raw, out))
+        return FPM_E_INVALID_ARG;
+    return FPM_OK;
+}
 
 int fpm_hist_derive(const uint32_t hist[256], fpm_hist_stats* out) {
     if (!hist || !out || !fpm::hist_derive(hist, out)) return FPM_E_INVALID_ARG;

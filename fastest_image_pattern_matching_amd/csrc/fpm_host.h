@@ -81,5 +81,15 @@ int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n);
 // the statistics and Otsu's threshold of one histogram by the header's rule; false (nothing written) when its total
 // exceeds 2^22
 bool hist_derive(const uint32_t hist[256], fpm_hist_stats* out);
+// ---- sub-pattern locators (include/fpm.h, "sub-pattern locators") ----
+// the range rules of one feature that need no template (sizes, radii, reserved); nullptr = fine, else what is wrong
+const char* feature_bad(const fpm_feature& f);
+// fpm_compare_derive's zncc of the six sums, in its order
+double locate_zncc(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt, int64_t sit);
+// sums, peak and raw record of one window against one template region (arguments checked by the caller); maps may be null
+void locate_host(const uint8_t* window, size_t ws, const uint8_t* tmpl, size_t ts, int w, int h, int rx, int ry,
+                 fpm_locate_raw* raw, int32_t* maps);
+// one raw record into *out; false (nothing written) for a record no search of f can have produced
+bool locate_derive(const fpm_feature& f, float lt_x, float lt_y, double angle, const fpm_locate_raw& r, fpm_locate_result* out);
 
 }  // namespace fpm

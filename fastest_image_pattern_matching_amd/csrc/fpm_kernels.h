@@ -391,6 +391,32 @@ struct GrayArgs {
 bool launch_patch_hist(const GrayArgs& a, hipStream_t st);
 // k_patch_threshold: k_patch_warp's grid over jobs of one size.  Returns false for a grid past 2^31 - 1.
 bool launch_patch_threshold(GrayArgs a, hipStream_t st);
+// ---- sub-pattern locators (fpm_last_locate / fpm_locate_at): the window of a (hit, feature) job
+// sampled into LDS, correlated there with the feature's template region at every offset of the search range, reduced to
+// the peak's record.  One descriptor per job, built on the host.
+constexpr int kLocateMaxSide = 128, kLocateMaxRadius = 16;
+constexpr int kLocateWords = 40;   // an fpm_locate_raw in dwords
+struct LocateJob {
+    PatchJob p;              // the inverted matrix of the WINDOW rectangle and the source, as for k_patch_warp; out_off unused
+    int32_t x, y, w, h;      // the feature's region in the template (inside it), w, h 1 .. kLocateMaxSide
+    int32_t rx, ry;          // radii 0 .. kLocateMaxRadius
+    int32_t bands;           // row bands an offset's S_it is cut into, 1 .. h (speed only: integer sums)
+    int32_t pad;
+};
+struct LocateArgs {
+    const LocateJob* jobs;
+    int32_t njobs;
+    const uint8_t* level0;   // as PatchArgs
+    size_t img_stride;
+    int32_t sw, sh, sp;
+    const uint8_t* tmpl;     // template level 0, row pitch tp (a multiple of 64)
+    int32_t tp;
+    int32_t* raw;            // [njobs][kLocateWords]: fpm_locate_raw records
+    int32_t* maps;           // [njobs][3][map_stride] or null
+    int32_t map_stride;
+};
+// k_patch_locate: one workgroup per job.  Returns false, launching nothing, without a record buffer.
+bool launch_patch_locate(const LocateArgs& a, hipStream_t st);
 // ---- defect blobs on the device (fpm_last_blobs / fpm_blobs_at / fpm_op_blobs): connected
 // components of n pitched u8 images of one size, by a union-find per 64 x 16 tile in LDS and a merge of the tile pieces
 // in device memory.  A label is the row-major index v * w + u, within its image, of a pixel of the same component that is

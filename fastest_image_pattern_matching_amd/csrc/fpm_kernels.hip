@@ -3526,6 +3526,258 @@ bool launch_patch_threshold(GrayArgs a, hipStream_t st) {
     return true;
 }
 
+// ============================================================================================== sub-pattern locators
+// k_patch_locate (fpm_last_locate / fpm_locate_at): one workgroup owns one (hit, feature) job and
+// keeps everything of it in LDS.
+//  1. The window, ww x wh = (w + 2 rx) x (h + 2 ry) pixels, is sampled in k_patch_warp's 64 x 16 tiles with the patch
+//     family's staging and sampler (patch_tile_stage_at / patch_sample4 through a local PatchArgs, as k_caliper), so the
+//     bytes are k_patch_warp's by construction, and stored as dwords into WIN, row pitch 164 bytes (41 dwords, odd: a
+//     lane per row or a lane per column both spread over the banks).
+//  2. S_i, then S_ii, from running sums: a lane per window column slides a column sum of h rows down the 2 ry + 1
+//     vertical offsets into C; a lane per vertical offset slides a sum of w such column sums along the 2 rx + 1
+//     horizontal ones.  One pass per kind: the u32 column sums of both would not fit beside the rest.
+//  3. The template region is staged from the template slab (k_patch_compare's aligned dword pair, funnel-shifted) into
+//     T, row pitch TP = w rounded up to 16, zero from w on, with sum T and sum T^2 on the way.
+//  4. S_it, the hot loop.  A work unit is (row band, offset); consecutive lanes take consecutive offsets, so a wave reads
+//     the same template dwords (an LDS broadcast, four at a time) and neighbouring window dwords.  Per template dword a
+//     lane reads one window dword, funnel-shifts it with the one before by dx & 3 (v_alignbyte) and issues one
+//     v_dot4_u32_u8; window bytes beyond column w meet a zero template byte.  A unit's partial sum is added to its
+//     offset with an LDS integer atomic: the sum does not depend on the order.
+//  5. z per offset in f64 (fpm_compare_derive's expression; the file is built with -ffp-contract=off, sqrt and / are
+//     correctly rounded), the peak under the tie rule by a tree over the 256 lanes -- the order (z, then the smaller
+//     dx^2 + dy^2, then the smaller row-major index) is total, so the tree's shape cannot matter --, then the record
+//     and the maps with plain vector stores.
+// LDS: WIN 26 240, S_i and S_ii 2 x 4 356, and one region of 21 264 bytes that is in turn the staging tables and
+// footprint, the column sums, then T (16 384), S_it (4 356) and the reduction's 4 096: 56 224 bytes in all.
+// Every loop bound comes from the job, the same words for every lane: every barrier is workgroup-uniform.
+constexpr int kLocWP = 164;                                  // window row pitch in bytes
+constexpr int kLocWinBytes = (kLocateMaxSide + 2 * kLocateMaxRadius) * kLocWP;
+constexpr int kLocMaxOff = (2 * kLocateMaxRadius + 1) * (2 * kLocateMaxRadius + 1);
+constexpr int kLocSOff = kLocWinBytes;                       // S_i, S_ii
+constexpr int kLocUOff = (kLocSOff + 2 * 4 * kLocMaxOff + 15) & ~15;
+constexpr int kLocTBytes = kLocateMaxSide * kLocateMaxSide;
+constexpr int kLocUBytes = 21264;
+constexpr int kLocArena = kLocUOff + kLocUBytes;
+static_assert(kLocUBytes >= 4 * kPatchTabWords + ((kPatchFtBytes + 15) & ~15), "the staging tables and footprint fit");
+static_assert(kLocUBytes >= 4 * (2 * kLocateMaxRadius + 1) * ((kLocateMaxSide + 2 * kLocateMaxRadius) | 1), "the column sums fit");
+static_assert(kLocUBytes >= kLocTBytes + 4 * kLocMaxOff && kLocTBytes >= 4096, "T, S_it and the reduction fit");
+static_assert(kLocArena <= 65536, "one workgroup's static LDS");
+
+__device__ __forceinline__ double locate_zncc_dev(int64_t n, int64_t si, int64_t sii, int64_t st, int64_t stt, int64_t sit) {
+    const int64_t Di = n * sii - si * si, Dt = n * stt - st * st, N = n * sit - si * st;
+    const double sdi = sqrt((double)Di), sdt = sqrt((double)Dt);
+    return Di == 0 || Dt == 0 ? 0.0 : (double)N / (sdi * sdt);
+}
+
+__global__ __launch_bounds__(256) void k_patch_locate(const LocateArgs c) {
+    __shared__ __attribute__((aligned(16))) uint8_t arena[kLocArena];
+    __shared__ uint32_t red[4][2];
+    uint8_t* const WIN = arena;
+    int32_t* const SI = (int32_t*)(arena + kLocSOff);
+    int32_t* const SII = SI + kLocMaxOff;
+    uint8_t* const U = arena + kLocUOff;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const LocateJob& J = c.jobs[blockIdx.x];
+    const int w = __builtin_amdgcn_readfirstlane(J.w), h = __builtin_amdgcn_readfirstlane(J.h);
+    const int rx = __builtin_amdgcn_readfirstlane(J.rx), ry = __builtin_amdgcn_readfirstlane(J.ry);
+    const int fx = __builtin_amdgcn_readfirstlane(J.x), fy = __builtin_amdgcn_readfirstlane(J.y);
+    const int bands = __builtin_amdgcn_readfirstlane(J.bands);
+    const int ww = w + 2 * rx, wh = h + 2 * ry, nx = 2 * rx + 1, ny = 2 * ry + 1, noff = nx * ny;
+    // ---- 1. the window into WIN
+    {
+        int32_t* const tab = (int32_t*)U;
+        uint8_t* const FT = U + 4 * kPatchTabWords;
+        PatchArgs a{};
+        a.jobs = &J.p;
+        a.njobs = 1;
+        a.level0 = c.level0;
+        a.img_stride = c.img_stride;
+        a.sw = c.sw; a.sh = c.sh; a.sp = c.sp;
+        a.pw = ww; a.ph = wh;
+        const int r = tid >> 4, gx = (tid & 15) * 4;
+        const int ntx = (ww + kPatchTw - 1) / kPatchTw, nty = (wh + kPatchTh - 1) / kPatchTh;
+#pragma unroll 1
+        for (int t = 0; t < ntx * nty; ++t) {
+            const int ty = t / ntx, tx = t - ty * ntx;
+            const int x = tx * kPatchTw + gx, y = ty * kPatchTh + r;
+            const int left = ww - x;
+            const int nu = y >= wh || left <= 0 ? 0 : (left < 4 ? left : 4);
+            const PatchTile T = patch_tile_stage_at(a, tab, FT, tid, 0, tx, ty);
+            const uint32_t word = patch_sample4(a, T, tab, FT, r, gx, nu);
+            if (nu > 0) *(uint32_t*)(WIN + y * kLocWP + x) = word;   // x + 3 <= 163: inside the row's pitch
+            __syncthreads();   // the next tile's tables and footprint overwrite what a slower wave still samples
+        }
+    }
+    // ---- 2. S_i, then S_ii: the last barrier above has the window complete and the staging region free
+    {
+        int32_t* const C = (int32_t*)U;
+        const int cp = ww | 1;
+#pragma unroll 1
+        for (int kind = 0; kind < 2; ++kind) {
+            int32_t* const S = kind ? SII : SI;
+            if (tid < ww) {
+                const uint8_t* col = WIN + tid;
+                int32_t s = 0;
+                for (int b = 0; b < h; ++b) {
+                    const int v = col[b * kLocWP];
+                    s += kind ? v * v : v;
+                }
+                C[tid] = s;
+                for (int j = 1; j < ny; ++j) {
+                    const int vin = col[(h + j - 1) * kLocWP], vout = col[(j - 1) * kLocWP];
+                    s += kind ? vin * vin - vout * vout : vin - vout;
+                    C[j * cp + tid] = s;
+                }
+            }
+            __syncthreads();
+            if (tid < ny) {
+                const int32_t* row = C + tid * cp;
+                int32_t s = 0;
+                for (int a = 0; a < w; ++a) s += row[a];
+                S[tid * nx] = s;
+                for (int i = 1; i < nx; ++i) {
+                    s += row[w + i - 1] - row[i - 1];
+                    S[tid * nx + i] = s;
+                }
+            }
+            __syncthreads();   // C is written again (the second kind, then T)
+        }
+    }
+    // ---- 3. the template region into T, S_it cleared
+    uint32_t* const T32 = (uint32_t*)U;
+    uint32_t* const SIT = (uint32_t*)(U + kLocTBytes);
+    const int tpw = ((w + 15) & ~15) >> 2;   // dwords per row of T
+    {
+        uint32_t st = 0, stt = 0;
+        for (int i = tid; i < h * tpw; i += 256) {
+            const int b = i / tpw, a = 4 * (i - b * tpw);
+            const int left = w - a;
+            const int nu = left <= 0 ? 0 : (left < 4 ? left : 4);
+            uint32_t tw = 0;
+            if (nu > 0) {
+                // the rectangle lies inside the template and the slab's pitch is a multiple of 64: the first dword is
+                // inside the row, the second is read only where it is too
+                const int tx = fx + a;
+                const uint8_t* trow = c.tmpl + (size_t)(fy + b) * c.tp;
+                const int c0 = tx & ~3;
+                const uint32_t lo = *(const uint32_t*)(trow + c0);
+                const uint32_t hi = (tx & 3) && c0 + 4 < c.tp ? *(const uint32_t*)(trow + c0 + 4) : 0u;
+                tw = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)tx);
+                if (nu < 4) tw &= (1u << (8 * nu)) - 1u;
+            }
+            T32[i] = tw;
+            st = __builtin_amdgcn_udot4(tw, 0x01010101u, st, false);
+            stt = __builtin_amdgcn_udot4(tw, tw, stt, false);
+        }
+        for (int o = tid; o < noff; o += 256) SIT[o] = 0;
+        // a lane holds at most 16 dwords: 16 320 and 4 161 600; a wave 64 times that, the workgroup below 2^31
+        st = wave_fold<false>(st);
+        stt = wave_fold<false>(stt);
+        if (lane == 0) { red[wave][0] = st; red[wave][1] = stt; }
+    }
+    __syncthreads();
+    const int64_t sum_t = (int64_t)(red[0][0] + red[1][0] + red[2][0] + red[3][0]);
+    const int64_t sum_tt = (int64_t)(red[0][1] + red[1][1] + red[2][1] + red[3][1]);
+    // ---- 4. S_it
+    {
+        const int rows = (h + bands - 1) / bands;
+        const int units = noff * bands;
+#pragma unroll 1
+        for (int unit = tid; unit < units; unit += 256) {
+            const int band = unit / noff, off = unit - band * noff;
+            const int j = off / nx, i = off - j * nx;
+            const int b0 = band * rows, b1 = b0 + rows < h ? b0 + rows : h;
+            if (b0 >= b1) continue;
+            const uint32_t sh = (uint32_t)(i & 3);
+            const uint32_t* wp = (const uint32_t*)(WIN + (b0 + j) * kLocWP + (i & ~3));
+            const uint32_t* tq = T32 + b0 * tpw;
+            uint32_t acc = 0;
+#pragma unroll 1
+            for (int b = b0; b < b1; ++b) {
+                uint32_t lo = wp[0];
+                for (int k = 0; k < tpw; k += 4) {   // the last window dword read ends at byte 32 + 128 + 3 of the row
+                    const uint4 t = *(const uint4*)(tq + k);
+                    const uint32_t h1 = wp[k + 1], h2 = wp[k + 2], h3 = wp[k + 3], h4 = wp[k + 4];
+                    acc = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(h1, lo, sh), t.x, acc, false);
+                    acc = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(h2, h1, sh), t.y, acc, false);
+                    acc = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(h3, h2, sh), t.z, acc, false);
+                    acc = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(h4, h3, sh), t.w, acc, false);
+                    lo = h4;
+                }
+                wp += kLocWP / 4;
+                tq += tpw;
+            }
+            atomicAdd(SIT + off, acc);
+        }
+    }
+    __syncthreads();   // S_it complete; T is free
+    // ---- 5. z and the peak
+    double* const bz = (double*)U;
+    int32_t* const bo = (int32_t*)(U + 2048);
+    int32_t* const bd = (int32_t*)(U + 3072);
+    const int64_t n = (int64_t)w * h;
+    {
+        double z0 = -4.0;   // below every z
+        int o0 = INT_MAX, d0 = INT_MAX;
+        for (int off = tid; off < noff; off += 256) {
+            const double z = locate_zncc_dev(n, SI[off], SII[off], sum_t, sum_tt, (int64_t)SIT[off]);
+            const int j = off / nx, i = off - j * nx;
+            const int d = (i - rx) * (i - rx) + (j - ry) * (j - ry);
+            if (z > z0 || (z == z0 && d < d0)) { z0 = z; o0 = off; d0 = d; }   // off rises: the earlier wins a full tie
+        }
+        bz[tid] = z0; bo[tid] = o0; bd[tid] = d0;
+    }
+#pragma unroll 1
+    for (int s = 128; s >= 1; s >>= 1) {
+        __syncthreads();
+        if (tid < s) {
+            const double z1 = bz[tid], z2 = bz[tid + s];
+            const int o1 = bo[tid], o2 = bo[tid + s], d1 = bd[tid], d2 = bd[tid + s];
+            if (z2 > z1 || (z2 == z1 && (d2 < d1 || (d2 == d1 && o2 < o1)))) { bz[tid] = z2; bo[tid] = o2; bd[tid] = d2; }
+        }
+    }
+    __syncthreads();
+    // ---- 6. the record and the maps
+    const int P = bo[0], pj = P / nx, pi = P - pj * nx;
+    if (tid < kLocateWords) {
+        int32_t v = 0;
+        if (tid == 0) v = pi - rx;
+        else if (tid == 1) v = pj - ry;
+        else if (tid == 4) v = (int32_t)n;
+        else if (tid == 6) v = (int32_t)sum_t;
+        else if (tid == 8) v = (int32_t)sum_tt;
+        else if (tid >= 10 && tid < 37) {
+            const int kind = (tid - 10) / 9, e = (tid - 10) - kind * 9;
+            const int qj = pj + e / 3 - 1, qi = pi + e % 3 - 1;
+            if (qi >= 0 && qi < nx && qj >= 0 && qj < ny) {
+                const int o = qj * nx + qi;
+                v = kind == 0 ? SI[o] : (kind == 1 ? SII[o] : (int32_t)SIT[o]);
+            }
+        } else if (tid >= 37) {
+            const int o = ry * nx + rx;
+            v = tid == 37 ? SI[o] : (tid == 38 ? SII[o] : (int32_t)SIT[o]);
+        }
+        // words 2, 3 (flags, reserved) and the upper halves 5, 7, 9 of the three 64-bit fields (all below 2^31) are 0
+        c.raw[(size_t)blockIdx.x * kLocateWords + tid] = v;
+    }
+    if (c.maps) {
+        int32_t* mp = c.maps + (size_t)blockIdx.x * 3 * (size_t)c.map_stride;
+        for (int idx = tid; idx < 3 * c.map_stride; idx += 256) {
+            const int kind = idx / c.map_stride, o = idx - kind * c.map_stride;
+            int32_t v = 0;
+            if (o < noff) v = kind == 0 ? SI[o] : (kind == 1 ? SII[o] : (int32_t)SIT[o]);
+            mp[idx] = v;
+        }
+    }
+}
+
+bool launch_patch_locate(const LocateArgs& a, hipStream_t st) {
+    if (a.njobs <= 0) return true;
+    if (!a.raw || !a.tmpl || (a.maps && a.map_stride < 1)) return false;
+    hipLaunchKernelGGL(k_patch_locate, dim3((unsigned)a.njobs), dim3(256), 0, st, a);
+    return true;
+}
+
 // ============================================================================================== variation model
 // k_model_accum (fpm_model_train_last / fpm_model_train_at): the per-pixel sum and sum of squares
 // of the patches of a job table, none of them written.  k_patch_warp's tile and 4 pixels per lane; a workgroup owns one

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -581,6 +581,86 @@ def caliper_derive(cal, lt_k, angle_k: float, raw) -> np.ndarray:
     if rc != L.FPM_OK:
         raise ValueError(f"fpm_caliper_derive failed with {rc}")
     return out
+
+
+# -- sub-pattern locators (fpm_locate_host / fpm_locate_derive / fpm_last_locate / fpm_locate_at) ---------------------
+# fpm_feature, fpm_locate_raw and fpm_locate_result, field for field
+FEATURE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Feature._fields_], align=True)
+LOCATE_RAW_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.LocateRaw._fields_], align=True)
+LOCATE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.LocateResult._fields_], align=True)
+assert FEATURE_DTYPE.itemsize == C.sizeof(L.Feature) == 32 and LOCATE_RAW_DTYPE.itemsize == C.sizeof(L.LocateRaw) == 160
+assert LOCATE_DTYPE.itemsize == C.sizeof(L.LocateResult) == 80
+
+
+def feature(x: int, y: int, w: int, h: int, rx: int = 8, ry: Optional[int] = None) -> np.ndarray:
+    """One feature as a FEATURE_DTYPE record: the region (x, y, w, h) of the template to find again on a hit, w and h
+    1 .. 128, and the search radii rx, ry (``ry=None``: rx) in pixels, 0 .. 16.  Whether the region lies inside the
+    learned template is checked by the call that uses it.  Raises ValueError outside the ranges.  Pure: no device."""
+    ry = rx if ry is None else ry
+    vals = [int(v) for v in (x, y, w, h, rx, ry)]
+    if vals != [x, y, w, h, rx, ry]:
+        raise ValueError("x, y, w, h, rx and ry must be whole numbers")
+    x, y, w, h, rx, ry = vals
+    if not (1 <= w <= L.LOCATE_MAX_SIDE and 1 <= h <= L.LOCATE_MAX_SIDE):
+        raise ValueError(f"w {w} and h {h} must be 1 .. {L.LOCATE_MAX_SIDE}")
+    if not (0 <= rx <= L.LOCATE_MAX_RADIUS and 0 <= ry <= L.LOCATE_MAX_RADIUS):
+        raise ValueError(f"rx {rx} and ry {ry} must be 0 .. {L.LOCATE_MAX_RADIUS}")
+    if x < 0 or y < 0 or abs(x) > 1 << 20 or abs(y) > 1 << 20:
+        raise ValueError("x and y must not be negative")
+    rec = np.zeros((), FEATURE_DTYPE)
+    rec["x"], rec["y"], rec["w"], rec["h"], rec["rx"], rec["ry"] = x, y, w, h, rx, ry
+    return rec
+
+
+def _features(feats) -> np.ndarray:
+    """A contiguous FEATURE_DTYPE array of one or more features (records of feature(), or such an array)."""
+    if isinstance(feats, np.ndarray) and feats.dtype == FEATURE_DTYPE:
+        arr = np.ascontiguousarray(feats).reshape(-1)
+    else:
+        arr = np.array([np.asarray(f, FEATURE_DTYPE).reshape(()) for f in feats], FEATURE_DTYPE).reshape(-1)
+    if not 1 <= arr.size <= L.LOCATE_MAX_FEATURES:
+        raise ValueError(f"1 .. {L.LOCATE_MAX_FEATURES} features expected, got {arr.size}")
+    return arr
+
+
+def locate_host(window, tmpl, rx: int, ry: int, maps: bool = False):
+    """fpm_locate_host: the template region ``tmpl`` (uint8, h x w) searched in ``window`` (uint8, (h + 2 ry) x (w + 2
+    rx)) by the rules of include/fpm.h.  Returns the LOCATE_RAW_DTYPE record; with ``maps=True`` also the int32 sums
+    (3, 2 ry + 1, 2 rx + 1): S_i, S_ii, S_it per offset.  Host only (no device)."""
+    t = np.ascontiguousarray(tmpl, np.uint8)
+    win = np.ascontiguousarray(window, np.uint8)
+    if t.ndim != 2 or win.ndim != 2 or int(rx) != rx or int(ry) != ry:
+        raise ValueError("two uint8 images and whole radii expected")
+    h, w = t.shape
+    rx, ry = int(rx), int(ry)
+    if win.shape != (h + 2 * ry, w + 2 * rx):
+        raise ValueError(f"window {win.shape} must be {(h + 2 * ry, w + 2 * rx)}")
+    raw = np.zeros(1, LOCATE_RAW_DTYPE)
+    m = np.zeros((3, 2 * max(ry, 0) + 1, 2 * max(rx, 0) + 1), np.int32) if maps else None
+    rc = L.load().fpm_locate_host(win.ctypes.data_as(C.POINTER(C.c_uint8)), win.strides[0],
+                                  t.ctypes.data_as(C.POINTER(C.c_uint8)), t.strides[0], w, h, rx, ry,
+                                  raw.ctypes.data_as(C.POINTER(L.LocateRaw)),
+                                  m.ctypes.data_as(C.POINTER(C.c_int32)) if maps else None)
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_locate_host failed with {rc}")
+    return (raw[0], m) if maps else raw[0]
+
+
+def locate_derive(feat, lt, angle: float, raw) -> np.ndarray:
+    """fpm_locate_derive: one raw record ``raw`` (LOCATE_RAW_DTYPE) of feature ``feat`` on a hit at ptLT ``lt`` (as
+    f32) and ``angle`` (degrees) as a LOCATE_DTYPE record: score, score_nominal, the sub-pixel displacement (ox, oy),
+    the found centre in template (tx, ty) and source (sx, sy) coordinates, and flags.  Host only (no device)."""
+    f = _features([feat] if not (isinstance(feat, np.ndarray) and feat.ndim >= 1) else feat)
+    r = np.ascontiguousarray(raw, LOCATE_RAW_DTYPE).reshape(-1)
+    if f.size != 1 or r.size != 1:
+        raise ValueError("one feature and one raw record expected")
+    out = np.zeros(1, LOCATE_DTYPE)
+    rc = L.load().fpm_locate_derive(f.ctypes.data_as(C.POINTER(L.Feature)), float(np.float32(lt[0])),
+                                    float(np.float32(lt[1])), float(angle), r.ctypes.data_as(C.POINTER(L.LocateRaw)),
+                                    out.ctypes.data_as(C.POINTER(L.LocateResult)))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_locate_derive failed with {rc}")
+    return out[0]
 
 
 # -- gray-value tools (fpm_hist_derive / fpm_last_histogram / fpm_last_segment ..): the hit's own gray values ---------
@@ -1774,6 +1854,76 @@ class TemplateMatcher:
         ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
         if self._lib.fpm_gray_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
             raise ValueError(f"gray_profile({which!r}) failed")
+        return ms.value, n.value, b.value
+
+    # -- sub-pattern locators: template regions found again on every hit (fpm_last_locate / fpm_locate_at) ------------
+    @staticmethod
+    def _locate_buffers(n, feats, raw, maps):
+        K = len(feats)
+        if n * K > L.LOCATE_MAX_JOBS:
+            raise ValueError(f"{n} hits x {K} features above {L.LOCATE_MAX_JOBS}")
+        res = np.zeros((n, K), LOCATE_DTYPE)
+        rw = np.zeros((n, K), LOCATE_RAW_DTYPE) if raw else None
+        stride = int(((2 * feats["rx"] + 1) * (2 * feats["ry"] + 1)).max())
+        mp = np.zeros((n, K, 3, stride), np.int32) if maps else None
+        return res, rw, mp, stride
+
+    @staticmethod
+    def _locate_result(res, rw, mp, raw, maps):
+        out = (res,) + ((rw,) if raw else ()) + ((mp,) if maps else ())
+        return out if len(out) > 1 else res
+
+    def last_locate(self, features, source: int = 0, raw: bool = False, maps: bool = False):
+        """The features ``features`` (records of feature()) found again on every result of the last search, where the
+        pixels are: one launch of k_patch_locate, no image crosses the host (fpm_last_locate).  Each feature's template
+        region is correlated (the search's own normalized correlation) with the hit's pixels at every offset of +-rx,
+        +-ry around its nominal place.  Returns a LOCATE_DTYPE array (n_hits, K): the peak (dx, dy), score and
+        score_nominal (the score at offset 0), the sub-pixel displacement (ox, oy) in template pixels, the found centre
+        in template (tx, ty) and source (sx, sy) coordinates, and flags (L.LOCATE_EDGE_X / _EDGE_Y: the peak lies on
+        the search range's border, no sub-pixel step on that axis; L.LOCATE_FLAT: no contrast, score 0 at nominal;
+        L.LOCATE_OUTSIDE: the window leaves the source, border zeros are in it).  Hits come in result order of
+        ``source`` (``source=-1``: all sources), at the raw poses, or the aligned ones after align_last(adopt=True).
+        ``raw=True`` adds the LOCATE_RAW_DTYPE records, ``maps=True`` the int32 sums (n_hits, K, 3, the largest offset
+        count), offsets row-major, zero behind a feature's own count.  A template mask is not honoured."""
+        arr = _features(features)
+        pf = arr.ctypes.data_as(C.POINTER(L.Feature))
+        n = C.c_int32()
+        rc = self._lib.fpm_last_locate(self._ctx, int(source), pf, len(arr), None, None, None, 0, 0, C.byref(n))
+        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
+            self._patch_fail(rc, "last_locate")
+        res, rw, mp, stride = self._locate_buffers(n.value, arr, raw, maps)
+        if n.value:
+            rc = self._lib.fpm_last_locate(self._ctx, int(source), pf, len(arr),
+                                           res.ctypes.data_as(C.POINTER(L.LocateResult)),
+                                           rw.ctypes.data_as(C.POINTER(L.LocateRaw)) if raw else None,
+                                           mp.ctypes.data_as(C.POINTER(C.c_int32)) if maps else None, stride, n.value,
+                                           C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, "last_locate")
+        return self._locate_result(res, rw, mp, raw, maps)
+
+    def locate_at(self, src_index, lts, angles, features, raw: bool = False, maps: bool = False):
+        """last_locate at poses the caller supplies, on the staged sources (fpm_locate_at); poses as patches_at.  Needs
+        staged sources and a template, not a search; nothing in the matcher changes."""
+        idx, lt, ang = patch_poses(src_index, lts, angles)
+        arr = _features(features)
+        res, rw, mp, stride = self._locate_buffers(len(idx), arr, raw, maps)
+        rc = self._lib.fpm_locate_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
+                                     len(idx), arr.ctypes.data_as(C.POINTER(L.Feature)), len(arr),
+                                     res.ctypes.data_as(C.POINTER(L.LocateResult)),
+                                     rw.ctypes.data_as(C.POINTER(L.LocateRaw)) if raw else None,
+                                     mp.ctypes.data_as(C.POINTER(C.c_int32)) if maps else None, stride)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "locate_at")
+        return self._locate_result(res, rw, mp, raw, maps)
+
+    def locate_profile(self):
+        """``(ms, launches, bytes)`` of k_patch_locate, collected under profile(True) and cleared by profile_reset
+        (fpm_locate_profile)."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if self._lib.fpm_locate_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError("fpm_locate_profile failed")
         return ms.value, n.value, b.value
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------

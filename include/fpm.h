@@ -785,8 +785,9 @@ int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64
  *   fpm_model_train_last / fpm_model_train_at: the planes accumulate EVERY pixel of the rectangle, masked or not -- the
  *     mask applies when inspecting, so it may be drawn or changed after training.  Only the FPM_COMPARE_NORMALIZE table
  *     is built from the masked sums.
- * Who does not: the search, fpm_last_patches* and fpm_patches_at, the calipers, the fpm_learn_* entries, fpm_model_sums
- * and fpm_model_images, fpm_op_blobs and fpm_blobs_host.
+ * Who does not: the search, fpm_last_patches* and fpm_patches_at, the calipers, fpm_last_locate and fpm_locate_at (the
+ * "sub-pattern locators" below), the fpm_learn_* entries, fpm_model_sums and fpm_model_images, fpm_op_blobs and
+ * fpm_blobs_host.
  * Launches.  Setting a mask runs k_mask_stage once (normalisation and the count, in integers).  A masked call launches
  * the MASK forms of k_patch_compare, k_patch_align and k_model_inspect: as many launches as the unmasked call, counted
  * under the same profile entries, the mask bytes read added to `bytes`.  Exact integers throughout: the results do not
@@ -904,6 +905,114 @@ int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles);
  * fpm_caliper_profile's (no FPM_K_* index).  which: 0 = k_patch_hist, 1 = k_patch_threshold; bytes = source pixels
  * read (+ mask bytes read) + histogram words or e pixels written. */
 int fpm_gray_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes);
+
+/* --- sub-pattern locators: find template regions on every hit (no reference equivalent) ------------------
+ * The tools above treat a hit as one rigid copy of the taught image.  A locator asks where on this hit a given piece of
+ * the taught image is, and how well it matches there: a label on a cap, a print on a package, a fiducial beside a pad,
+ * each with a placement error of its own.  It is the project's own operation, a normalized correlation, at its smallest
+ * scale: the piece is found again inside a small window around its nominal place.
+ * Feature.  fpm_feature, 32 bytes, no padding.  (x, y, w, h) is a rectangle in template coordinates, inside the learned
+ * template; w and h are 1 .. 128; rx and ry are the search radii in patch pixels, 0 .. 16; reserved is 0.  These caps
+ * keep every sum in int32 (sum I T <= 65025 * 16384 = 1,065,369,600 < 2^31) and the window, at most 160 x 160 bytes,
+ * and the template region, at most 16 KiB, inside one workgroup's LDS.
+ * Window pixels.  With ww = w + 2 rx and wh = h + 2 ry, I(u, v) is pixel (u, v) of the patch fpm_patches_at gives for
+ * the rectangle (x - rx, y - ry, ww, wh) at the hit's pose: same matrix, same fixed-point bilinear arithmetic, border 0,
+ * the inverted plane under bitwise_not.  The window may reach outside the template and outside the source.  T(a, b) is
+ * template level 0 at (x + a, y + b).
+ * Sums per offset.  For dx = -rx .. rx and dy = -ry .. ry, exact integers:
+ *     S_i(dx, dy)  = sum over a < w, b < h of I(a + rx + dx, b + ry + dy)
+ *     S_ii(dx, dy) = the same sum of squares;  S_it(dx, dy) = the same sum of products with T(a, b)
+ * n = w h, sum_t and sum_tt are constant per feature.
+ * Score.  z(dx, dy) is fpm_compare_derive's zncc of (n, S_i, S_ii, sum_t, sum_tt, S_it): the expression, the order and
+ * the 0 when Di == 0 or Dt == 0 are the same.  Host and device both evaluate it in f64; the device build is
+ * -ffp-contract=off with correctly rounded sqrt and /.
+ * Peak.  The offset with the largest z; ties go to the smallest dx^2 + dy^2, then the smallest dy, then the smallest dx.
+ * The result is fully determined and does not depend on any schedule; a flat region answers "at nominal, score 0".
+ * Raw record.  The device writes fpm_locate_raw, 160 bytes, no padding.  The three arrays hold the sums of the 3 x 3
+ * neighbourhood of the peak: entry (j + 1) * 3 + (i + 1) is offset (dx + i, dy + j), zero where that offset lies
+ * outside the search range.  c_i, c_ii, c_it are the three sums at offset (0, 0).  flags is 0 from the device and from
+ * fpm_locate_host; the entries set FPM_LOCATE_OUTSIDE there, on the host (below), and nothing else.
+ * Maps.  maps may be NULL.  It receives all three sums of every offset as int32 [job][3][map_stride], job = hit *
+ * n_features + feature; map_stride is at least the largest (2 rx + 1)(2 ry + 1) of the call.  Offsets are row-major, dy
+ * rising then dx.  Entries behind a feature's count are 0.
+ * Derivation (fpm_locate_derive; host only, no context).  f64, integers combined first, no fused multiply-add.  It fills
+ * fpm_locate_result, 80 bytes, no padding:
+ *     score = z at the peak;  score_nominal = z(0, 0)
+ *     per axis, when the peak is not on the search range's border on that axis, with z-, z0, z+ along it:
+ *       den = (z- - z0) + (z+ - z0);  delta = 0.5 (z- - z+) / den when den < 0, else 0  (so |delta| <= 0.5)
+ *     on the border, and for radius 0, delta = 0 and FPM_LOCATE_EDGE_X / FPM_LOCATE_EDGE_Y is set
+ *     ox = dx + delta_x, oy = dy + delta_y: the displacement from nominal in template pixels
+ *     tx = (x + (w - 1) / 2) + ox, ty = (y + (h - 1) / 2) + oy
+ *     (sx, sy) = lt + L (tx, ty): L the matrix of the hit's angle, lt the f32 pose widened to f64 -- the convention of
+ *       fpm_caliper_derive and fpm_align_update, with glibc cos and sin:
+ *       sx = (double)lt_x + (tx c - ty s), sy = (double)lt_y + (tx s + ty c), c, s = cos, sin of angle * pi / 180
+ *     FPM_LOCATE_FLAT is set when Dt == 0 or the peak's Di == 0
+ *     FPM_LOCATE_OUTSIDE is copied from the raw record's flags.  The entries set it there by the calipers' four-corner
+ *       rule on the window's corner pixels (0, 0), (ww - 1, 0), (0, wh - 1), (ww - 1, wh - 1), on the host, in f64,
+ *       through the matrix the sampler takes: border zeros are in the window.
+ *   A record that no search can have produced (n != w h, |dx| > rx, |dy| > ry) is FPM_E_INVALID_ARG, *out untouched.
+ * Host form.  fpm_locate_host applies the same rules to a caller's u8 window (ww x wh) and template region (w x h): the
+ * reference form, as fpm_blobs_host and fpm_caliper_edges_host are for their blocks.  maps there is [3][(2 rx + 1)(2 ry
+ * + 1)].
+ * Limits and errors.  n_features is 1 .. 64; hits * n_features <= 65536.  A bad rectangle, size or radius, a non-zero
+ * reserved, a null output, map_stride below the largest offset count (with maps), or a pose beyond the samplers' 2^20
+ * range: FPM_E_INVALID_ARG, nothing launched, nothing written.  FPM_E_NOT_LEARNED without a template.  State, source,
+ * cap (hits), *n and the count-only call are fpm_last_compare's for fpm_last_locate, which samples at the raw poses, or
+ * at the adopted ones after FPM_ALIGN_ADOPT; pose and state rules are fpm_compare_at's for fpm_locate_at.  The calls
+ * change no search state: results, poses, candidates, staged sources, template, model and mask stay as they were.
+ * Mask.  A template mask is not honoured (the block above).
+ * Launches.  One k_patch_locate per call over all (hit, feature) jobs, never part of a search or of a captured graph;
+ * the records (and maps) come back through a pinned buffer of the context, are checked, then copied to the caller.
+ * Out of scope: masked correlation, a rotation or scale search of the feature, a second-best peak, results left in
+ * device memory, features learned from anything but the current template.
+ * Additive entries: FPM_ABI_VERSION and FPM_K_COUNT are unchanged. */
+typedef struct fpm_feature {
+    int32_t x, y, w, h;          /* the region in template coordinates, inside the template; w, h 1 .. 128 */
+    int32_t rx, ry;              /* search radii in patch pixels, 0 .. 16                                 */
+    int32_t reserved[2];         /* 0 */
+} fpm_feature;
+typedef struct fpm_locate_raw {
+    int32_t dx, dy;              /* the peak's offset                                                     */
+    int32_t flags;               /* 0 from the device; FPM_LOCATE_OUTSIDE set by the entries, on the host */
+    int32_t reserved;            /* 0 */
+    int64_t n, sum_t, sum_tt;    /* w h, sum T, sum T^2                                                   */
+    int32_t s_i[9], s_ii[9], s_it[9];   /* the sums of the peak's 3 x 3 neighbourhood                     */
+    int32_t c_i, c_ii, c_it;     /* the sums at offset (0, 0)                                             */
+} fpm_locate_raw;
+typedef struct fpm_locate_result {
+    int32_t dx, dy;
+    int32_t flags;               /* FPM_LOCATE_EDGE_X | _EDGE_Y | _FLAT | _OUTSIDE                        */
+    int32_t reserved;            /* 0 */
+    double score, score_nominal;
+    double ox, oy;               /* displacement from nominal, template pixels                            */
+    double tx, ty;               /* the found centre in template coordinates                              */
+    double sx, sy;               /* and in source coordinates                                             */
+} fpm_locate_result;
+#define FPM_LOCATE_EDGE_X 1
+#define FPM_LOCATE_EDGE_Y 2
+#define FPM_LOCATE_FLAT 4
+#define FPM_LOCATE_OUTSIDE 8
+#define FPM_LOCATE_MAX_SIDE 128          /* w, h */
+#define FPM_LOCATE_MAX_RADIUS 16         /* rx, ry */
+#define FPM_LOCATE_MAX_FEATURES 64       /* n_features */
+#define FPM_LOCATE_MAX_JOBS 65536        /* hits * n_features */
+
+/* host only, no context: sums, peak and raw record of one window (ww x wh) against one template region (w x h) */
+int fpm_locate_host(const uint8_t* window, size_t window_stride, const uint8_t* tmpl, size_t tmpl_stride, int32_t w,
+                    int32_t h, int32_t rx, int32_t ry, fpm_locate_raw* raw, int32_t* maps /* may be NULL */);
+/* host only, no context: one raw record of feature feat on a hit at (lt, angle) into *out, by the rule above */
+int fpm_locate_derive(const fpm_feature* feat, float lt_x, float lt_y, double angle, const fpm_locate_raw* raw,
+                      fpm_locate_result* out);
+/* the features at caller-supplied poses on the staged sources; results, raw: [pose][feature] */
+int fpm_locate_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                  const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results, fpm_locate_raw* raw /* may be NULL */,
+                  int32_t* maps /* may be NULL */, int32_t map_stride);
+/* the same over the hits of the last search in result order (source = -1: of all sources) */
+int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results,
+                    fpm_locate_raw* raw, int32_t* maps, int32_t map_stride, int32_t cap /* hits */, int32_t* n);
+/* Timing of k_patch_locate, collected under fpm_profile_enable and cleared by fpm_profile_reset as fpm_caliper_profile's
+ * (no FPM_K_* index).  bytes = window pixels sampled + template pixels read + records and maps written. */
+int fpm_locate_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
 
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------

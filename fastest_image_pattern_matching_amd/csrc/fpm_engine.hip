@@ -23,6 +23,7 @@
 #include <new>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fpm.h"
@@ -320,6 +321,16 @@ void prof_collect(fpm_ctx* ctx) {
         }
         p.used = 0;
     }
+}
+
+// the fpm_*_profile getters: slot `first + which` of a tool whose slots are first .. first + last_which
+int kprof_out(const fpm_ctx* ctx, int first, int32_t which, int32_t last_which, double* ms, int64_t* launches, int64_t* bytes) {
+    if (!ctx || which < 0 || which > last_which || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
+    const KProf& p = ctx->kp[first + which];
+    *ms = p.ms;
+    *launches = p.launches;
+    *bytes = p.bytes;
+    return FPM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1959,6 +1970,65 @@ int last_poses(fpm_ctx* ctx, int source, std::vector<PatchPose>& poses) {
     return FPM_OK;
 }
 
+// Where the poses of a per-hit call come from: the last search's results of `source`, with the
+// caller's capacity `cap` and count `*n` (fpm_last_X), or the caller's own poses (fpm_X_at).
+struct HitQuery {
+    bool from_last = false;
+    int32_t source = 0, cap = 0;
+    int32_t* n = nullptr;
+    const int32_t* src_index = nullptr;
+    const float* lt = nullptr;
+    const double* angles = nullptr;
+    int32_t n_poses = 0;
+
+    static HitQuery last(int32_t source, int32_t cap, int32_t* n) {
+        HitQuery q;
+        q.from_last = true; q.source = source; q.cap = cap; q.n = n;
+        return q;
+    }
+    static HitQuery at(const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses) {
+        HitQuery q;
+        q.src_index = src_index; q.lt = lt; q.angles = angles; q.n_poses = n_poses;
+        return q;
+    }
+    bool need_search() const { return from_last; }   // for patch_state
+
+    // The call's own pointers, before anything else is looked at; a last call's count starts at 0.
+    int check(fpm_ctx* ctx) const {
+        if (!ctx || (from_last && !n)) return FPM_E_INVALID_ARG;
+        if (from_last) { *n = 0; return FPM_OK; }
+        if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+        return FPM_OK;
+    }
+
+    // The poses.  A last call also gets its count and the capacity check, under the tool's own text.  FPM_OK with
+    // `poses` empty: the caller has nothing to do and returns FPM_OK.
+    int resolve(fpm_ctx* ctx, const char* too_small, std::vector<PatchPose>& poses) const {
+        if (!from_last) {
+            poses.resize((size_t)n_poses);
+            for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
+            return FPM_OK;
+        }
+        const int rc = last_poses(ctx, source, poses);
+        if (rc != FPM_OK) return rc;
+        *n = (int32_t)poses.size();
+        if ((int)poses.size() > cap) { ctx->err = too_small; return FPM_E_CAPACITY; }
+        return FPM_OK;
+    }
+};
+
+const char* kPatchCap = "patch buffer too small";
+using RectRule = int (*)(fpm_ctx*, const fpm_patch_rect*, fpm_patch_rect*);   // patch_rect, compare_rect, align_rect, model_rect
+
+// State, rectangle and poses of a call with one rectangle, in this order; FPM_OK with poses empty = nothing to do.
+int hits_begin(fpm_ctx* ctx, const HitQuery& q, RectRule rule, const fpm_patch_rect* rect, fpm_patch_rect* r,
+               std::vector<PatchPose>& poses) {
+    int rc = patch_state(ctx, q.need_search());
+    if (rc == FPM_OK) rc = rule(ctx, rect, r);
+    if (rc == FPM_OK) rc = q.resolve(ctx, kPatchCap, poses);
+    return rc;
+}
+
 int check_patch_out(fpm_ctx* ctx, const void* out, const fpm_patch_rect& r, size_t row_stride, size_t patch_stride) {
     if (!out) { ctx->err = "null patch buffer"; return FPM_E_INVALID_ARG; }
     if (row_stride < (size_t)r.w || row_stride > (size_t)INT32_MAX || patch_stride / (size_t)r.h < row_stride) {
@@ -1992,6 +2062,61 @@ int patch_pose_matrix(fpm_ctx* ctx, const fpm_patch_rect& r, const PatchPose& p,
 
 size_t patch_tab_bytes(int n) { return round_up(std::max(sizeof(PatchJob), sizeof(WarpJob)) * (size_t)n, (size_t)256); }
 
+// ---- the job table of a per-hit tool: h_patchtab filled on the host, sent to d_patchtab ----
+// begin: the pinned table is free again (an earlier call's copy out of it is long done as a rule), both buffers hold
+// `bytes`; *jobs = the pinned table.
+template <class Job>
+int tab_begin(fpm_ctx* ctx, size_t bytes, Job** jobs) {
+    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));
+    HIP_TRY(ctx->h_patchtab.ensure(bytes));
+    HIP_TRY(ctx->d_patchtab.ensure(bytes));
+    *jobs = ctx->h_patchtab.as<Job>();
+    return FPM_OK;
+}
+
+// head: pose i of the call checked (patch_pose_matrix), its sampler matrix, output offset and source into a job's head
+int tab_head(fpm_ctx* ctx, PatchJob& j, const fpm_patch_rect& r, const PatchPose& p, int i, int64_t out_off, double* fwd = nullptr) {
+    const int rc = patch_pose_matrix(ctx, r, p, i, fwd, j.M);
+    if (rc != FPM_OK) return rc;
+    j.out_off = out_off;
+    j.src = p.src;
+    j.pad = 0;
+    return FPM_OK;
+}
+
+// send: the first `bytes` of the pinned table to the device, on the context's stream (no wait)
+int tab_send(fpm_ctx* ctx, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
+    return FPM_OK;
+}
+
+// outside: border zeros in a w x h region -- a corner sample outside the source, through the matrix the sampler takes
+bool corners_outside(const fpm_ctx* ctx, const double M[6], int w, int h) {
+    bool o = false;
+    for (int e = 0; e < 4; ++e) {
+        const double x = (e & 1) ? w - 1 : 0, y = (e & 2) ? h - 1 : 0;
+        const double sx = M[0] * x + M[1] * y + M[2], sy = M[3] * x + M[4] * y + M[5];
+        o = o || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
+    }
+    return o;
+}
+
+// source fields: the sent table and level 0 of the staged sources, as PatchArgs, CaliperArgs, GrayArgs and LocateArgs
+// name them; every other field zero
+template <class Args>
+Args source_args(fpm_ctx* ctx, int njobs) {
+    const SrcLevel& l0 = ctx->src[0];
+    Args a{};
+    a.jobs = ctx->d_patchtab.as<std::remove_pointer_t<decltype(a.jobs)>>();
+    a.njobs = njobs;
+    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
+    a.img_stride = l0.img_bytes;
+    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    return a;
+}
+
 // The job table of `poses` (PatchJob when tiled, else WarpJob), built in h_patchtab and sent to d_patchtab on the
 // context's stream (no wait): patch i goes to d_out + i * patch_stride.  matrices (optional): the forward matrices,
 // [n][6].  extra: bytes kept free in both buffers behind the table, from patch_tab_bytes(n) on (the comparison's tables).
@@ -1999,49 +2124,35 @@ int stage_patch_jobs(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pa
                      size_t row_stride, size_t patch_stride, double* matrices, bool tiled, size_t extra = 0) {
     const int n = (int)poses.size();
     const SrcLevel& l0 = ctx->src[0];
-    const size_t tab = patch_tab_bytes(n) + extra;
-    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table (long done as a rule)
-    HIP_TRY(ctx->h_patchtab.ensure(tab));
-    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    uint8_t* tab = nullptr;
+    int rc = tab_begin(ctx, patch_tab_bytes(n) + extra, &tab);
+    if (rc != FPM_OK) return rc;
     const uint8_t* level0 = ctx->d_src.as<uint8_t>() + l0.off;
     for (int i = 0; i < n; ++i) {
         const PatchPose& p = poses[i];
-        double M[6];
-        const int rc = patch_pose_matrix(ctx, r, p, i, matrices ? matrices + 6 * (size_t)i : nullptr, M);
-        if (rc != FPM_OK) return rc;
+        double* fwd = matrices ? matrices + 6 * (size_t)i : nullptr;
         const size_t off = (size_t)i * patch_stride;
         if (tiled) {
-            PatchJob& j = ctx->h_patchtab.as<PatchJob>()[i];
-            std::copy(M, M + 6, j.M);
-            j.out_off = (int64_t)off;
-            j.src = p.src;
-            j.pad = 0;
+            rc = tab_head(ctx, ((PatchJob*)tab)[i], r, p, i, (int64_t)off, fwd);
+            if (rc != FPM_OK) return rc;
         } else {
-            WarpJob& j = ctx->h_patchtab.as<WarpJob>()[i];
+            WarpJob& j = ((WarpJob*)tab)[i];
+            rc = patch_pose_matrix(ctx, r, p, i, fwd, j.M);
+            if (rc != FPM_OK) return rc;
             j.src = level0 + l0.img_bytes * (size_t)p.src;
             j.dst = d_out + off;
             j.sw = l0.w; j.sh = l0.h; j.sp = l0.pitch;
             j.dw = r.w; j.dh = r.h; j.dp = (int32_t)row_stride;
             j.border = 0;
             j.pad = 0;
-            std::copy(M, M + 6, j.M);
         }
     }
-    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, patch_tab_bytes(n), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
-    return FPM_OK;
+    return tab_send(ctx, patch_tab_bytes(n));
 }
 
 // the arguments of the tiled kernels (k_patch_warp, k_patch_compare) for a staged PatchJob table
 PatchArgs patch_args(fpm_ctx* ctx, const fpm_patch_rect& r, int n, uint8_t* d_out, size_t row_stride, size_t patch_stride) {
-    const SrcLevel& l0 = ctx->src[0];
-    PatchArgs a{};
-    a.jobs = ctx->d_patchtab.as<PatchJob>();
-    a.njobs = n;
-    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
-    a.img_stride = l0.img_bytes;
-    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    PatchArgs a = source_args<PatchArgs>(ctx, n);
     a.out = d_out;
     a.row_stride = row_stride;
     a.pw = r.w; a.ph = r.h;
@@ -2645,6 +2756,13 @@ int model_need(fpm_ctx* ctx, fpm_patch_rect* r) {
     return FPM_OK;
 }
 
+// the RectRule of the inspection and the blobs: the model's rectangle under the comparison's rules; no rectangle is passed
+int model_rect(fpm_ctx* ctx, const fpm_patch_rect*, fpm_patch_rect* r) {
+    fpm_patch_rect mr;
+    const int rc = model_need(ctx, &mr);
+    return rc != FPM_OK ? rc : compare_rect(ctx, &mr, r);
+}
+
 int model_args(fpm_ctx* ctx, int a, int kq) {
     if (a < 0 || a > 255 || kq < 0 || kq > 255) {
         ctx->err = "abs threshold must be 0 .. 255 and the sigma multiple 0 .. 255 sixteenths";
@@ -3098,14 +3216,12 @@ int caliper_outputs(fpm_ctx* ctx, size_t hits, const fpm_caliper* cals, int32_t 
 int calipers_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_caliper* cals, int n_cals, int cap_per,
                      fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t stride) {
     const int njobs = (int)poses.size() * n_cals;
-    const SrcLevel& l0 = ctx->src[0];
     int max_len = 0;
     for (int k = 0; k < n_cals; ++k) max_len = std::max(max_len, cals[k].length);
     const size_t tab = round_up(sizeof(CaliperJob) * (size_t)njobs, (size_t)256);
-    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
-    HIP_TRY(ctx->h_patchtab.ensure(tab));
-    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    CaliperJob* jobs = nullptr;
+    int rc = tab_begin(ctx, tab, &jobs);
+    if (rc != FPM_OK) return rc;
     // the device output: records, counts, then the profiles at the largest length (the caller's stride is the host's)
     const size_t rec_b = sizeof(int4) * (size_t)njobs * cap_per, cnt_b = round_up(sizeof(int32_t) * (size_t)njobs, (size_t)16);
     const size_t prof_b = profiles ? sizeof(int32_t) * (size_t)njobs * max_len : 0;
@@ -3113,7 +3229,6 @@ int calipers_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fp
     HIP_TRY(ctx->h_calout.ensure(rec_b + cnt_b + prof_b));
     std::vector<fpm_caliper_summary> sm((size_t)njobs);
     int64_t bytes = (int64_t)(rec_b + sizeof(int32_t) * (size_t)njobs + prof_b);
-    CaliperJob* jobs = ctx->h_patchtab.as<CaliperJob>();
     for (int i = 0, j = 0; i < (int)poses.size(); ++i)
         for (int k = 0; k < n_cals; ++k, ++j) {
             const fpm_caliper& c = cals[k];
@@ -3125,34 +3240,20 @@ int calipers_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fp
             caliper_pose(poses[i].pose.x, poses[i].pose.y, poses[i].pose.angle, c, &q.pose.x, &q.pose.y, &q.pose.angle);
             const fpm_patch_rect r{0, 0, c.length, c.width};
             CaliperJob& job = jobs[j];
-            const int rc = patch_pose_matrix(ctx, r, q, i, nullptr, job.p.M);
+            rc = tab_head(ctx, job.p, r, q, i, (int64_t)j * cap_per);
             if (rc != FPM_OK) return rc;
-            job.p.out_off = (int64_t)j * cap_per;
-            job.p.src = q.src;
-            job.p.pad = 0;
             job.L = c.length; job.W = c.width; job.s = c.half;
             job.thr = c.contrast * c.half * c.width;
             job.polarity = c.polarity;
             job.pad = 0;
             job.prof_off = (int64_t)j * max_len;
             bytes += (int64_t)c.length * c.width;
-            // border zeros in the profile: a corner sample outside the source, through the matrix the sampler takes
-            bool outside = false;
-            for (int e = 0; e < 4; ++e) {
-                const double x = (e & 1) ? c.length - 1 : 0, y = (e & 2) ? c.width - 1 : 0;
-                const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
-                outside = outside || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
-            }
+            const bool outside = corners_outside(ctx, job.p.M, c.length, c.width);   // border zeros in the profile
             sm[j] = fpm_caliper_summary{0, 0, -1, outside ? FPM_CALIPER_OUTSIDE : 0, q.pose.x, q.pose.y, q.pose.angle};
         }
-    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
-    CaliperArgs a{};
-    a.jobs = ctx->d_patchtab.as<CaliperJob>();
-    a.njobs = njobs;
-    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
-    a.img_stride = l0.img_bytes;
-    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    rc = tab_send(ctx, tab);
+    if (rc != FPM_OK) return rc;
+    CaliperArgs a = source_args<CaliperArgs>(ctx, njobs);
     a.cap = cap_per;
     a.prof_stride = max_len;
     a.edges = ctx->d_calout.as<int4>();
@@ -3245,10 +3346,9 @@ int gray_jobs(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const std:
     const int K = (int)rects.size();
     g->njobs = (int)poses.size() * K;
     g->tab = round_up(sizeof(GrayJob) * (size_t)g->njobs, (size_t)256);
-    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
-    HIP_TRY(ctx->h_patchtab.ensure(g->tab));
-    HIP_TRY(ctx->d_patchtab.ensure(g->tab));
+    GrayJob* jobs = nullptr;
+    int rc = tab_begin(ctx, g->tab, &jobs);
+    if (rc != FPM_OK) return rc;
     int64_t tiles = 0;
     g->px = 0;
     for (const fpm_patch_rect& r : rects) {
@@ -3257,17 +3357,13 @@ int gray_jobs(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const std:
     }
     g->run = gray_run_for(ctx, tiles);
     if (outside) outside->assign((size_t)g->njobs, 0);
-    GrayJob* jobs = ctx->h_patchtab.as<GrayJob>();
     int64_t wg = 0;
     for (int i = 0, j = 0; i < (int)poses.size(); ++i)
         for (int k = 0; k < K; ++k, ++j) {
             const fpm_patch_rect& r = rects[(size_t)k];
             GrayJob& job = jobs[j];
-            const int rc = patch_pose_matrix(ctx, r, poses[(size_t)i], i, nullptr, job.p.M);
+            rc = tab_head(ctx, job.p, r, poses[(size_t)i], i, (int64_t)((size_t)j * patch_stride));
             if (rc != FPM_OK) return rc;
-            job.p.out_off = (int64_t)((size_t)j * patch_stride);
-            job.p.src = poses[(size_t)i].src;
-            job.p.pad = 0;
             job.pw = r.w; job.ph = r.h; job.rx = r.x; job.ry = r.y;
             job.hist_off = (int64_t)j * 256;
             job.wg0 = (int32_t)wg;
@@ -3275,35 +3371,14 @@ int gray_jobs(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const std:
             const int64_t jt = (int64_t)((r.w + 63) / 64) * ((r.h + 15) / 16);
             wg += (jt + g->run - 1) / g->run;
             if (wg > INT_MAX) { ctx->err = "too many patch tiles for one launch"; return FPM_E_INVALID_ARG; }
-            if (outside) {   // border zeros in the region: a corner sample outside the source, through the sampler's matrix
-                bool o = false;
-                for (int e = 0; e < 4; ++e) {
-                    const double x = (e & 1) ? r.w - 1 : 0, y = (e & 2) ? r.h - 1 : 0;
-                    const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
-                    o = o || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
-                }
-                (*outside)[(size_t)j] = o ? FPM_GRAY_OUTSIDE : 0;
-            }
+            if (outside && corners_outside(ctx, job.p.M, r.w, r.h)) (*outside)[(size_t)j] = FPM_GRAY_OUTSIDE;   // border zeros
         }
     g->grid = (int)wg;
     return FPM_OK;
 }
 
-// the pinned job table to the device, on the stream (no wait)
-int gray_send_jobs(fpm_ctx* ctx, const GrayCall& g) {
-    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, g.tab, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
-    return FPM_OK;
-}
-
 GrayArgs gray_args(fpm_ctx* ctx, const GrayCall& g) {
-    const SrcLevel& l0 = ctx->src[0];
-    GrayArgs a{};
-    a.jobs = ctx->d_patchtab.as<GrayJob>();
-    a.njobs = g.njobs;
-    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
-    a.img_stride = l0.img_bytes;
-    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    GrayArgs a = source_args<GrayArgs>(ctx, g.njobs);
     a.mask = mask_plane(ctx);
     a.mkp = ctx->tmpl[0].pitch;
     a.run = g.run;
@@ -3349,7 +3424,7 @@ int gray_to_host(fpm_ctx* ctx, const std::vector<fpm_patch_rect>& rects, const s
     HIP_TRY(ctx->h_gray.ensure(hb));
     std::vector<int64_t> used(rects.size());
     for (size_t k = 0; k < rects.size(); ++k) used[k] = mask_used(ctx, rects[k]);
-    rc = gray_send_jobs(ctx, g);
+    rc = tab_send(ctx, g.tab);
     if (rc == FPM_OK) rc = gray_hist_run(ctx, g, used);
     if (rc != FPM_OK) return rc;
     std::memcpy(hist, ctx->h_gray.p, hb);
@@ -3376,7 +3451,7 @@ int segment_of_poses(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pa
     GrayCall g;
     std::vector<int32_t> flags;
     rc = gray_jobs(ctx, {r}, poses, pbytes, otsu ? 0 : threshold, polarity, &g, &flags);
-    if (rc == FPM_OK) rc = gray_send_jobs(ctx, g);
+    if (rc == FPM_OK) rc = tab_send(ctx, g.tab);
     if (rc != FPM_OK) return rc;
     const int64_t used = mask_used(ctx, r);
     std::vector<int32_t> ts((size_t)n, threshold);
@@ -3393,7 +3468,7 @@ int segment_of_poses(fpm_ctx* ctx, const fpm_patch_rect& r, const std::vector<Pa
             jobs[i].t = ts[(size_t)i];
             jobs[i].polarity = s.flags ? 0 : polarity;   // empty or flat: no foreground
         }
-        rc = gray_send_jobs(ctx, g);
+        rc = tab_send(ctx, g.tab);
         if (rc != FPM_OK) return rc;
     }
     GrayArgs a = gray_args(ctx, g);
@@ -3460,13 +3535,11 @@ int locate_bands(int noff, int h) {
 int locate_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_feature* feats, int n_feats, int max_off,
                    fpm_locate_result* results, fpm_locate_raw* raw, int32_t* maps, int32_t map_stride) {
     const int njobs = (int)poses.size() * n_feats;
-    const SrcLevel& l0 = ctx->src[0];
     const TmplLevel& t0 = ctx->tmpl[0];
     const size_t tab = round_up(sizeof(LocateJob) * (size_t)njobs, (size_t)256);
-    if (!ctx->tab_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tab_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(ctx->tab_ev));   // an earlier call's copy out of the pinned table
-    HIP_TRY(ctx->h_patchtab.ensure(tab));
-    HIP_TRY(ctx->d_patchtab.ensure(tab));
+    LocateJob* jobs = nullptr;
+    int rc = tab_begin(ctx, tab, &jobs);
+    if (rc != FPM_OK) return rc;
     // the device output: records, then the maps at the largest offset count (the caller's stride is the host's)
     const size_t rec_b = sizeof(fpm_locate_raw) * (size_t)njobs;
     const size_t map_b = maps ? sizeof(int32_t) * 3 * (size_t)max_off * (size_t)njobs : 0;
@@ -3474,38 +3547,22 @@ int locate_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_
     HIP_TRY(ctx->h_locout.ensure(rec_b + map_b));
     std::vector<int32_t> outside((size_t)njobs, 0);
     int64_t bytes = (int64_t)(rec_b + map_b);
-    LocateJob* jobs = ctx->h_patchtab.as<LocateJob>();
     for (int i = 0, j = 0; i < (int)poses.size(); ++i)
         for (int k = 0; k < n_feats; ++k, ++j) {
             const fpm_feature& f = feats[k];
             const fpm_patch_rect r{f.x - f.rx, f.y - f.ry, f.w + 2 * f.rx, f.h + 2 * f.ry};   // the window
             LocateJob& job = jobs[j];
-            const int rc = patch_pose_matrix(ctx, r, poses[(size_t)i], i, nullptr, job.p.M);
+            rc = tab_head(ctx, job.p, r, poses[(size_t)i], i, 0);
             if (rc != FPM_OK) return rc;
-            job.p.out_off = 0;
-            job.p.src = poses[(size_t)i].src;
-            job.p.pad = 0;
             job.x = f.x; job.y = f.y; job.w = f.w; job.h = f.h; job.rx = f.rx; job.ry = f.ry;
             job.bands = locate_bands((2 * f.rx + 1) * (2 * f.ry + 1), f.h);
             job.pad = 0;
             bytes += (int64_t)r.w * r.h + (int64_t)f.w * f.h;
-            // border zeros in the window: a corner sample outside the source, through the matrix the sampler takes
-            bool o = false;
-            for (int e = 0; e < 4; ++e) {
-                const double x = (e & 1) ? r.w - 1 : 0, y = (e & 2) ? r.h - 1 : 0;
-                const double sx = job.p.M[0] * x + job.p.M[1] * y + job.p.M[2], sy = job.p.M[3] * x + job.p.M[4] * y + job.p.M[5];
-                o = o || !(sx >= 0.0 && sx <= (double)(ctx->sw - 1) && sy >= 0.0 && sy <= (double)(ctx->sh - 1));
-            }
-            outside[(size_t)j] = o ? FPM_LOCATE_OUTSIDE : 0;
+            outside[(size_t)j] = corners_outside(ctx, job.p.M, r.w, r.h) ? FPM_LOCATE_OUTSIDE : 0;   // border zeros in the window
         }
-    HIP_TRY(hipMemcpyAsync(ctx->d_patchtab.p, ctx->h_patchtab.p, tab, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->tab_ev, ctx->stream));
-    LocateArgs a{};
-    a.jobs = ctx->d_patchtab.as<LocateJob>();
-    a.njobs = njobs;
-    a.level0 = ctx->d_src.as<uint8_t>() + l0.off;
-    a.img_stride = l0.img_bytes;
-    a.sw = l0.w; a.sh = l0.h; a.sp = l0.pitch;
+    rc = tab_send(ctx, tab);
+    if (rc != FPM_OK) return rc;
+    LocateArgs a = source_args<LocateArgs>(ctx, njobs);
     a.tmpl = ctx->d_tmpl.as<uint8_t>() + t0.off;
     a.tp = t0.pitch;
     a.raw = ctx->d_locout.as<int32_t>();
@@ -3932,29 +3989,15 @@ int fpm_set_patch_form(fpm_ctx* ctx, int32_t form) {
     return FPM_OK;
 }
 
-// state, rectangle, poses and capacity of a fpm_last_patches* / fpm_last_compare call; FPM_OK with poses empty =
-// nothing to do.  inside: the rectangle is a comparison's (within the template).
-static int last_patches_begin(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t cap, int32_t* n_patches,
-                              fpm_patch_rect* r, std::vector<PatchPose>& poses, bool inside = false) {
-    *n_patches = 0;
-    int rc = patch_state(ctx, true);
-    if (rc == FPM_OK) rc = inside ? compare_rect(ctx, rect, r) : patch_rect(ctx, rect, r);
-    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
+// One body per tool: query, state, rectangle or arguments, poses, outputs, run.  The public
+// entries of a pair differ in their HitQuery alone unless a comment says otherwise.
+static int patches_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, uint8_t* out, size_t row_stride,
+                         size_t patch_stride, double* matrices) {
+    int rc = q.check(ctx);
     if (rc != FPM_OK) return rc;
-    *n_patches = (int32_t)poses.size();
-    if ((int)poses.size() > cap) {
-        ctx->err = "patch buffer too small";
-        return FPM_E_CAPACITY;
-    }
-    return FPM_OK;
-}
-
-int fpm_last_patches(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, uint8_t* out, size_t row_stride,
-                     size_t patch_stride, int32_t cap, int32_t* n_patches, double* matrices) {
-    if (!ctx || !n_patches) return FPM_E_INVALID_ARG;
     fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    int rc = last_patches_begin(ctx, rect, source, cap, n_patches, &r, poses);
+    rc = hits_begin(ctx, q, patch_rect, rect, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     rc = check_patch_out(ctx, out, r, row_stride, patch_stride);
     if (rc != FPM_OK) return rc;
@@ -3962,12 +4005,26 @@ int fpm_last_patches(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, u
     return patches_to_host(ctx, r, poses, out, row_stride, patch_stride, matrices);
 }
 
+int fpm_last_patches(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, uint8_t* out, size_t row_stride,
+                     size_t patch_stride, int32_t cap, int32_t* n_patches, double* matrices) {
+    return patches_entry(ctx, HitQuery::last(source, cap, n_patches), rect, out, row_stride, patch_stride, matrices);
+}
+
+int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
+                   const double* angles, int32_t n, uint8_t* out, size_t row_stride, size_t patch_stride,
+                   double* matrices) {
+    return patches_entry(ctx, HitQuery::at(src_index, lt, angles, n), rect, out, row_stride, patch_stride, matrices);
+}
+
+// the device variant has no _at entry: one body, written out
 int fpm_last_patches_device(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, void* d_out, size_t row_stride,
                             size_t patch_stride, int32_t cap, int32_t* n_patches, void* consumer_stream) {
-    if (!ctx || !n_patches) return FPM_E_INVALID_ARG;
+    const HitQuery q = HitQuery::last(source, cap, n_patches);
+    int rc = q.check(ctx);
+    if (rc != FPM_OK) return rc;
     fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    int rc = last_patches_begin(ctx, rect, source, cap, n_patches, &r, poses);
+    rc = hits_begin(ctx, q, patch_rect, rect, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     rc = check_patch_out(ctx, d_out, r, row_stride, patch_stride);
     if (rc != FPM_OK) return rc;
@@ -3989,23 +4046,6 @@ int fpm_last_patches_device(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t so
     return FPM_OK;
 }
 
-int fpm_patches_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
-                   const double* angles, int32_t n, uint8_t* out, size_t row_stride, size_t patch_stride,
-                   double* matrices) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    fpm_patch_rect r;
-    int rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = patch_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n == 0) return rc;
-    rc = check_patch_out(ctx, out, r, row_stride, patch_stride);
-    if (rc != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n);
-    for (int i = 0; i < n; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return patches_to_host(ctx, r, poses, out, row_stride, patch_stride, matrices);
-}
-
 // --- patch comparison -----------------------------------------------------------------
 int fpm_compare_derive(int64_t n, int64_t sum_i, int64_t sum_ii, int64_t sum_t, int64_t sum_tt, int64_t sum_it,
                        int32_t normalize, double* zncc, double* gain, double* offset, uint8_t lut[256]) {
@@ -4025,16 +4065,14 @@ static int compare_args(fpm_ctx* ctx, int32_t threshold, int32_t flags) {
     return FPM_OK;
 }
 
-int fpm_last_compare(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t threshold, int32_t flags,
-                     fpm_compare_stats* out, int32_t cap, int32_t* n, uint8_t* diff, size_t row_stride,
-                     size_t patch_stride) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = compare_args(ctx, threshold, flags);
+static int compare_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, int32_t threshold, int32_t flags,
+                         fpm_compare_stats* out, uint8_t* diff, size_t row_stride, size_t patch_stride) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = compare_args(ctx, threshold, flags);
     if (rc != FPM_OK) return rc;
     fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    rc = last_patches_begin(ctx, rect, source, cap, n, &r, poses, true);
+    rc = hits_begin(ctx, q, compare_rect, rect, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
     if (diff && (rc = check_patch_out(ctx, diff, r, row_stride, patch_stride)) != FPM_OK) return rc;
@@ -4042,23 +4080,17 @@ int fpm_last_compare(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, i
     return compare_to_host(ctx, r, poses, threshold, flags, out, diff, row_stride, patch_stride);
 }
 
+int fpm_last_compare(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t threshold, int32_t flags,
+                     fpm_compare_stats* out, int32_t cap, int32_t* n, uint8_t* diff, size_t row_stride,
+                     size_t patch_stride) {
+    return compare_entry(ctx, HitQuery::last(source, cap, n), rect, threshold, flags, out, diff, row_stride, patch_stride);
+}
+
 int fpm_compare_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
                    const double* angles, int32_t n_poses, int32_t threshold, int32_t flags, fpm_compare_stats* out,
                    uint8_t* diff, size_t row_stride, size_t patch_stride) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = compare_args(ctx, threshold, flags);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r;
-    rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
-    if (diff && (rc = check_patch_out(ctx, diff, r, row_stride, patch_stride)) != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return compare_to_host(ctx, r, poses, threshold, flags, out, diff, row_stride, patch_stride);
+    return compare_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), rect, threshold, flags, out, diff, row_stride,
+                         patch_stride);
 }
 
 // --- learning on the device -----------------------------------------------------------
@@ -4134,34 +4166,31 @@ int fpm_model_info(const fpm_ctx* ctx, int32_t* n, fpm_patch_rect* rect) {
     return FPM_OK;
 }
 
-int fpm_model_train_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t flags, int32_t* n_added) {
-    if (!ctx || !n_added) return FPM_E_INVALID_ARG;
-    *n_added = 0;
+static int model_train_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, int32_t flags) {
+    int rc = q.check(ctx);
+    if (rc != FPM_OK) return rc;
     if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown training flags"; return FPM_E_INVALID_ARG; }
     fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    int32_t n = 0;
-    int rc = last_patches_begin(ctx, rect, source, INT32_MAX, &n, &r, poses, true);
+    rc = hits_begin(ctx, q, compare_rect, rect, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = model_train(ctx, r, poses, flags);
+    return model_train(ctx, r, poses, flags);
+}
+
+// no capacity: every hit is taken, and *n_added is their count only once they are in the model
+int fpm_model_train_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t flags, int32_t* n_added) {
+    if (!ctx || !n_added) return FPM_E_INVALID_ARG;
+    *n_added = 0;
+    int32_t n = 0;
+    const int rc = model_train_entry(ctx, HitQuery::last(source, INT32_MAX, &n), rect, flags);
     if (rc == FPM_OK) *n_added = n;
     return rc;
 }
 
 int fpm_model_train_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
                        const double* angles, int32_t n_poses, int32_t flags) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown training flags"; return FPM_E_INVALID_ARG; }
-    fpm_patch_rect r;
-    int rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return model_train(ctx, r, poses, flags);
+    return model_train_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), rect, flags);
 }
 
 int fpm_model_sums(fpm_ctx* ctx, uint32_t* sum, uint32_t* sum_sq) {
@@ -4205,17 +4234,14 @@ static int inspect_args(fpm_ctx* ctx, int32_t a, int32_t kq, int32_t flags) {
     return model_args(ctx, a, kq);
 }
 
-int fpm_last_inspect(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out,
-                     int32_t cap, int32_t* n, uint8_t* img, size_t row_stride, size_t patch_stride) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = inspect_args(ctx, a, kq, flags);
+static int inspect_entry(fpm_ctx* ctx, const HitQuery& q, int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out,
+                         uint8_t* img, size_t row_stride, size_t patch_stride) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = inspect_args(ctx, a, kq, flags);
     if (rc != FPM_OK) return rc;
-    fpm_patch_rect r, mr;
+    fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    rc = patch_state(ctx, true);
-    if (rc == FPM_OK) rc = model_need(ctx, &mr);
-    if (rc == FPM_OK) rc = last_patches_begin(ctx, &mr, source, cap, n, &r, poses, true);
+    rc = hits_begin(ctx, q, model_rect, nullptr, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
     if (img && (rc = check_patch_out(ctx, img, r, row_stride, patch_stride)) != FPM_OK) return rc;
@@ -4223,24 +4249,15 @@ int fpm_last_inspect(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_
     return inspect_to_host(ctx, r, poses, a, kq, flags, out, img, row_stride, patch_stride);
 }
 
+int fpm_last_inspect(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out,
+                     int32_t cap, int32_t* n, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    return inspect_entry(ctx, HitQuery::last(source, cap, n), a, kq, flags, out, img, row_stride, patch_stride);
+}
+
 int fpm_inspect_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
                    int32_t a, int32_t kq, int32_t flags, fpm_inspect_stats* out, uint8_t* img, size_t row_stride,
                    size_t patch_stride) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = inspect_args(ctx, a, kq, flags);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r, mr;
-    rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = model_need(ctx, &mr);
-    if (rc == FPM_OK) rc = compare_rect(ctx, &mr, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!out) { ctx->err = "null statistics buffer"; return FPM_E_INVALID_ARG; }
-    if (img && (rc = check_patch_out(ctx, img, r, row_stride, patch_stride)) != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return inspect_to_host(ctx, r, poses, a, kq, flags, out, img, row_stride, patch_stride);
+    return inspect_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), a, kq, flags, out, img, row_stride, patch_stride);
 }
 
 int fpm_model_learn(fpm_ctx* ctx) {
@@ -4345,12 +4362,7 @@ int fpm_mask_count(fpm_ctx* ctx, const fpm_patch_rect* rect, int64_t* n) {
 }
 
 int fpm_model_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || which < 0 || which > 2 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfModelTrain + which];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfModelTrain, which, 2, ms, launches, bytes);
 }
 
 // --- defect blobs on the device -----------------------------------------------------------
@@ -4361,18 +4373,15 @@ static int blob_args(fpm_ctx* ctx, int64_t n, int32_t level, int32_t connectivit
     return FPM_OK;
 }
 
-int fpm_last_blobs(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, int32_t level,
-                   int32_t connectivity, int32_t min_area, fpm_inspect_stats* stats, fpm_blob_summary* summary,
-                   fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = inspect_args(ctx, a, kq, flags);
+static int blobs_entry(fpm_ctx* ctx, const HitQuery& q, int32_t a, int32_t kq, int32_t flags, int32_t level,
+                       int32_t connectivity, int32_t min_area, fpm_inspect_stats* stats, fpm_blob_summary* summary,
+                       fpm_blob* out, int32_t cap_per_hit) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = inspect_args(ctx, a, kq, flags);
     if (rc != FPM_OK) return rc;
-    fpm_patch_rect r, mr;
+    fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    rc = patch_state(ctx, true);
-    if (rc == FPM_OK) rc = model_need(ctx, &mr);
-    if (rc == FPM_OK) rc = last_patches_begin(ctx, &mr, source, cap, n, &r, poses, true);
+    rc = hits_begin(ctx, q, model_rect, nullptr, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     rc = blob_args(ctx, (int64_t)poses.size(), level, connectivity, min_area, cap_per_hit, summary, out);
     if (rc != FPM_OK) return rc;
@@ -4380,24 +4389,18 @@ int fpm_last_blobs(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t 
     return blobs_of_poses(ctx, r, poses, a, kq, flags, level, connectivity, min_area, cap_per_hit, stats, summary, out);
 }
 
+int fpm_last_blobs(fpm_ctx* ctx, int32_t source, int32_t a, int32_t kq, int32_t flags, int32_t level,
+                   int32_t connectivity, int32_t min_area, fpm_inspect_stats* stats, fpm_blob_summary* summary,
+                   fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n) {
+    return blobs_entry(ctx, HitQuery::last(source, cap, n), a, kq, flags, level, connectivity, min_area, stats, summary, out,
+                       cap_per_hit);
+}
+
 int fpm_blobs_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
                  int32_t a, int32_t kq, int32_t flags, int32_t level, int32_t connectivity, int32_t min_area,
                  fpm_inspect_stats* stats, fpm_blob_summary* summary, fpm_blob* out, int32_t cap_per_hit) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = inspect_args(ctx, a, kq, flags);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r, mr;
-    rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = model_need(ctx, &mr);
-    if (rc == FPM_OK) rc = compare_rect(ctx, &mr, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    rc = blob_args(ctx, n_poses, level, connectivity, min_area, cap_per_hit, summary, out);
-    if (rc != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return blobs_of_poses(ctx, r, poses, a, kq, flags, level, connectivity, min_area, cap_per_hit, stats, summary, out);
+    return blobs_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), a, kq, flags, level, connectivity, min_area, stats,
+                       summary, out, cap_per_hit);
 }
 
 int fpm_op_blobs(fpm_ctx* ctx, const uint8_t* images, int32_t n, int32_t w, int32_t h, size_t stride, int32_t level,
@@ -4450,12 +4453,7 @@ int fpm_blobs_set_round(fpm_ctx* ctx, int32_t images) {
 }
 
 int fpm_blobs_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || which < 0 || which > 4 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfBlobTile + which];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfBlobTile, which, 4, ms, launches, bytes);
 }
 
 // --- pose alignment --------------------------------------------------------------------
@@ -4479,55 +4477,57 @@ static int align_args(fpm_ctx* ctx, int32_t iters, double max_step, int32_t flag
     return FPM_OK;
 }
 
+// state, alignment rectangle and poses, then the output pointer under the entry's own text
+static int align_begin_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, const void* out, const char* null_out,
+                             fpm_patch_rect* r, std::vector<PatchPose>& poses) {
+    // align_rect is compare_rect under narrower caps, so what passes it needs no second look by compare_rect: one rule
+    // for all three entries
+    const int rc = hits_begin(ctx, q, align_rect, rect, r, poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    if (!out) { ctx->err = null_out; return FPM_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    return FPM_OK;
+}
+
 int fpm_align_sums_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
                       const double* angles, int32_t n_poses, int32_t flags, fpm_align_sums* out) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
+    const HitQuery q = HitQuery::at(src_index, lt, angles, n_poses);
+    int rc = q.check(ctx);
+    if (rc != FPM_OK) return rc;
     if (flags & ~FPM_COMPARE_NORMALIZE) { ctx->err = "unknown alignment flags"; return FPM_E_INVALID_ARG; }
     fpm_patch_rect r;
-    int rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!out) { ctx->err = "null sums buffer"; return FPM_E_INVALID_ARG; }
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<PatchPose> poses;
+    rc = align_begin_entry(ctx, q, rect, out, "null sums buffer", &r, poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
     return align_sums_to_host(ctx, r, poses, flags, out);
+}
+
+// known: the flags the entry takes.  FPM_ALIGN_ADOPT is fpm_align_last's alone (intended: only it has last poses to
+// replace); `aligned` receives the returned poses when it is set.
+static int align_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, int32_t iters, double max_step,
+                       int32_t flags, int32_t known, fpm_align_result* out, std::vector<PatchPose>* aligned) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = align_args(ctx, iters, max_step, flags, known);
+    if (rc != FPM_OK) return rc;
+    fpm_patch_rect r;
+    std::vector<PatchPose> poses;
+    rc = align_begin_entry(ctx, q, rect, out, "null result buffer", &r, poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    return align_iterate(ctx, r, poses, iters, max_step, flags & FPM_COMPARE_NORMALIZE, out, aligned);
 }
 
 int fpm_align_at(fpm_ctx* ctx, const fpm_patch_rect* rect, const int32_t* src_index, const float* lt,
                  const double* angles, int32_t n_poses, int32_t iters, double max_step, int32_t flags,
                  fpm_align_result* out) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = align_args(ctx, iters, max_step, flags, FPM_COMPARE_NORMALIZE);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r;
-    rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!out) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return align_iterate(ctx, r, poses, iters, max_step, flags, out, nullptr);
+    return align_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), rect, iters, max_step, flags, FPM_COMPARE_NORMALIZE,
+                       out, nullptr);
 }
 
 int fpm_align_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int32_t iters, double max_step,
                    int32_t flags, fpm_align_result* out, int32_t cap, int32_t* n) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = align_args(ctx, iters, max_step, flags, FPM_COMPARE_NORMALIZE | FPM_ALIGN_ADOPT);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r;
-    std::vector<PatchPose> poses, aligned;
-    rc = patch_state(ctx, true);
-    if (rc == FPM_OK) rc = align_rect(ctx, rect, &r);   // the narrower caps before the comparison's own
-    if (rc == FPM_OK) rc = last_patches_begin(ctx, &r, source, cap, n, &r, poses, true);
-    if (rc != FPM_OK || poses.empty()) return rc;
-    if (!out) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    rc = align_iterate(ctx, r, poses, iters, max_step, flags & FPM_COMPARE_NORMALIZE, out, &aligned);
+    std::vector<PatchPose> aligned;
+    const int rc = align_entry(ctx, HitQuery::last(source, cap, n), rect, iters, max_step, flags,
+                               FPM_COMPARE_NORMALIZE | FPM_ALIGN_ADOPT, out, &aligned);
     if (rc != FPM_OK || !(flags & FPM_ALIGN_ADOPT)) return rc;
     // the aligned poses become the last poses, in last_poses' order; the results and candidates stay what they were
     size_t i = 0;
@@ -4538,93 +4538,68 @@ int fpm_align_last(fpm_ctx* ctx, const fpm_patch_rect* rect, int32_t source, int
 }
 
 int fpm_align_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfAlign];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfAlign, 0, 0, ms, launches, bytes);
 }
 
 // --- edge calipers (fpm_caliper_pose, fpm_caliper_edges_host and fpm_caliper_derive: fpm_host.cpp) --
-int fpm_calipers_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
-                    const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper, fpm_caliper_summary* summary,
-                    fpm_edge* edges, int32_t* profiles, int32_t profile_stride) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = caliper_args(ctx, cals, n_cals, cap_per_caliper);
-    if (rc == FPM_OK) rc = caliper_state(ctx);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    rc = caliper_outputs(ctx, (size_t)n_poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
-    if (rc != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return calipers_to_host(ctx, poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
-}
-
-int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper,
-                      fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t profile_stride,
-                      int32_t cap, int32_t* n) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = caliper_args(ctx, cals, n_cals, cap_per_caliper);
-    if (rc == FPM_OK) rc = patch_state(ctx, true);
+static int calipers_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper,
+                          fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t profile_stride) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = caliper_args(ctx, cals, n_cals, cap_per_caliper);
+    // intended: a caliper reads level 0 alone, so the caller's poses need no template (caliper_state); the last
+    // search's poses imply one (patch_state)
+    if (rc == FPM_OK) rc = q.need_search() ? patch_state(ctx, true) : caliper_state(ctx);
     std::vector<PatchPose> poses;
-    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
-    if (rc != FPM_OK) return rc;
-    *n = (int32_t)poses.size();
-    if ((int)poses.size() > cap) { ctx->err = "caliper buffers too small"; return FPM_E_CAPACITY; }
-    if (poses.empty()) return FPM_OK;
+    if (rc == FPM_OK) rc = q.resolve(ctx, "caliper buffers too small", poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
     rc = caliper_outputs(ctx, poses.size(), cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
     if (rc != FPM_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     return calipers_to_host(ctx, poses, cals, n_cals, cap_per_caliper, summary, edges, profiles, profile_stride);
 }
 
+int fpm_calipers_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                    const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper, fpm_caliper_summary* summary,
+                    fpm_edge* edges, int32_t* profiles, int32_t profile_stride) {
+    return calipers_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), cals, n_cals, cap_per_caliper, summary, edges,
+                          profiles, profile_stride);
+}
+
+int fpm_last_calipers(fpm_ctx* ctx, int32_t source, const fpm_caliper* cals, int32_t n_cals, int32_t cap_per_caliper,
+                      fpm_caliper_summary* summary, fpm_edge* edges, int32_t* profiles, int32_t profile_stride,
+                      int32_t cap, int32_t* n) {
+    return calipers_entry(ctx, HitQuery::last(source, cap, n), cals, n_cals, cap_per_caliper, summary, edges, profiles,
+                          profile_stride);
+}
+
 int fpm_caliper_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfCaliper];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfCaliper, 0, 0, ms, launches, bytes);
 }
 
 // --- gray-value tools (fpm_hist_derive: fpm_host.cpp) ------------------------------------------
-int fpm_histogram_at(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, const int32_t* src_index, const float* lt,
-                     const double* angles, int32_t n_poses, uint32_t* hist) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    std::vector<fpm_patch_rect> rs;
-    int rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = gray_rects(ctx, rects, n_rects, rs);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!hist) { ctx->err = "null histogram buffer"; return FPM_E_INVALID_ARG; }
-    if ((int64_t)n_poses * n_rects > FPM_GRAY_MAX_JOBS) { ctx->err = "hits x rectangles above 65536"; return FPM_E_INVALID_ARG; }
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return gray_to_host(ctx, rs, poses, hist);
-}
-
-int fpm_last_histogram(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, int32_t source, uint32_t* hist,
-                       int32_t cap, int32_t* n) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
+static int histogram_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rects, int32_t n_rects, uint32_t* hist) {
+    int rc = q.check(ctx);
+    if (rc != FPM_OK) return rc;
     std::vector<fpm_patch_rect> rs;
     std::vector<PatchPose> poses;
-    int rc = patch_state(ctx, true);
+    rc = patch_state(ctx, q.need_search());
     if (rc == FPM_OK) rc = gray_rects(ctx, rects, n_rects, rs);
-    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
-    if (rc != FPM_OK) return rc;
-    *n = (int32_t)poses.size();
-    if ((int)poses.size() > cap) { ctx->err = "histogram buffer too small"; return FPM_E_CAPACITY; }
-    if (poses.empty()) return FPM_OK;
+    if (rc == FPM_OK) rc = q.resolve(ctx, "histogram buffer too small", poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
     if (!hist) { ctx->err = "null histogram buffer"; return FPM_E_INVALID_ARG; }
     if ((int64_t)poses.size() * n_rects > FPM_GRAY_MAX_JOBS) { ctx->err = "hits x rectangles above 65536"; return FPM_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     return gray_to_host(ctx, rs, poses, hist);
+}
+
+int fpm_histogram_at(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, const int32_t* src_index, const float* lt,
+                     const double* angles, int32_t n_poses, uint32_t* hist) {
+    return histogram_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), rects, n_rects, hist);
+}
+
+int fpm_last_histogram(fpm_ctx* ctx, const fpm_patch_rect* rects, int32_t n_rects, int32_t source, uint32_t* hist,
+                       int32_t cap, int32_t* n) {
+    return histogram_entry(ctx, HitQuery::last(source, cap, n), rects, n_rects, hist);
 }
 
 static int segment_args(fpm_ctx* ctx, int32_t threshold, int32_t polarity) {
@@ -4643,17 +4618,15 @@ static int segment_outputs(fpm_ctx* ctx, int64_t hits, const fpm_patch_rect& r, 
     return FPM_OK;
 }
 
-int fpm_last_segment(fpm_ctx* ctx, int32_t source, const fpm_patch_rect* rect, int32_t threshold, int32_t polarity,
-                     int32_t connectivity, int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary,
-                     fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n, uint8_t* img, size_t row_stride,
-                     size_t patch_stride) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
-    int rc = segment_args(ctx, threshold, polarity);
+static int segment_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_patch_rect* rect, int32_t threshold, int32_t polarity,
+                         int32_t connectivity, int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary,
+                         fpm_blob* out, int32_t cap_per_hit, uint8_t* img, size_t row_stride, size_t patch_stride) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = segment_args(ctx, threshold, polarity);
     if (rc != FPM_OK) return rc;
     fpm_patch_rect r;
     std::vector<PatchPose> poses;
-    rc = last_patches_begin(ctx, rect, source, cap, n, &r, poses, true);
+    rc = hits_begin(ctx, q, compare_rect, rect, &r, poses);
     if (rc != FPM_OK || poses.empty()) return rc;
     rc = segment_outputs(ctx, (int64_t)poses.size(), r, connectivity, min_area, cap_per_hit, info, summary, out, img,
                          row_stride, patch_stride);
@@ -4663,26 +4636,20 @@ int fpm_last_segment(fpm_ctx* ctx, int32_t source, const fpm_patch_rect* rect, i
                             img, row_stride, patch_stride);
 }
 
+int fpm_last_segment(fpm_ctx* ctx, int32_t source, const fpm_patch_rect* rect, int32_t threshold, int32_t polarity,
+                     int32_t connectivity, int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary,
+                     fpm_blob* out, int32_t cap_per_hit, int32_t cap, int32_t* n, uint8_t* img, size_t row_stride,
+                     size_t patch_stride) {
+    return segment_entry(ctx, HitQuery::last(source, cap, n), rect, threshold, polarity, connectivity, min_area, info, summary,
+                         out, cap_per_hit, img, row_stride, patch_stride);
+}
+
 int fpm_segment_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
                    const fpm_patch_rect* rect, int32_t threshold, int32_t polarity, int32_t connectivity,
                    int32_t min_area, fpm_segment_info* info, fpm_blob_summary* summary, fpm_blob* out,
                    int32_t cap_per_hit, uint8_t* img, size_t row_stride, size_t patch_stride) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int rc = segment_args(ctx, threshold, polarity);
-    if (rc != FPM_OK) return rc;
-    fpm_patch_rect r;
-    rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = compare_rect(ctx, rect, &r);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    rc = segment_outputs(ctx, n_poses, r, connectivity, min_area, cap_per_hit, info, summary, out, img, row_stride,
-                         patch_stride);
-    if (rc != FPM_OK) return rc;
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return segment_of_poses(ctx, r, poses, threshold, polarity, connectivity, min_area, cap_per_hit, info, summary, out,
-                            img, row_stride, patch_stride);
+    return segment_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), rect, threshold, polarity, connectivity, min_area,
+                         info, summary, out, cap_per_hit, img, row_stride, patch_stride);
 }
 
 int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles) {
@@ -4693,58 +4660,39 @@ int fpm_gray_set_run(fpm_ctx* ctx, int32_t tiles) {
 }
 
 int fpm_gray_profile(const fpm_ctx* ctx, int32_t which, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || which < 0 || which > 1 || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfGrayHist + which];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfGrayHist, which, 1, ms, launches, bytes);
 }
 
 // --- sub-pattern locators (fpm_locate_host and fpm_locate_derive: fpm_host.cpp) --------------------
-int fpm_locate_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
-                  const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results, fpm_locate_raw* raw, int32_t* maps,
-                  int32_t map_stride) {
-    if (!ctx) return FPM_E_INVALID_ARG;
-    if (n_poses < 0 || (n_poses > 0 && (!src_index || !lt || !angles))) { ctx->err = "bad poses"; return FPM_E_INVALID_ARG; }
-    int max_off = 0;
-    int rc = patch_state(ctx, false);
-    if (rc == FPM_OK) rc = locate_args(ctx, feats, n_feats, maps, map_stride, &max_off);
-    if (rc != FPM_OK || n_poses == 0) return rc;
-    if (!results) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
-    if ((int64_t)n_poses * n_feats > FPM_LOCATE_MAX_JOBS) { ctx->err = "hits x features above 65536"; return FPM_E_INVALID_ARG; }
-    std::vector<PatchPose> poses((size_t)n_poses);
-    for (int i = 0; i < n_poses; ++i) poses[i] = {src_index[i], {lt[2 * i], lt[2 * i + 1], angles[i]}};
-    HIP_TRY(hipSetDevice(ctx->device));
-    return locate_to_host(ctx, poses, feats, n_feats, max_off, results, raw, maps, map_stride);
-}
-
-int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results,
-                    fpm_locate_raw* raw, int32_t* maps, int32_t map_stride, int32_t cap, int32_t* n) {
-    if (!ctx || !n) return FPM_E_INVALID_ARG;
-    *n = 0;
+static int locate_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results,
+                        fpm_locate_raw* raw, int32_t* maps, int32_t map_stride) {
+    int rc = q.check(ctx);
+    if (rc != FPM_OK) return rc;
     int max_off = 0;
     std::vector<PatchPose> poses;
-    int rc = patch_state(ctx, true);
+    rc = patch_state(ctx, q.need_search());
     if (rc == FPM_OK) rc = locate_args(ctx, feats, n_feats, maps, map_stride, &max_off);
-    if (rc == FPM_OK) rc = last_poses(ctx, source, poses);
-    if (rc != FPM_OK) return rc;
-    *n = (int32_t)poses.size();
-    if ((int)poses.size() > cap) { ctx->err = "locate buffers too small"; return FPM_E_CAPACITY; }
-    if (poses.empty()) return FPM_OK;
+    if (rc == FPM_OK) rc = q.resolve(ctx, "locate buffers too small", poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
     if (!results) { ctx->err = "null result buffer"; return FPM_E_INVALID_ARG; }
     if ((int64_t)poses.size() * n_feats > FPM_LOCATE_MAX_JOBS) { ctx->err = "hits x features above 65536"; return FPM_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     return locate_to_host(ctx, poses, feats, n_feats, max_off, results, raw, maps, map_stride);
 }
 
+int fpm_locate_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                  const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results, fpm_locate_raw* raw, int32_t* maps,
+                  int32_t map_stride) {
+    return locate_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), feats, n_feats, results, raw, maps, map_stride);
+}
+
+int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int32_t n_feats, fpm_locate_result* results,
+                    fpm_locate_raw* raw, int32_t* maps, int32_t map_stride, int32_t cap, int32_t* n) {
+    return locate_entry(ctx, HitQuery::last(source, cap, n), feats, n_feats, results, raw, maps, map_stride);
+}
+
 int fpm_locate_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
-    if (!ctx || !ms || !launches || !bytes) return FPM_E_INVALID_ARG;
-    const KProf& p = ctx->kp[kProfLocate];
-    *ms = p.ms;
-    *launches = p.launches;
-    *bytes = p.bytes;
-    return FPM_OK;
+    return kprof_out(ctx, kProfLocate, 0, 0, ms, launches, bytes);
 }
 
 int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count) {

@@ -256,6 +256,18 @@ def patch_poses(src_index, lts, angles):
     return idx, lt, ang
 
 
+def _ptr(a, ctype):
+    """``a``'s data as a ``ctype`` pointer (None stays NULL); the pointer keeps the array alive."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _pose_args(src_index, lts, angles):
+    """``(src_index*, lt*, angles*, n)`` as every fpm_*_at entry takes them, from patch_poses' arrays, which the
+    pointers keep alive."""
+    idx, lt, ang = patch_poses(src_index, lts, angles)
+    return _ptr(idx, C.c_int32), _ptr(lt, C.c_float), _ptr(ang, C.c_double), len(idx)
+
+
 def patch_matrix(src_w: int, src_h: int, lt, angle: float, rect_xy=(0, 0)) -> np.ndarray:
     """fpm_patch_matrix: the forward 2x3 matrix of the patch of a pose (ptLT ``lt`` as f32, ``angle`` in degrees) on a
     ``src_w`` x ``src_h`` source, for a rectangle whose origin is ``rect_xy`` in template coordinates.  Host only (no
@@ -1116,13 +1128,29 @@ class TemplateMatcher:
         self._check(rc, what)
         raise ValueError(f"{what} failed with {rc}: {self.last_error()}")
 
-    def _patch_count(self, r, source):
+    def _last(self, what, call, nulls, alloc, count_what=None):
+        """Count, then fill, of a last_* wrapper.  ``call(outs, cap, n)`` makes the C call with the output arguments
+        ``outs``: first with ``nulls`` and capacity 0, which gives the count (FPM_OK or FPM_E_CAPACITY);
+        ``alloc(count)`` then returns ``(results, outs)``, and the fill call runs only when there is a hit.  Returns
+        ``results``.
+        ``count_what``: the name in a failed count call's message when it is not ``what``."""
         n = C.c_int32()
-        rc = self._lib.fpm_last_patches(self._ctx, C.byref(r) if r is not None else None, int(source), None, 0, 0, 0,
-                                        C.byref(n), None)
+        rc = call(nulls, 0, C.byref(n))
         if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_patches")
-        return n.value
+            self._patch_fail(rc, count_what or what)
+        results, outs = alloc(n.value)
+        if n.value:
+            rc = call(outs, n.value, C.byref(n))
+            if rc != L.FPM_OK:
+                self._patch_fail(rc, what)
+        return results
+
+    def _profile(self, getter, *which, fail):
+        """``(ms, launches, bytes)`` of one fpm_*_profile getter; ValueError(``fail``) when it is rejected."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
+        if getter(self._ctx, *which, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
+            raise ValueError(fail)
+        return ms.value, n.value, b.value
 
     def _last_counts(self) -> np.ndarray:
         n = (C.c_int32 * max(self._staged, 1))()
@@ -1151,16 +1179,17 @@ class TemplateMatcher:
         launch (fpm_last_patches)."""
         r = self._patch_rect(rect)
         pr = C.byref(r) if r is not None else None
-        n = self._patch_count(r, source)
-        pw, ph = self.patch_size(rect)
-        out, row, patch = self._host_patch_out(out, n, ph, pw)
-        mats = np.zeros((n, 2, 3), np.float64)
-        if n:
-            got = C.c_int32()
-            rc = self._lib.fpm_last_patches(self._ctx, pr, int(source), L.u8ptr(out), row, patch, n, C.byref(got),
-                                            mats.ctypes.data_as(C.POINTER(C.c_double)))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_patches")
+
+        def call(o, cap, n):
+            return self._lib.fpm_last_patches(self._ctx, pr, int(source), o[0], o[1], o[2], cap, n, o[3])
+
+        def alloc(n):
+            pw, ph = self.patch_size(rect)
+            buf, row, patch = self._host_patch_out(out, n, ph, pw)
+            mats = np.zeros((n, 2, 3), np.float64)
+            return (buf, mats), (L.u8ptr(buf), row, patch, _ptr(mats, C.c_double))
+
+        out, mats = self._last("last_patches", call, (None, 0, 0, None), alloc)
         res = (out,) if source >= 0 else (out, self._last_counts())
         res = res + (mats,) if matrices else res
         return res[0] if len(res) == 1 else res
@@ -1175,26 +1204,31 @@ class TemplateMatcher:
         import torch
 
         r = self._patch_rect(rect)
-        n = self._patch_count(r, source)
-        pw, ph = self.patch_size(rect)
+        pr = C.byref(r) if r is not None else None
         dev = torch.device("cuda", self._device)
-        if out is None:
-            ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else torch.cuda.device(dev)
-            with ctx:
-                out = torch.empty((n, ph, pw), dtype=torch.uint8, device=dev)
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8:
-            raise TypeError("out must be a uint8 torch.Tensor")
-        if out.device != dev:
-            raise ValueError(f"out on {out.device}, context on {dev}")
-        self._check_one_runtime()
-        row, patch = patch_out_layout(tuple(out.shape), tuple(out.stride()), n, ph, pw)
-        if n:
-            got = C.c_int32()
-            rc = self._lib.fpm_last_patches_device(self._ctx, C.byref(r) if r is not None else None, int(source),
-                                                   out.data_ptr(), row, patch, n, C.byref(got),
-                                                   self._producer_stream(stream))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_patches_device")
+
+        def call(o, cap, n):
+            if o is None:                                   # the count comes from the host entry: no stream is touched
+                return self._lib.fpm_last_patches(self._ctx, pr, int(source), None, 0, 0, 0, n, None)
+            return self._lib.fpm_last_patches_device(self._ctx, pr, int(source), o[0], o[1], o[2], cap, n,
+                                                     self._producer_stream(stream))
+
+        def alloc(n):
+            pw, ph = self.patch_size(rect)
+            buf = out
+            if buf is None:
+                ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else torch.cuda.device(dev)
+                with ctx:
+                    buf = torch.empty((n, ph, pw), dtype=torch.uint8, device=dev)
+            if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8:
+                raise TypeError("out must be a uint8 torch.Tensor")
+            if buf.device != dev:
+                raise ValueError(f"out on {buf.device}, context on {dev}")
+            self._check_one_runtime()
+            row, patch = patch_out_layout(tuple(buf.shape), tuple(buf.stride()), n, ph, pw)
+            return buf, (buf.data_ptr(), row, patch)
+
+        out = self._last("last_patches_device", call, None, alloc, count_what="last_patches")
         return out if source >= 0 else (out, self._last_counts())
 
     def patches_at(self, src_index, lts, angles, rect=None, matrices: bool = False, out=None):
@@ -1203,16 +1237,14 @@ class TemplateMatcher:
         for all.  For results that no context holds, such as the merged results of an angle-sharded search.  Needs
         staged sources (stage / stage_device, or the source of the last match), not a search.  Returns uint8
         (n, ph, pw), with ``matrices`` also (n, 2, 3); ``out`` as last_patches."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         r = self._patch_rect(rect)
         pw, ph = self.patch_size(rect)
-        n = len(idx)
+        n = poses[3]
         out, row, patch = self._host_patch_out(out, n, ph, pw)
         mats = np.zeros((n, 2, 3), np.float64)
-        rc = self._lib.fpm_patches_at(self._ctx, C.byref(r) if r is not None else None,
-                                      idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
-                                      ang.ctypes.data_as(C.POINTER(C.c_double)), n, L.u8ptr(out), row, patch,
-                                      mats.ctypes.data_as(C.POINTER(C.c_double)))
+        rc = self._lib.fpm_patches_at(self._ctx, C.byref(r) if r is not None else None, *poses, L.u8ptr(out), row,
+                                      patch, _ptr(mats, C.c_double))
         if rc != L.FPM_OK:
             self._patch_fail(rc, "patches_at")
         return (out, mats) if matrices else out
@@ -1253,34 +1285,30 @@ class TemplateMatcher:
         r, w, h = self._compare_rect(rect)
         pr = C.byref(r) if r is not None else None
         flags = L.COMPARE_NORMALIZE if normalize else 0
-        n = C.c_int32()
-        rc = self._lib.fpm_last_compare(self._ctx, pr, int(source), int(threshold), flags, None, 0, C.byref(n), None, 0, 0)
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_compare")
-        stats = np.zeros(n.value, COMPARE_DTYPE)
-        img, pimg, row, patch = self._compare_diff(diff, n.value, h, w)
-        if n.value:
-            rc = self._lib.fpm_last_compare(self._ctx, pr, int(source), int(threshold), flags,
-                                            stats.ctypes.data_as(C.POINTER(L.CompareStats)), n.value, C.byref(n), pimg,
-                                            row, patch)
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_compare")
+
+        def call(o, cap, n):
+            return self._lib.fpm_last_compare(self._ctx, pr, int(source), int(threshold), flags, o[0], cap, n, *o[1:])
+
+        def alloc(n):
+            stats = np.zeros(n, COMPARE_DTYPE)
+            img, pimg, row, patch = self._compare_diff(diff, n, h, w)
+            return (stats, img), (_ptr(stats, L.CompareStats), pimg, row, patch)
+
+        stats, img = self._last("last_compare", call, (None, None, 0, 0), alloc)
         return (stats, img) if diff else stats
 
     def compare_at(self, src_index, lts, angles, rect=None, threshold: int = 16, normalize: bool = False,
                    diff: bool = False):
         """last_compare at poses the caller supplies, on the staged sources (fpm_compare_at); poses as patches_at.
         Needs staged sources, not a search."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         r, w, h = self._compare_rect(rect)
-        n = len(idx)
+        n = poses[3]
         stats = np.zeros(n, COMPARE_DTYPE)
         img, pimg, row, patch = self._compare_diff(diff, n, h, w)
-        rc = self._lib.fpm_compare_at(self._ctx, C.byref(r) if r is not None else None,
-                                      idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
-                                      ang.ctypes.data_as(C.POINTER(C.c_double)), n, int(threshold),
-                                      L.COMPARE_NORMALIZE if normalize else 0,
-                                      stats.ctypes.data_as(C.POINTER(L.CompareStats)), pimg, row, patch)
+        rc = self._lib.fpm_compare_at(self._ctx, C.byref(r) if r is not None else None, *poses, int(threshold),
+                                      L.COMPARE_NORMALIZE if normalize else 0, _ptr(stats, L.CompareStats), pimg, row,
+                                      patch)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "compare_at")
         return (stats, img) if diff else stats
@@ -1317,15 +1345,13 @@ class TemplateMatcher:
     def model_train_at(self, src_index, lts, angles, rect=None, normalize: bool = False) -> int:
         """model_train_last at poses the caller supplies, on the staged sources (fpm_model_train_at); poses as
         patches_at.  Needs staged sources, not a search."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         r, _, _ = self._compare_rect(rect)
-        rc = self._lib.fpm_model_train_at(self._ctx, C.byref(r) if r is not None else None,
-                                          idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
-                                          ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx),
+        rc = self._lib.fpm_model_train_at(self._ctx, C.byref(r) if r is not None else None, *poses,
                                           L.COMPARE_NORMALIZE if normalize else 0)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "model_train_at")
-        return len(idx)
+        return poses[3]
 
     def model_info(self):
         """``(n, (x, y, w, h))`` of the variation model: its sample count and rectangle; ``(0, None)`` without one."""
@@ -1372,33 +1398,29 @@ class TemplateMatcher:
         a, kq = model_thresholds(abs_threshold, k)
         w, h = self._model_size("last_inspect")
         flags = L.COMPARE_NORMALIZE if normalize else 0
-        n = C.c_int32()
-        rc = self._lib.fpm_last_inspect(self._ctx, int(source), a, kq, flags, None, 0, C.byref(n), None, 0, 0)
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_inspect")
-        stats = np.zeros(n.value, INSPECT_DTYPE)
-        img, pimg, row, patch = self._compare_diff(image, n.value, h, w)
-        if n.value:
-            rc = self._lib.fpm_last_inspect(self._ctx, int(source), a, kq, flags,
-                                            stats.ctypes.data_as(C.POINTER(L.InspectStats)), n.value, C.byref(n), pimg,
-                                            row, patch)
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_inspect")
+
+        def call(o, cap, n):
+            return self._lib.fpm_last_inspect(self._ctx, int(source), a, kq, flags, o[0], cap, n, *o[1:])
+
+        def alloc(n):
+            stats = np.zeros(n, INSPECT_DTYPE)
+            img, pimg, row, patch = self._compare_diff(image, n, h, w)
+            return (stats, img), (_ptr(stats, L.InspectStats), pimg, row, patch)
+
+        stats, img = self._last("last_inspect", call, (None, None, 0, 0), alloc)
         return (stats, img) if image else stats
 
     def inspect_at(self, src_index, lts, angles, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
                    image: bool = False):
         """last_inspect at poses the caller supplies, on the staged sources (fpm_inspect_at); poses as patches_at."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         a, kq = model_thresholds(abs_threshold, k)
         w, h = self._model_size("inspect_at")
-        n = len(idx)
+        n = poses[3]
         stats = np.zeros(n, INSPECT_DTYPE)
         img, pimg, row, patch = self._compare_diff(image, n, h, w)
-        rc = self._lib.fpm_inspect_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                      lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                      n, a, kq, L.COMPARE_NORMALIZE if normalize else 0,
-                                      stats.ctypes.data_as(C.POINTER(L.InspectStats)), pimg, row, patch)
+        rc = self._lib.fpm_inspect_at(self._ctx, *poses, a, kq, L.COMPARE_NORMALIZE if normalize else 0,
+                                      _ptr(stats, L.InspectStats), pimg, row, patch)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "inspect_at")
         return (stats, img) if image else stats
@@ -1416,38 +1438,31 @@ class TemplateMatcher:
         self._model_size("last_blobs")
         flags = L.COMPARE_NORMALIZE if normalize else 0
         args = (int(level), int(connectivity), int(min_area))
-        n = C.c_int32()
-        rc = self._lib.fpm_last_blobs(self._ctx, int(source), a, kq, flags, *args, None, None, None, int(cap), 0,
-                                      C.byref(n))
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_blobs")
-        rows = np.zeros(n.value, INSPECT_DTYPE)
-        summary, recs, _, _ = _blob_buffers(n.value, 0, 0, cap, False)
-        if n.value:
-            rc = self._lib.fpm_last_blobs(self._ctx, int(source), a, kq, flags, *args,
-                                          rows.ctypes.data_as(C.POINTER(L.InspectStats)),
-                                          summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
-                                          recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), n.value, C.byref(n))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_blobs")
+
+        def call(o, hits, n):
+            return self._lib.fpm_last_blobs(self._ctx, int(source), a, kq, flags, *args, *o, int(cap), hits, n)
+
+        def alloc(n):
+            rows = np.zeros(n, INSPECT_DTYPE)
+            summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
+            return (rows, summary, recs), (_ptr(rows, L.InspectStats), _ptr(summary, L.BlobSummary), _ptr(recs, L.Blob))
+
+        rows, summary, recs = self._last("last_blobs", call, (None, None, None), alloc)
         out = _blob_result(summary, recs, None, False)
         return out + (rows,) if stats else out
 
     def blobs_at(self, src_index, lts, angles, abs_threshold: int = 8, k: float = 3.0, normalize: bool = False,
                  level: int = 0, min_area: int = 4, connectivity: int = 8, cap: int = 64, stats: bool = False):
         """last_blobs at poses the caller supplies, on the staged sources (fpm_blobs_at); poses as patches_at."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         a, kq = model_thresholds(abs_threshold, k)
         self._model_size("blobs_at")
-        n = len(idx)
+        n = poses[3]
         rows = np.zeros(n, INSPECT_DTYPE)
         summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
-        rc = self._lib.fpm_blobs_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                    n, a, kq, L.COMPARE_NORMALIZE if normalize else 0, int(level), int(connectivity),
-                                    int(min_area), rows.ctypes.data_as(C.POINTER(L.InspectStats)),
-                                    summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
-                                    recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap))
+        rc = self._lib.fpm_blobs_at(self._ctx, *poses, a, kq, L.COMPARE_NORMALIZE if normalize else 0, int(level),
+                                    int(connectivity), int(min_area), _ptr(rows, L.InspectStats),
+                                    _ptr(summary, L.BlobSummary), _ptr(recs, L.Blob), int(cap))
         if rc != L.FPM_OK:
             self._patch_fail(rc, "blobs_at")
         out = _blob_result(summary, recs, None, False)
@@ -1488,10 +1503,7 @@ class TemplateMatcher:
     def blobs_profile(self, which: int):
         """``(ms, launches, bytes)`` of L.BLOB_TILE .. L.BLOB_FEATURES, collected under profile(True) and cleared by
         profile_reset (fpm_blobs_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_blobs_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError(f"fpm_blobs_profile({which}) failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_blobs_profile, int(which), fail=f"fpm_blobs_profile({which}) failed")
 
     def model_learn(self):
         """Learns the model's mean image as the new template, on the device (fpm_model_learn): re-teach from many good
@@ -1576,10 +1588,7 @@ class TemplateMatcher:
     def model_profile(self, which: int):
         """``(ms, launches, bytes)`` of L.MODEL_TRAIN / L.MODEL_PREPARE / L.MODEL_INSPECT, collected under profile(True)
         and cleared by profile_reset (fpm_model_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_model_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError(f"fpm_model_profile({which}) failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_model_profile, int(which), fail=f"fpm_model_profile({which}) failed")
 
     # -- pose alignment: every hit polished by least squares against the template (fpm_align_*) ---------------------
     def _align_rect(self, rect):
@@ -1607,14 +1616,11 @@ class TemplateMatcher:
         (fpm_align_sums_at): a structured array (ALIGN_SUMS_DTYPE) of exact integers -- n_used, the six entries of the
         normal matrix, the three of the gradient, ssd (include/fpm.h).  One launch of k_patch_align; poses as
         patches_at."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         r, _ = self._align_rect(rect)
-        out = np.zeros(len(idx), ALIGN_SUMS_DTYPE)
-        rc = self._lib.fpm_align_sums_at(self._ctx, C.byref(r) if r is not None else None,
-                                         idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
-                                         ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx),
-                                         L.COMPARE_NORMALIZE if normalize else 0,
-                                         out.ctypes.data_as(C.POINTER(L.AlignSums)))
+        out = np.zeros(poses[3], ALIGN_SUMS_DTYPE)
+        rc = self._lib.fpm_align_sums_at(self._ctx, C.byref(r) if r is not None else None, *poses,
+                                         L.COMPARE_NORMALIZE if normalize else 0, _ptr(out, L.AlignSums))
         if rc != L.FPM_OK:
             self._patch_fail(rc, "align_sums_at")
         return out
@@ -1623,14 +1629,12 @@ class TemplateMatcher:
                  normalize: bool = False) -> np.ndarray:
         """align_last from poses the caller supplies, on the staged sources (fpm_align_at); poses as patches_at.  Needs
         staged sources, not a search; nothing in the matcher changes."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         iters, max_step = self._align_args(iters, max_step)
         r, _ = self._align_rect(rect)
-        out = np.zeros(len(idx), ALIGN_DTYPE)
-        rc = self._lib.fpm_align_at(self._ctx, C.byref(r) if r is not None else None,
-                                    idx.ctypes.data_as(C.POINTER(C.c_int32)), lt.ctypes.data_as(C.POINTER(C.c_float)),
-                                    ang.ctypes.data_as(C.POINTER(C.c_double)), len(idx), iters, max_step,
-                                    L.COMPARE_NORMALIZE if normalize else 0, out.ctypes.data_as(C.POINTER(L.AlignResult)))
+        out = np.zeros(poses[3], ALIGN_DTYPE)
+        rc = self._lib.fpm_align_at(self._ctx, C.byref(r) if r is not None else None, *poses, iters, max_step,
+                                    L.COMPARE_NORMALIZE if normalize else 0, _ptr(out, L.AlignResult))
         if rc != L.FPM_OK:
             self._patch_fail(rc, "align_at")
         return out
@@ -1651,25 +1655,20 @@ class TemplateMatcher:
         r, _ = self._align_rect(rect)
         pr = C.byref(r) if r is not None else None
         flags = (L.COMPARE_NORMALIZE if normalize else 0) | (L.ALIGN_ADOPT if adopt else 0)
-        n = C.c_int32()
-        rc = self._lib.fpm_align_last(self._ctx, pr, int(source), iters, max_step, flags, None, 0, C.byref(n))
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "align_last")
-        out = np.zeros(n.value, ALIGN_DTYPE)
-        if n.value:
-            rc = self._lib.fpm_align_last(self._ctx, pr, int(source), iters, max_step, flags,
-                                          out.ctypes.data_as(C.POINTER(L.AlignResult)), n.value, C.byref(n))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "align_last")
-        return out
+
+        def call(o, cap, n):
+            return self._lib.fpm_align_last(self._ctx, pr, int(source), iters, max_step, flags, o, cap, n)
+
+        def alloc(n):
+            out = np.zeros(n, ALIGN_DTYPE)
+            return out, _ptr(out, L.AlignResult)
+
+        return self._last("align_last", call, None, alloc)
 
     def align_profile(self):
         """``(ms, launches, bytes)`` of k_patch_align, collected under profile(True) and cleared by profile_reset
         (fpm_align_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_align_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError("fpm_align_profile failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_align_profile, fail="fpm_align_profile failed")
 
     # -- edge calipers: edges measured across every hit, on the device (fpm_last_calipers / fpm_calipers_at) --------
     @staticmethod
@@ -1701,33 +1700,27 @@ class TemplateMatcher:
         pc = arr.ctypes.data_as(C.POINTER(L.Caliper))
         if int(cap) != cap or not 1 <= int(cap) <= L.CALIPER_MAX_CAP:
             raise ValueError(f"cap {cap!r} must be a whole number 1 .. {L.CALIPER_MAX_CAP}")
-        n = C.c_int32()
-        rc = self._lib.fpm_last_calipers(self._ctx, int(source), pc, len(arr), int(cap), None, None, None, 0, 0, C.byref(n))
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_calipers")
-        summary, edges, prof, stride = self._caliper_buffers(n.value, arr, cap, profiles)
-        if n.value:
-            rc = self._lib.fpm_last_calipers(self._ctx, int(source), pc, len(arr), int(cap),
-                                             summary.ctypes.data_as(C.POINTER(L.CaliperSummary)),
-                                             edges.ctypes.data_as(C.POINTER(L.Edge)),
-                                             prof.ctypes.data_as(C.POINTER(C.c_int32)) if profiles else None, stride,
-                                             n.value, C.byref(n))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_calipers")
+
+        def call(o, hits, n):
+            return self._lib.fpm_last_calipers(self._ctx, int(source), pc, len(arr), int(cap), *o, hits, n)
+
+        def alloc(n):
+            summary, edges, prof, stride = self._caliper_buffers(n, arr, cap, profiles)
+            return (summary, edges, prof), (_ptr(summary, L.CaliperSummary), _ptr(edges, L.Edge),
+                                            _ptr(prof, C.c_int32), stride)
+
+        summary, edges, prof = self._last("last_calipers", call, (None, None, None, 0), alloc)
         return (summary, edges, prof) if profiles else (summary, edges)
 
     def calipers_at(self, src_index, lts, angles, cals, cap: int = 8, profiles: bool = False):
         """last_calipers at poses the caller supplies, on the staged sources (fpm_calipers_at); poses as patches_at.
         Needs staged sources, not a search; nothing in the matcher changes."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         arr = _calipers(cals)
-        summary, edges, prof, stride = self._caliper_buffers(len(idx), arr, cap, profiles)
-        rc = self._lib.fpm_calipers_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                       lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                       len(idx), arr.ctypes.data_as(C.POINTER(L.Caliper)), len(arr), int(cap),
-                                       summary.ctypes.data_as(C.POINTER(L.CaliperSummary)),
-                                       edges.ctypes.data_as(C.POINTER(L.Edge)),
-                                       prof.ctypes.data_as(C.POINTER(C.c_int32)) if profiles else None, stride)
+        summary, edges, prof, stride = self._caliper_buffers(poses[3], arr, cap, profiles)
+        rc = self._lib.fpm_calipers_at(self._ctx, *poses, _ptr(arr, L.Caliper), len(arr), int(cap),
+                                       _ptr(summary, L.CaliperSummary), _ptr(edges, L.Edge), _ptr(prof, C.c_int32),
+                                       stride)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "calipers_at")
         return (summary, edges, prof) if profiles else (summary, edges)
@@ -1735,10 +1728,7 @@ class TemplateMatcher:
     def caliper_profile(self):
         """``(ms, launches, bytes)`` of k_caliper, collected under profile(True) and cleared by profile_reset
         (fpm_caliper_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_caliper_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError("fpm_caliper_profile failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_caliper_profile, fail="fpm_caliper_profile failed")
 
     # -- gray-value tools: histograms, Otsu and threshold blobs of every hit (fpm_*histogram* / fpm_*segment*) --------
     def _gray_rects(self, rects):
@@ -1763,27 +1753,23 @@ class TemplateMatcher:
         ones only.  Hits come in result order of ``source`` (``source=-1``: all sources), at the raw poses, or the aligned
         ones after align_last(adopt=True).  hist_derive turns them into mean, median, Otsu's threshold and so on."""
         arr, K = self._gray_rects(rects)
-        n = C.c_int32()
-        rc = self._lib.fpm_last_histogram(self._ctx, arr, K, int(source), None, 0, C.byref(n))
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_histogram")
-        hist = np.zeros((n.value, K, 256), np.uint32)
-        if n.value:
-            rc = self._lib.fpm_last_histogram(self._ctx, arr, K, int(source), hist.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              n.value, C.byref(n))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_histogram")
-        return hist
+
+        def call(o, cap, n):
+            return self._lib.fpm_last_histogram(self._ctx, arr, K, int(source), o, cap, n)
+
+        def alloc(n):
+            hist = np.zeros((n, K, 256), np.uint32)
+            return hist, _ptr(hist, C.c_uint32)
+
+        return self._last("last_histogram", call, None, alloc)
 
     def histogram_at(self, src_index, lts, angles, rects=None) -> np.ndarray:
         """last_histogram at poses the caller supplies, on the staged sources (fpm_histogram_at); poses as patches_at.
         Needs staged sources and a template, not a search."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         arr, K = self._gray_rects(rects)
-        hist = np.zeros((len(idx), K, 256), np.uint32)
-        rc = self._lib.fpm_histogram_at(self._ctx, arr, K, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                        lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                        len(idx), hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+        hist = np.zeros((poses[3], K, 256), np.uint32)
+        rc = self._lib.fpm_histogram_at(self._ctx, arr, K, *poses, _ptr(hist, C.c_uint32))
         if rc != L.FPM_OK:
             self._patch_fail(rc, "histogram_at")
         return hist
@@ -1802,41 +1788,34 @@ class TemplateMatcher:
         pr = C.byref(r) if r is not None else None
         t = _segment_threshold(threshold)
         args = (t, int(polarity), int(connectivity), int(min_area))
-        n = C.c_int32()
-        rc = self._lib.fpm_last_segment(self._ctx, int(source), pr, *args, None, None, None, int(cap), 0, C.byref(n),
-                                        None, 0, 0)
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_segment")
-        info = np.zeros(n.value, SEGMENT_INFO_DTYPE)
-        summary, recs, _, _ = _blob_buffers(n.value, 0, 0, cap, False)
-        img, pimg, row, patch = self._compare_diff(image, n.value, h, w)
-        if n.value:
-            rc = self._lib.fpm_last_segment(self._ctx, int(source), pr, *args,
-                                            info.ctypes.data_as(C.POINTER(L.SegmentInfo)),
-                                            summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
-                                            recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), n.value, C.byref(n), pimg,
-                                            row, patch)
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_segment")
+
+        def call(o, hits, n):
+            return self._lib.fpm_last_segment(self._ctx, int(source), pr, *args, *o[:3], int(cap), hits, n, *o[3:])
+
+        def alloc(n):
+            info = np.zeros(n, SEGMENT_INFO_DTYPE)
+            summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
+            img, pimg, row, patch = self._compare_diff(image, n, h, w)
+            return (info, summary, recs, img), (_ptr(info, L.SegmentInfo), _ptr(summary, L.BlobSummary),
+                                                _ptr(recs, L.Blob), pimg, row, patch)
+
+        info, summary, recs, img = self._last("last_segment", call, (None, None, None, None, 0, 0), alloc)
         out = (info,) + _blob_result(summary, recs, None, False)
         return out + (img,) if image else out
 
     def segment_at(self, src_index, lts, angles, rect=None, threshold="otsu", polarity: int = -1, min_area: int = 4,
                    connectivity: int = 8, cap: int = 64, image: bool = False):
         """last_segment at poses the caller supplies, on the staged sources (fpm_segment_at); poses as patches_at."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         r, w, h = self._compare_rect(rect)
-        n = len(idx)
+        n = poses[3]
         info = np.zeros(n, SEGMENT_INFO_DTYPE)
         summary, recs, _, _ = _blob_buffers(n, 0, 0, cap, False)
         img, pimg, row, patch = self._compare_diff(image, n, h, w)
-        rc = self._lib.fpm_segment_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                      lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                      n, C.byref(r) if r is not None else None, _segment_threshold(threshold),
-                                      int(polarity), int(connectivity), int(min_area),
-                                      info.ctypes.data_as(C.POINTER(L.SegmentInfo)),
-                                      summary.ctypes.data_as(C.POINTER(L.BlobSummary)),
-                                      recs.ctypes.data_as(C.POINTER(L.Blob)), int(cap), pimg, row, patch)
+        rc = self._lib.fpm_segment_at(self._ctx, *poses, C.byref(r) if r is not None else None,
+                                      _segment_threshold(threshold), int(polarity), int(connectivity), int(min_area),
+                                      _ptr(info, L.SegmentInfo), _ptr(summary, L.BlobSummary), _ptr(recs, L.Blob),
+                                      int(cap), pimg, row, patch)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "segment_at")
         out = (info,) + _blob_result(summary, recs, None, False)
@@ -1851,10 +1830,7 @@ class TemplateMatcher:
     def gray_profile(self, which: int):
         """``(ms, launches, bytes)`` of one gray-value kernel (L.GRAY_HIST, L.GRAY_THRESHOLD), collected under
         profile(True) and cleared by profile_reset (fpm_gray_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_gray_profile(self._ctx, int(which), C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError(f"gray_profile({which!r}) failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_gray_profile, int(which), fail=f"gray_profile({which!r}) failed")
 
     # -- sub-pattern locators: template regions found again on every hit (fpm_last_locate / fpm_locate_at) ------------
     @staticmethod
@@ -1887,33 +1863,25 @@ class TemplateMatcher:
         count), offsets row-major, zero behind a feature's own count.  A template mask is not honoured."""
         arr = _features(features)
         pf = arr.ctypes.data_as(C.POINTER(L.Feature))
-        n = C.c_int32()
-        rc = self._lib.fpm_last_locate(self._ctx, int(source), pf, len(arr), None, None, None, 0, 0, C.byref(n))
-        if rc not in (L.FPM_OK, L.FPM_E_CAPACITY):
-            self._patch_fail(rc, "last_locate")
-        res, rw, mp, stride = self._locate_buffers(n.value, arr, raw, maps)
-        if n.value:
-            rc = self._lib.fpm_last_locate(self._ctx, int(source), pf, len(arr),
-                                           res.ctypes.data_as(C.POINTER(L.LocateResult)),
-                                           rw.ctypes.data_as(C.POINTER(L.LocateRaw)) if raw else None,
-                                           mp.ctypes.data_as(C.POINTER(C.c_int32)) if maps else None, stride, n.value,
-                                           C.byref(n))
-            if rc != L.FPM_OK:
-                self._patch_fail(rc, "last_locate")
+
+        def call(o, cap, n):
+            return self._lib.fpm_last_locate(self._ctx, int(source), pf, len(arr), *o, cap, n)
+
+        def alloc(n):
+            res, rw, mp, stride = self._locate_buffers(n, arr, raw, maps)
+            return (res, rw, mp), (_ptr(res, L.LocateResult), _ptr(rw, L.LocateRaw), _ptr(mp, C.c_int32), stride)
+
+        res, rw, mp = self._last("last_locate", call, (None, None, None, 0), alloc)
         return self._locate_result(res, rw, mp, raw, maps)
 
     def locate_at(self, src_index, lts, angles, features, raw: bool = False, maps: bool = False):
         """last_locate at poses the caller supplies, on the staged sources (fpm_locate_at); poses as patches_at.  Needs
         staged sources and a template, not a search; nothing in the matcher changes."""
-        idx, lt, ang = patch_poses(src_index, lts, angles)
+        poses = _pose_args(src_index, lts, angles)
         arr = _features(features)
-        res, rw, mp, stride = self._locate_buffers(len(idx), arr, raw, maps)
-        rc = self._lib.fpm_locate_at(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                     lt.ctypes.data_as(C.POINTER(C.c_float)), ang.ctypes.data_as(C.POINTER(C.c_double)),
-                                     len(idx), arr.ctypes.data_as(C.POINTER(L.Feature)), len(arr),
-                                     res.ctypes.data_as(C.POINTER(L.LocateResult)),
-                                     rw.ctypes.data_as(C.POINTER(L.LocateRaw)) if raw else None,
-                                     mp.ctypes.data_as(C.POINTER(C.c_int32)) if maps else None, stride)
+        res, rw, mp, stride = self._locate_buffers(poses[3], arr, raw, maps)
+        rc = self._lib.fpm_locate_at(self._ctx, *poses, _ptr(arr, L.Feature), len(arr), _ptr(res, L.LocateResult),
+                                     _ptr(rw, L.LocateRaw), _ptr(mp, C.c_int32), stride)
         if rc != L.FPM_OK:
             self._patch_fail(rc, "locate_at")
         return self._locate_result(res, rw, mp, raw, maps)
@@ -1921,10 +1889,7 @@ class TemplateMatcher:
     def locate_profile(self):
         """``(ms, launches, bytes)`` of k_patch_locate, collected under profile(True) and cleared by profile_reset
         (fpm_locate_profile)."""
-        ms, n, b = C.c_double(), C.c_int64(), C.c_int64()
-        if self._lib.fpm_locate_profile(self._ctx, C.byref(ms), C.byref(n), C.byref(b)) != L.FPM_OK:
-            raise ValueError("fpm_locate_profile failed")
-        return ms.value, n.value, b.value
+        return self._profile(self._lib.fpm_locate_profile, fail="fpm_locate_profile failed")
 
     # -- pixel operators (fpm_op_*) ---------------------------------------------------------------------------
     def pyr_down(self, img) -> np.ndarray:

@@ -85,6 +85,14 @@ GRAY_KERNEL_SYMBOLS = ["k_patch_hist", "k_patch_threshold"]
 LOCATE_EDGE_X, LOCATE_EDGE_Y, LOCATE_FLAT, LOCATE_OUTSIDE = 1, 2, 4, 8
 LOCATE_MAX_SIDE, LOCATE_MAX_RADIUS, LOCATE_MAX_FEATURES, LOCATE_MAX_JOBS = 128, 16, 64, 65536
 LOCATE_KERNEL_SYMBOL = "k_patch_locate"
+# edge probes (fpm_probe_* / fpm_last_probes / fpm_probes_at / fpm_fit_*): select rules, flags and caps; the kernel has
+# no FPM_K_* index (fpm_probe_profile)
+PROBE_NEAREST, PROBE_STRONGEST, PROBE_FIRST, PROBE_LAST = 0, 1, 2, 3
+PROBE_OUTSIDE = 1
+PROBE_MIN_LENGTH, PROBE_MAX_LENGTH, PROBE_MAX_WIDTH, PROBE_MAX_HALF = 4, 64, 16, 8
+PROBE_MAX, PROBE_MAX_SLOTS = 4096, 1 << 22
+PROBE_KERNEL_SYMBOL = "k_probe"
+FIT_NOT_CONVERGED, FIT_COLLINEAR, FIT_TRIM_STARVED = 1, 2, 4
 
 
 class Params(C.Structure):
@@ -238,6 +246,54 @@ class LocateResult(C.Structure):
 
     _fields_ = [(n, C.c_int32) for n in ("dx", "dy", "flags", "reserved")] + \
                [(n, C.c_double) for n in ("score", "score_nominal", "ox", "oy", "tx", "ty", "sx", "sy")]
+
+
+class Probe(C.Structure):
+    """fpm_probe -- one edge probe: the nominal edge point and the scan direction, template frame."""
+
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("phi", C.c_double)]
+
+
+class ProbeParams(C.Structure):
+    """fpm_probe_params -- the size and rules all probes of a call share."""
+
+    _fields_ = [(n, C.c_int32) for n in ("length", "width", "half", "contrast", "polarity", "select")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
+class ProbeRaw(C.Structure):
+    """fpm_probe_raw -- what k_probe writes per (hit, probe): the selected edge's integers, the count, the flags."""
+
+    _fields_ = [(n, C.c_int32) for n in ("index", "n_edges", "d_prev", "d", "d_next", "flags")]
+
+
+class ProbeResult(C.Structure):
+    """fpm_probe_result -- what fpm_probe_derive makes of one raw record."""
+
+    _fields_ = [(n, C.c_int32) for n in ("index", "n_edges", "d", "flags")] + \
+               [(n, C.c_double) for n in ("dev", "contrast", "tx", "ty", "sx", "sy")]
+
+
+class ProbeSummary(C.Structure):
+    """fpm_probe_summary -- one hit: counts, the deviation sums and the hit's pose."""
+
+    _fields_ = [(n, C.c_int32) for n in ("n_found", "n_missing", "n_ambiguous", "n_outside", "worst", "reserved")] + \
+               [(n, C.c_double) for n in ("sum_dev", "sum_dev_sq", "max_abs_dev")] + \
+               [("lt_x", C.c_float), ("lt_y", C.c_float), ("angle", C.c_double)]
+
+
+class LineFit(C.Structure):
+    """fpm_line_fit -- fpm_fit_line's result."""
+
+    _fields_ = [(n, C.c_double) for n in ("angle", "px", "py", "rms", "max_resid")] + \
+               [("n_used", C.c_int32), ("flags", C.c_int32)]
+
+
+class CircleFit(C.Structure):
+    """fpm_circle_fit -- fpm_fit_circle's result."""
+
+    _fields_ = [(n, C.c_double) for n in ("cx", "cy", "r", "rms", "max_resid")] + \
+               [("n_used", C.c_int32), ("flags", C.c_int32)]
 
 
 class RoiRecord(C.Structure):
@@ -423,6 +479,20 @@ SIGNATURES = {
     "fpm_last_locate": (C.c_int, [_P, C.c_int32, C.POINTER(Feature), C.c_int32, C.POINTER(LocateResult),
                                   C.POINTER(LocateRaw), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_locate_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_probe_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.POINTER(Probe),
+                                   C.POINTER(ProbeParams), C.POINTER(C.c_double)]),
+    "fpm_probe_edges_host": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(ProbeParams), C.POINTER(ProbeRaw)]),
+    "fpm_probe_derive": (C.c_int, [C.POINTER(Probe), C.POINTER(ProbeParams), C.c_float, C.c_float, C.c_double,
+                                   C.POINTER(ProbeRaw), C.c_int32, C.POINTER(ProbeResult)]),
+    "fpm_probes_at": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32,
+                                C.POINTER(Probe), C.c_int32, C.POINTER(ProbeParams), C.POINTER(ProbeSummary),
+                                C.POINTER(ProbeResult), C.POINTER(C.c_int32), C.c_int32]),
+    "fpm_last_probes": (C.c_int, [_P, C.c_int32, C.POINTER(Probe), C.c_int32, C.POINTER(ProbeParams),
+                                  C.POINTER(ProbeSummary), C.POINTER(ProbeResult), C.POINTER(C.c_int32), C.c_int32,
+                                  C.c_int32, C.POINTER(C.c_int32)]),
+    "fpm_probe_profile": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fpm_fit_line": (C.c_int, [C.POINTER(C.c_double), C.c_int32, C.c_double, C.POINTER(LineFit)]),
+    "fpm_fit_circle": (C.c_int, [C.POINTER(C.c_double), C.c_int32, C.c_double, C.POINTER(CircleFit)]),
     "fpm_merge_candidates": (C.c_int, [C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(Candidate), C.c_int32,
                                        C.POINTER(Result), C.c_int32, C.POINTER(C.c_int32)]),
     "fpm_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32]),

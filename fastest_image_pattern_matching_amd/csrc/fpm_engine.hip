@@ -155,11 +155,11 @@ struct KProf {
 };
 // Profiling slots: one per FPM_K_* index (fpm_profile_get), then the variation model's three (fpm_model_profile) and the
 // alignment's one (fpm_align_profile), the blob labelling's five (fpm_blobs_profile), the calipers' one
-// (fpm_caliper_profile), the gray-value tools' two (fpm_gray_profile) and the locators' one (fpm_locate_profile), which
-// have no FPM_K_* index: FPM_K_COUNT stays what it is.
+// (fpm_caliper_profile), the gray-value tools' two (fpm_gray_profile), the locators' one (fpm_locate_profile) and the
+// probes' one (fpm_probe_profile), which have no FPM_K_* index: FPM_K_COUNT stays what it is.
 enum { kProfModelTrain = FPM_K_COUNT, kProfModelPrepare, kProfModelInspect, kProfAlign, kProfBlobTile, kProfBlobMerge,
        kProfBlobFlatten, kProfBlobSlots, kProfBlobFeatures, kProfCaliper, kProfGrayHist, kProfGrayThreshold, kProfLocate,
-       kProfSlots };
+       kProfProbe, kProfSlots };
 
 }  // namespace
 
@@ -260,6 +260,9 @@ struct fpm_ctx {
     // sub-pattern locators (fpm_last_locate / fpm_locate_at): the raw records and maps of a call and their host copy
     DevBuf d_locout;
     PinBuf h_locout;
+    // edge probes (fpm_last_probes / fpm_probes_at): the raw records and profiles of a call and their host copy
+    DevBuf d_probeout;
+    PinBuf h_probeout;
     // template mask (fpm_mask_*): one u8 plane of the template's level-0 size and row pitch, 0x00 /
     // 0xFF, zero behind a row's end; mask_host = its dense host copy (the counts, fpm_mask_get).  d_mask_in = the
     // staging buffer (a host mask's upload, the plane being staged, the count); a set that fails leaves d_mask alone.
@@ -3600,6 +3603,134 @@ int locate_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_
     return FPM_OK;
 }
 
+// ---- edge probes (fpm_last_probes, fpm_probes_at) ----
+static_assert(sizeof(fpm_probe) == 24 && sizeof(fpm_probe_params) == 32 && sizeof(fpm_probe_raw) == 24 &&
+              sizeof(fpm_probe_result) == 64 && sizeof(fpm_probe_summary) == 64, "the probe structs have no padding");
+static_assert(sizeof(ProbeRaw) == sizeof(fpm_probe_raw) && sizeof(ProbeFrame) == 32 && sizeof(PatchJob) == 64,
+              "the kernel's record is fpm_probe_raw, field for field; the job table is 64 hits + 32 n_probes bytes");
+static_assert(kProbeMaxLength == FPM_PROBE_MAX_LENGTH && kProbeMaxWidth == FPM_PROBE_MAX_WIDTH &&
+              kProbeMaxHalf == FPM_PROBE_MAX_HALF && kProbeMax == FPM_PROBE_MAX && kProbeOutside == FPM_PROBE_OUTSIDE &&
+              kProbeNearest == FPM_PROBE_NEAREST && kProbeLast == FPM_PROBE_LAST, "one set of caps and codes");
+
+// the rules of a call's probes and parameters that do not depend on the number of hits
+int probe_args(fpm_ctx* ctx, const fpm_probe* probes, int32_t n_probes, const fpm_probe_params* params) {
+    if (!probes || n_probes < 1 || n_probes > FPM_PROBE_MAX) { ctx->err = "1 .. 4096 probes expected"; return FPM_E_INVALID_ARG; }
+    if (!params) { ctx->err = "null probe parameters"; return FPM_E_INVALID_ARG; }
+    if (const char* bad = probe_params_bad(*params)) { ctx->err = bad; return FPM_E_INVALID_ARG; }
+    for (int k = 0; k < n_probes; ++k)
+        if (const char* bad = probe_bad(probes[k])) { ctx->err = bad; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+// and those that do: the outputs and the slots
+int probe_outputs(fpm_ctx* ctx, size_t hits, int32_t n_probes, const fpm_probe_params& p, const fpm_probe_summary* summary,
+                  const fpm_probe_result* results, const int32_t* profiles, int32_t stride) {
+    if (!summary || !results) { ctx->err = "null summary or result buffer"; return FPM_E_INVALID_ARG; }
+    if ((int64_t)hits * n_probes > FPM_PROBE_MAX_SLOTS) { ctx->err = "hits x probes above 2^22"; return FPM_E_INVALID_ARG; }
+    if (profiles && stride < p.length) { ctx->err = "profile_stride below the length"; return FPM_E_INVALID_ARG; }
+    return FPM_OK;
+}
+
+// The probes of `poses` (n >= 1), every argument checked: the job table -- one head per hit, then one frame per probe,
+// in the same pinned buffer -- one launch of k_probe, the raw records and profiles to pinned memory, every record
+// checked by probe_derive, then results, summaries and profiles into the caller's buffers.  Caller memory is written
+// only after the device pass has succeeded.  The host's work per (hit, probe) is the derivation of its one record.
+int probes_to_host(fpm_ctx* ctx, const std::vector<PatchPose>& poses, const fpm_probe* probes, int n_probes,
+                   const fpm_probe_params& prm, fpm_probe_summary* summary, fpm_probe_result* results, int32_t* profiles,
+                   int32_t stride) {
+    const int hits = (int)poses.size(), L = prm.length, W = prm.width;
+    const size_t njobs = (size_t)hits * (size_t)n_probes;
+    const size_t heads_b = sizeof(PatchJob) * (size_t)hits;
+    const size_t tab = round_up(heads_b + sizeof(ProbeFrame) * (size_t)n_probes, (size_t)256);
+    uint8_t* base = nullptr;
+    int rc = tab_begin(ctx, tab, &base);
+    if (rc != FPM_OK) return rc;
+    PatchJob* heads = (PatchJob*)base;
+    ProbeFrame* frames = (ProbeFrame*)(base + heads_b);
+    // the frames, and the box of every probe's sample grid in template coordinates
+    std::vector<ProbeGeom> geom((size_t)n_probes);
+    double bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+    for (int k = 0; k < n_probes; ++k) {
+        const ProbeGeom g = probe_geom(probes[k], prm);
+        geom[(size_t)k] = g;
+        frames[k] = ProbeFrame{g.cp, g.sp, g.ox, g.oy};
+        for (int e = 0; e < 4; ++e) {
+            const double u = (e & 1) ? L - 1 : 0, v = (e & 2) ? W - 1 : 0;
+            const double x = g.ox + (u * g.cp - v * g.sp), y = g.oy + (u * g.sp + v * g.cp);
+            if (k == 0 && e == 0) { bx0 = bx1 = x; by0 = by1 = y; }
+            bx0 = std::min(bx0, x); bx1 = std::max(bx1, x);
+            by0 = std::min(by0, y); by1 = std::max(by1, y);
+        }
+    }
+    const fpm_patch_rect origin{0, 0, 1, 1};
+    for (int i = 0; i < hits; ++i) {
+        rc = tab_head(ctx, heads[i], origin, poses[(size_t)i], i, (int64_t)i * n_probes);
+        if (rc != FPM_OK) return rc;
+        const double* M = heads[i].M;
+        for (int e = 0; e < 4; ++e) {   // the samplers' 2^20 range: the box's corners bound every sample of every probe
+            const double x = (e & 1) ? bx1 : bx0, y = (e & 2) ? by1 : by0;
+            const double sx = M[0] * x + M[1] * y + M[2], sy = M[3] * x + M[4] * y + M[5];
+            if (!(std::fabs(sx) < 1048576.0 && std::fabs(sy) < 1048576.0)) {
+                ctx->err = "pose " + std::to_string(i) + ": farther than 2^20 pixels from the source";
+                return FPM_E_INVALID_ARG;
+            }
+        }
+    }
+    // the device output: records, then the profiles at stride L (the caller's stride is the host's)
+    const size_t rec_b = round_up(sizeof(fpm_probe_raw) * njobs, (size_t)16);
+    const size_t prof_b = profiles ? sizeof(int32_t) * njobs * (size_t)L : 0;
+    HIP_TRY(ctx->d_probeout.ensure(rec_b + prof_b));
+    HIP_TRY(ctx->h_probeout.ensure(rec_b + prof_b));
+    rc = tab_send(ctx, tab);
+    if (rc != FPM_OK) return rc;
+    ProbeArgs a = source_args<ProbeArgs>(ctx, hits);
+    a.frames = (const ProbeFrame*)(ctx->d_patchtab.as<uint8_t>() + heads_b);
+    a.n_probes = n_probes;
+    a.L = L; a.W = W; a.s = prm.half;
+    a.thr = prm.contrast * prm.half * prm.width;
+    a.polarity = prm.polarity;
+    a.select = prm.select;
+    a.records = ctx->d_probeout.as<ProbeRaw>();
+    a.profiles = profiles ? ctx->d_probeout.as<int32_t>(rec_b) : nullptr;
+    {
+        // L W source pixels per (hit, probe) + the job table + the records and profiles written
+        ProfScope ps(ctx, kProfProbe, (int64_t)njobs * L * W + (int64_t)tab + (int64_t)(rec_b + prof_b));
+        if (!launch_probe(a, ctx->stream)) { ctx->err = "bad probe launch"; return FPM_E_INTERNAL; }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_probeout.p, ctx->d_probeout.p, rec_b + prof_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const fpm_probe_raw* raw = ctx->h_probeout.as<fpm_probe_raw>();
+    std::vector<fpm_probe_result> res(njobs);
+    for (int i = 0; i < hits; ++i) {   // what the device wrote is checked before anything of it reaches the caller
+        const RawPose& p = poses[(size_t)i].pose;
+        const double rad = p.angle * kD2R, ca = std::cos(rad), sa = std::sin(rad);
+        for (int k = 0; k < n_probes; ++k) {
+            const size_t j = (size_t)i * n_probes + k;
+            if ((raw[j].flags & ~FPM_PROBE_OUTSIDE) != 0 ||
+                !probe_derive(geom[(size_t)k], prm, p.x, p.y, ca, sa, raw[j], &res[j])) {
+                ctx->err = "k_probe returned a record that is no edge";
+                return FPM_E_INTERNAL;
+            }
+        }
+    }
+    std::memcpy(results, res.data(), sizeof(fpm_probe_result) * njobs);
+    for (int i = 0; i < hits; ++i) {
+        const RawPose& p = poses[(size_t)i].pose;
+        probe_summarise(res.data() + (size_t)i * n_probes, n_probes, p.x, p.y, p.angle, summary + i);
+    }
+    if (profiles) {
+        const int32_t* prof = ctx->h_probeout.as<int32_t>(rec_b);
+        for (size_t j = 0; j < njobs; ++j) {
+            int32_t* pj = profiles + j * (size_t)stride;
+            std::memcpy(pj, prof + j * (size_t)L, sizeof(int32_t) * (size_t)L);
+            if (stride > L) std::memset(pj + L, 0, sizeof(int32_t) * (size_t)(stride - L));
+        }
+    }
+    return FPM_OK;
+}
+
 // fpm_model_learn after its checks: the mean image written into level 0 of the template slab by k_model_prepare, then
 // the device learn's second half
 int learn_from_model(fpm_ctx* ctx) {
@@ -3693,6 +3824,7 @@ int fpm_destroy(fpm_ctx* ctx) {
     ctx->d_calout.release(); ctx->h_calout.release();
     ctx->d_gray.release(); ctx->h_gray.release();
     ctx->d_locout.release(); ctx->h_locout.release();
+    ctx->d_probeout.release(); ctx->h_probeout.release();
     ctx->d_mask.release(); ctx->d_mask_in.release();
     for (hipEvent_t e : {ctx->tab_ev, ctx->out_ev})
         if (e) (void)hipEventDestroy(e);
@@ -4693,6 +4825,44 @@ int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int3
 
 int fpm_locate_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
     return kprof_out(ctx, kProfLocate, 0, 0, ms, launches, bytes);
+}
+
+// --- edge probes (fpm_probe_matrix, fpm_probe_edges_host, fpm_probe_derive and the fits:
+// fpm_host.cpp) ------------------------------------------------------------------------------------------------------
+static int probes_entry(fpm_ctx* ctx, const HitQuery& q, const fpm_probe* probes, int32_t n_probes,
+                        const fpm_probe_params* params, fpm_probe_summary* summary, fpm_probe_result* results,
+                        int32_t* profiles, int32_t profile_stride) {
+    int rc = q.check(ctx);
+    if (rc == FPM_OK) rc = probe_args(ctx, probes, n_probes, params);
+    // intended, as for the calipers: a probe reads level 0 alone, so the caller's poses need no template
+    // (caliper_state); the last search's poses imply one (patch_state).  No rule ties a probe to the template's
+    // rectangle -- it may be drawn past the part -- so step 4 is empty.
+    if (rc == FPM_OK) rc = q.need_search() ? patch_state(ctx, true) : caliper_state(ctx);
+    std::vector<PatchPose> poses;
+    if (rc == FPM_OK) rc = q.resolve(ctx, "probe buffers too small", poses);
+    if (rc != FPM_OK || poses.empty()) return rc;
+    rc = probe_outputs(ctx, poses.size(), n_probes, *params, summary, results, profiles, profile_stride);
+    if (rc != FPM_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return probes_to_host(ctx, poses, probes, n_probes, *params, summary, results, profiles, profile_stride);
+}
+
+int fpm_probes_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                  const fpm_probe* probes, int32_t n_probes, const fpm_probe_params* params, fpm_probe_summary* summary,
+                  fpm_probe_result* results, int32_t* profiles, int32_t profile_stride) {
+    return probes_entry(ctx, HitQuery::at(src_index, lt, angles, n_poses), probes, n_probes, params, summary, results,
+                        profiles, profile_stride);
+}
+
+int fpm_last_probes(fpm_ctx* ctx, int32_t source, const fpm_probe* probes, int32_t n_probes, const fpm_probe_params* params,
+                    fpm_probe_summary* summary, fpm_probe_result* results, int32_t* profiles, int32_t profile_stride,
+                    int32_t cap, int32_t* n) {
+    return probes_entry(ctx, HitQuery::last(source, cap, n), probes, n_probes, params, summary, results, profiles,
+                        profile_stride);
+}
+
+int fpm_probe_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes) {
+    return kprof_out(ctx, kProfProbe, 0, 0, ms, launches, bytes);
 }
 
 int fpm_template_operands(const fpm_ctx* ctx, int8_t* t8, size_t* t8_bytes, int32_t* tsum, size_t* tsum_count) {

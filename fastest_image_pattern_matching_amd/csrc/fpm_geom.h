@@ -74,6 +74,18 @@ FPM_HD void patch_matrix(int src_w, int src_h, F2 lt, double c, double s, int rx
     M[5] -= ltr.y + (float)ry;
 }
 
+// An edge probe's sampling matrix (include/fpm.h, "edge probes"): the hit's inverted patch matrix M composed with the
+// probe's frame -- (cp, sp) the scan direction's cos and sin, (ox, oy) the template point of sample (0, 0) -- in the
+// header's order, every product and sum rounded once.  Host and device run these same lines.
+FPM_HD void probe_compose(const double M[6], double cp, double sp, double ox, double oy, double N[6]) {
+    N[0] = M[0] * cp + M[1] * sp;
+    N[1] = M[1] * cp - M[0] * sp;
+    N[2] = (M[0] * ox + M[1] * oy) + M[2];
+    N[3] = M[3] * cp + M[4] * sp;
+    N[4] = M[4] * cp - M[3] * sp;
+    N[5] = (M[3] * ox + M[4] * oy) + M[5];
+}
+
 // Fixed-point sampling constants of cv::warpAffine INTER_LINEAR.
 constexpr int kAbBits = 10, kAbScale = 1 << kAbBits, kInterBits = 5, kInterTab = 1 << kInterBits;
 constexpr int kRoundDelta = kAbScale / kInterTab / 2;

@@ -708,6 +708,211 @@ int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n) {
     return best;
 }
 
+// ---- edge probes (include/fpm.h, "edge probes"): every product and sum below is rounded on its own, in the header's
+// order.
+const char* probe_params_bad(const fpm_probe_params& p) {
+    if (p.length < FPM_PROBE_MIN_LENGTH || p.length > FPM_PROBE_MAX_LENGTH) return "probe: length must be 4 .. 64";
+    if (p.width < 1 || p.width > FPM_PROBE_MAX_WIDTH) return "probe: width must be 1 .. 16";
+    if (p.half < 1 || p.half > FPM_PROBE_MAX_HALF || 2 * p.half > p.length) return "probe: half must be 1 .. 8 with 2 half <= length";
+    if (p.contrast < 1 || p.contrast > 255) return "probe: contrast must be 1 .. 255";
+    if (p.polarity < -1 || p.polarity > 1) return "probe: polarity must be +1, -1 or 0";
+    if (p.select < FPM_PROBE_NEAREST || p.select > FPM_PROBE_LAST) return "probe: unknown select rule";
+    if (p.reserved[0] != 0 || p.reserved[1] != 0) return "probe: reserved must be 0";
+    return nullptr;
+}
+
+const char* probe_bad(const fpm_probe& k) {
+    if (!std::isfinite(k.x) || !std::isfinite(k.y) || !std::isfinite(k.phi)) return "probe: x, y and phi must be finite";
+    return nullptr;
+}
+
+ProbeGeom probe_geom(const fpm_probe& k, const fpm_probe_params& p) {
+    const double hl = (p.length - 1) / 2.0, hw = (p.width - 1) / 2.0;
+    const double rp = k.phi * kD2R, cp = std::cos(rp), sp = std::sin(rp);
+    return {cp, sp, k.x - (hl * cp - hw * sp), k.y - (hl * sp + hw * cp), hl, hw};
+}
+
+void probe_edges(const int32_t* profile, const fpm_probe_params& p, fpm_probe_raw* out) {
+    const int L = p.length, s = p.half, thr = p.contrast * p.half * p.width;
+    int32_t D[FPM_PROBE_MAX_LENGTH + 1] = {};   // D[0 .. L], 0 outside s .. L - s
+    for (int i = s; i <= L - s; ++i)
+        for (int j = 0; j < s; ++j) D[i] += profile[i + j] - profile[i - 1 - j];
+    int32_t n = 0, best = 0;
+    int64_t best_key = 0;
+    for (int i = s; i <= L - s; ++i) {
+        const int32_t d = D[i], dp = D[i - 1], dn = D[i + 1];
+        const bool up = d >= thr && d > dp && d >= dn, down = -d >= thr && d < dp && d <= dn;
+        if (!((p.polarity >= 0 && up) || (p.polarity <= 0 && down))) continue;
+        ++n;
+        // larger is better; a tie keeps the earlier index
+        const int64_t key = p.select == FPM_PROBE_NEAREST ? 128 - std::abs(2 * i - L)
+                          : p.select == FPM_PROBE_STRONGEST ? (int64_t)std::abs(d)
+                          : p.select == FPM_PROBE_FIRST ? 128 - i : i;
+        if (best == 0 || key > best_key) { best = i; best_key = key; }
+    }
+    *out = best ? fpm_probe_raw{best, n, D[best - 1], D[best], D[best + 1], 0} : fpm_probe_raw{0, 0, 0, 0, 0, 0};
+}
+
+bool probe_derive(const ProbeGeom& g, const fpm_probe_params& p, float lt_x, float lt_y, double ca, double sa,
+                  const fpm_probe_raw& r, fpm_probe_result* out) {
+    if (r.index == 0) {
+        if (r.n_edges != 0 || r.d_prev != 0 || r.d != 0 || r.d_next != 0) return false;
+        *out = fpm_probe_result{0, 0, 0, r.flags, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        return true;
+    }
+    if (r.d == 0 || r.index < p.half || r.index > p.length - p.half || r.n_edges < 1 || r.n_edges > p.length) return false;
+    const int64_t sg = r.d > 0 ? 1 : -1;
+    const int64_t am = sg * r.d_prev, a0 = sg * r.d, ap = sg * r.d_next;
+    if (!(am < a0 && ap <= a0)) return false;   // the local-maximum rule: den < 0 and delta in (-0.5, 0.5] follow
+    const int64_t den = (am - a0) + (ap - a0);
+    const double delta = 0.5 * (double)(am - ap) / (double)den;
+    const double t = ((double)r.index - 0.5) + delta;
+    const double tx = g.ox + (t * g.cp - g.hw * g.sp), ty = g.oy + (t * g.sp + g.hw * g.cp);
+    out->index = r.index; out->n_edges = r.n_edges; out->d = r.d; out->flags = r.flags;
+    out->dev = t - g.hl;
+    out->contrast = (double)a0 / (double)(p.half * p.width);
+    out->tx = tx; out->ty = ty;
+    out->sx = (double)lt_x + (tx * ca - ty * sa);
+    out->sy = (double)lt_y + (tx * sa + ty * ca);
+    return true;
+}
+
+void probe_summarise(const fpm_probe_result* res, int32_t n, float lt_x, float lt_y, double angle, fpm_probe_summary* out) {
+    fpm_probe_summary s{};
+    s.worst = -1;
+    s.lt_x = lt_x; s.lt_y = lt_y; s.angle = angle;
+    for (int32_t k = 0; k < n; ++k) {
+        const fpm_probe_result& r = res[k];
+        if (r.flags & FPM_PROBE_OUTSIDE) ++s.n_outside;
+        if (r.index < 1) { ++s.n_missing; continue; }
+        ++s.n_found;
+        if (r.n_edges > 1) ++s.n_ambiguous;
+        const double a = std::fabs(r.dev);
+        if (s.worst < 0 || a > s.max_abs_dev) { s.worst = k; s.max_abs_dev = a; }
+        s.sum_dev += r.dev;
+        s.sum_dev_sq += r.dev * r.dev;
+    }
+    *out = s;
+}
+
+namespace {
+// the fits' shared tail: rms and the largest |residual| over the points used
+void fit_residual_stats(const std::vector<double>& res, double* rms, double* max_resid) {
+    double ss = 0.0, mx = 0.0;
+    for (double r : res) {
+        ss += r * r;
+        if (std::fabs(r) > mx) mx = std::fabs(r);
+    }
+    *rms = std::sqrt(ss / (double)res.size());
+    *max_resid = mx;
+}
+
+bool fit_points_ok(const double* pts, int32_t n, int32_t least, double trim) {
+    if (!pts || n < least || !std::isfinite(trim) || trim < 0.0) return false;
+    for (int64_t i = 0; i < 2 * (int64_t)n; ++i)
+        if (!std::isfinite(pts[i])) return false;
+    return true;
+}
+
+// total least squares on the points idx of pts; res = the signed residuals in idx's order
+fpm_line_fit line_fit_once(const double* pts, const std::vector<int32_t>& idx, std::vector<double>& res) {
+    const double m = (double)idx.size();
+    double sx = 0.0, sy = 0.0;
+    for (int32_t i : idx) { sx += pts[2 * i]; sy += pts[2 * i + 1]; }
+    const double mx = sx / m, my = sy / m;
+    double sxx = 0.0, sxy = 0.0, syy = 0.0;
+    for (int32_t i : idx) {
+        const double dx = pts[2 * i] - mx, dy = pts[2 * i + 1] - my;
+        sxx += dx * dx; sxy += dx * dy; syy += dy * dy;
+    }
+    const double theta = 0.5 * std::atan2(2.0 * sxy, sxx - syy), c = std::cos(theta), s = std::sin(theta);
+    res.clear();
+    for (int32_t i : idx) {
+        const double dx = pts[2 * i] - mx, dy = pts[2 * i + 1] - my;
+        res.push_back(dy * c - dx * s);
+    }
+    fpm_line_fit f{};
+    f.angle = theta * kR2D;
+    const double along = mx * c + my * s;
+    f.px = mx - along * c;
+    f.py = my - along * s;
+    fit_residual_stats(res, &f.rms, &f.max_resid);
+    f.n_used = (int32_t)idx.size();
+    return f;
+}
+
+// Kasa's fit on centred coordinates, then at most 8 Gauss-Newton steps on the geometric residual
+fpm_circle_fit circle_fit_once(const double* pts, const std::vector<int32_t>& idx, std::vector<double>& res) {
+    const double m = (double)idx.size();
+    fpm_circle_fit f{};
+    f.n_used = (int32_t)idx.size();
+    double sx = 0.0, sy = 0.0;
+    for (int32_t i : idx) { sx += pts[2 * i]; sy += pts[2 * i + 1]; }
+    const double mx = sx / m, my = sy / m;
+    double suu = 0.0, suv = 0.0, svv = 0.0, suuu = 0.0, svvv = 0.0, suvv = 0.0, svuu = 0.0;
+    for (int32_t i : idx) {
+        const double u = pts[2 * i] - mx, v = pts[2 * i + 1] - my;
+        const double uu = u * u, vv = v * v;
+        suu += uu; suv += u * v; svv += vv;
+        suuu += uu * u; svvv += vv * v; suvv += u * vv; svuu += v * uu;
+    }
+    res.assign(idx.size(), 0.0);
+    const double det = suu * svv - suv * suv, tr = suu + svv;
+    if (!(det > 1e-12 * (tr * tr))) {
+        f.flags = FPM_FIT_COLLINEAR;
+        return f;
+    }
+    const double bu = 0.5 * (suuu + suvv), bv = 0.5 * (svvv + svuu);
+    double a = (bu * svv - bv * suv) / det, b = (bv * suu - bu * suv) / det;
+    double r = std::sqrt((a * a + b * b) + tr / m);
+    bool converged = false;
+    for (int it = 0; it < 8 && !converged; ++it) {
+        // the Jacobian's rows are (-ex, -ey, -1) and the residuals q = d - r: J^T J (da, db, dr) = -J^T q = (gx, gy, g1)
+        double jxx = 0.0, jxy = 0.0, jx1 = 0.0, jyy = 0.0, jy1 = 0.0, gx = 0.0, gy = 0.0, g1 = 0.0;
+        for (int32_t i : idx) {
+            const double du = (pts[2 * i] - mx) - a, dv = (pts[2 * i + 1] - my) - b;
+            const double d = std::sqrt(du * du + dv * dv);
+            const double ex = d > 0.0 ? du / d : 0.0, ey = d > 0.0 ? dv / d : 0.0, q = d - r;
+            jxx += ex * ex; jxy += ex * ey; jx1 += ex; jyy += ey * ey; jy1 += ey;
+            gx += ex * q; gy += ey * q; g1 += q;
+        }
+        // [jxx jxy jx1; jxy jyy jy1; jx1 jy1 m] (da, db, dr) = (gx, gy, g1), by Cramer's rule
+        const double c00 = jyy * m - jy1 * jy1, c01 = jxy * m - jy1 * jx1, c02 = jxy * jy1 - jyy * jx1;
+        const double dd = (jxx * c00 - jxy * c01) + jx1 * c02;
+        if (!(std::fabs(dd) > 0.0) || !std::isfinite(dd)) break;
+        const double da = ((gx * c00 - jxy * (gy * m - jy1 * g1)) + jx1 * (gy * jy1 - jyy * g1)) / dd;
+        const double db = ((jxx * (gy * m - jy1 * g1) - gx * c01) + jx1 * (jxy * g1 - gy * jx1)) / dd;
+        const double dr = ((jxx * (jyy * g1 - gy * jy1) - jxy * (jxy * g1 - gy * jx1)) + gx * c02) / dd;
+        a += da; b += db; r += dr;
+        converged = std::fabs(da) <= 1e-10 && std::fabs(db) <= 1e-10 && std::fabs(dr) <= 1e-10;
+    }
+    if (!converged) f.flags |= FPM_FIT_NOT_CONVERGED;
+    size_t k = 0;
+    for (int32_t i : idx) {
+        const double du = (pts[2 * i] - mx) - a, dv = (pts[2 * i + 1] - my) - b;
+        res[k++] = std::sqrt(du * du + dv * dv) - r;
+    }
+    f.cx = mx + a; f.cy = my + b; f.r = r;
+    fit_residual_stats(res, &f.rms, &f.max_resid);
+    return f;
+}
+
+// fit, drop the points beyond trim, fit the rest once more
+template <class Fit, class Once>
+Fit fit_trimmed(const double* pts, int32_t n, double trim, int32_t least, Once once) {
+    std::vector<int32_t> idx((size_t)n), kept;
+    for (int32_t i = 0; i < n; ++i) idx[(size_t)i] = i;
+    std::vector<double> res;
+    Fit f = once(pts, idx, res);
+    if (!(trim > 0.0)) return f;
+    for (size_t k = 0; k < idx.size(); ++k)
+        if (!(std::fabs(res[k]) > trim)) kept.push_back(idx[k]);
+    if (kept.size() == idx.size()) return f;
+    if ((int32_t)kept.size() < least) { f.flags |= FPM_FIT_TRIM_STARVED; return f; }
+    return once(pts, kept, res);
+}
+}  // namespace
+
 // ---- gray-value tools (include/fpm.h, "gray-value tools"): integers first, then f64 in the header's order; the file is
 // built with -ffp-contract=off, so B's two products and its quotient are three roundings.
 bool hist_derive(const uint32_t hist[256], fpm_hist_stats* out) {
@@ -908,6 +1113,56 @@ int fpm_caliper_derive(const fpm_caliper* cal, float ltk_x, float ltk_y, double 
     for (int32_t i = 0; i < n; ++i)   // every record is checked before the first is written
         if (!fpm::caliper_derive(*cal, ltk_x, ltk_y, angle_k, raw[i], &e)) return FPM_E_INVALID_ARG;
     for (int32_t i = 0; i < n; ++i) (void)fpm::caliper_derive(*cal, ltk_x, ltk_y, angle_k, raw[i], out + i);
+    return FPM_OK;
+}
+
+int fpm_probe_matrix(int32_t src_w, int32_t src_h, float lt_x, float lt_y, double angle, const fpm_probe* probe,
+                     const fpm_probe_params* params, double n[6]) {
+    if (!probe || !params || !n || src_w <= 0 || src_h <= 0 || fpm::probe_params_bad(*params) || fpm::probe_bad(*probe) ||
+        !std::isfinite(lt_x) || !std::isfinite(lt_y) || !std::isfinite(angle))
+        return FPM_E_INVALID_ARG;
+    const double rad = angle * fpm::kD2R;
+    double M[6];
+    fpm::patch_matrix(src_w, src_h, fpm::f2(lt_x, lt_y), std::cos(rad), std::sin(rad), 0, 0, M);
+    fpm::invert_affine(M);
+    const fpm::ProbeGeom g = fpm::probe_geom(*probe, *params);
+    fpm::probe_compose(M, g.cp, g.sp, g.ox, g.oy, n);
+    return FPM_OK;
+}
+
+int fpm_probe_edges_host(const int32_t* profile, const fpm_probe_params* params, fpm_probe_raw* out) {
+    if (!profile || !params || !out || fpm::probe_params_bad(*params)) return FPM_E_INVALID_ARG;
+    for (int32_t u = 0; u < params->length; ++u)
+        if (profile[u] < 0 || profile[u] > 255 * params->width) return FPM_E_INVALID_ARG;   // of no width pixels
+    fpm::probe_edges(profile, *params, out);
+    return FPM_OK;
+}
+
+int fpm_probe_derive(const fpm_probe* probes, const fpm_probe_params* params, float lt_x, float lt_y, double angle,
+                     const fpm_probe_raw* raw, int32_t n, fpm_probe_result* out) {
+    if (!params || n < 0 || (n > 0 && (!probes || !raw || !out)) || fpm::probe_params_bad(*params) || !std::isfinite(lt_x) ||
+        !std::isfinite(lt_y) || !std::isfinite(angle))
+        return FPM_E_INVALID_ARG;
+    const double rad = angle * fpm::kD2R, ca = std::cos(rad), sa = std::sin(rad);
+    fpm_probe_result r;
+    for (int32_t i = 0; i < n; ++i)   // every probe and record is checked before the first result is written
+        if (fpm::probe_bad(probes[i]) ||
+            !fpm::probe_derive(fpm::probe_geom(probes[i], *params), *params, lt_x, lt_y, ca, sa, raw[i], &r))
+            return FPM_E_INVALID_ARG;
+    for (int32_t i = 0; i < n; ++i)
+        (void)fpm::probe_derive(fpm::probe_geom(probes[i], *params), *params, lt_x, lt_y, ca, sa, raw[i], out + i);
+    return FPM_OK;
+}
+
+int fpm_fit_line(const double* pts, int32_t n, double trim, fpm_line_fit* out) {
+    if (!out || !fpm::fit_points_ok(pts, n, 2, trim)) return FPM_E_INVALID_ARG;
+    *out = fpm::fit_trimmed<fpm_line_fit>(pts, n, trim, 2, fpm::line_fit_once);
+    return FPM_OK;
+}
+
+int fpm_fit_circle(const double* pts, int32_t n, double trim, fpm_circle_fit* out) {
+    if (!out || !fpm::fit_points_ok(pts, n, 3, trim)) return FPM_E_INVALID_ARG;
+    *out = fpm::fit_trimmed<fpm_circle_fit>(pts, n, trim, 3, fpm::circle_fit_once);
     return FPM_OK;
 }
 

@@ -77,6 +77,24 @@ int32_t caliper_edges(const int32_t* profile, const fpm_caliper& k, int32_t cap,
 bool caliper_derive(const fpm_caliper& k, float ltk_x, float ltk_y, double angle_k, const fpm_edge_raw& r, fpm_edge* e);
 // the returned record with the largest |d|, the earliest on ties; -1 for n = 0
 int32_t caliper_strongest(const fpm_edge_raw* r, int32_t n);
+// ---- edge probes (include/fpm.h, "edge probes"): the host half the probe entries share ----
+// the range rules of a call's parameters and of one probe; nullptr = fine, else what is wrong
+const char* probe_params_bad(const fpm_probe_params& p);
+const char* probe_bad(const fpm_probe& k);
+// what a probe contributes to the sampling matrix and the derivation: cos and sin of phi, the template point of
+// sample (0, 0), hl and hw
+struct ProbeGeom {
+    double cp, sp, ox, oy, hl, hw;
+};
+ProbeGeom probe_geom(const fpm_probe& k, const fpm_probe_params& p);
+// the step, edge and select rules on a profile of p.length entries into *out (flags = 0)
+void probe_edges(const int32_t* profile, const fpm_probe_params& p, fpm_probe_raw* out);
+// one raw record of a probe with geometry g on a hit at lt whose angle has the cos and sin (ca, sa) into *out; false
+// (nothing written) for a record that is no edge.  The geometry is formed once per probe and the trig once per hit.
+bool probe_derive(const ProbeGeom& g, const fpm_probe_params& p, float lt_x, float lt_y, double ca, double sa,
+                  const fpm_probe_raw& r, fpm_probe_result* out);
+// a hit's summary from its n results in ascending probe index
+void probe_summarise(const fpm_probe_result* res, int32_t n, float lt_x, float lt_y, double angle, fpm_probe_summary* out);
 // ---- gray-value tools (include/fpm.h, "gray-value tools") ----
 // the statistics and Otsu's threshold of one histogram by the header's rule; false (nothing written) when its total
 // exceeds 2^22

@@ -356,6 +356,37 @@ struct CaliperArgs {
 };
 // k_caliper: one workgroup per job.  Returns false, launching nothing, for a capacity outside its range.
 bool launch_caliper(const CaliperArgs& a, hipStream_t st);
+// ---- edge probes (fpm_last_probes / fpm_probes_at): thousands of short calipers per hit that
+// share one size and one set of rules and report one edge each.  The job table is one PatchJob head per hit (the
+// inverted matrix of the template frame and the source) and one ProbeFrame per probe; k_probe composes the two.
+constexpr int kProbeMaxLength = 64, kProbeMaxWidth = 16, kProbeMaxHalf = 8, kProbeMax = 4096;
+constexpr int kProbeOutside = 1;                      // FPM_PROBE_OUTSIDE
+enum { kProbeNearest, kProbeStrongest, kProbeFirst, kProbeLast };   // FPM_PROBE_NEAREST ..
+struct ProbeFrame {
+    double cp, sp;           // cos and sin of the scan direction
+    double ox, oy;           // the template point of sample (0, 0)
+};
+struct ProbeRaw {            // fpm_probe_raw, field for field
+    int32_t index, n_edges, d_prev, d, d_next, flags;
+};
+struct ProbeArgs {
+    const PatchJob* jobs;    // [njobs]: one head per hit; out_off unused (hit h's records start at h * n_probes)
+    int32_t njobs;           // hits
+    const uint8_t* level0;   // as PatchArgs
+    size_t img_stride;
+    int32_t sw, sh, sp;
+    const ProbeFrame* frames;   // [n_probes]
+    int32_t n_probes;
+    int32_t L, W, s;         // length, width, half
+    int32_t thr;             // c s W: the least |D| of an edge
+    int32_t polarity;        // +1, -1, 0 = both
+    int32_t select;          // kProbeNearest ..
+    ProbeRaw* records;       // [njobs][n_probes]
+    int32_t* profiles;       // [njobs][n_probes][L] or null
+};
+// k_probe: one wave per (hit, probe), four probes of a hit per workgroup.  Returns false, launching nothing, for a
+// parameter outside its range, a null output or a grid past 2^31 - 1.
+bool launch_probe(const ProbeArgs& a, hipStream_t st);
 // ---- gray-value tools (fpm_last_histogram / fpm_histogram_at / fpm_last_segment / fpm_segment_at, DESIGN.md section
 // 23): the 256-bin histogram of a (hit, rectangle) patch that is never written, and the patch thresholded into the u8
 // image e that the labelling kernels take.  One descriptor per job serves both kernels, built on the host.

@@ -3359,6 +3359,99 @@ bool launch_caliper(const CaliperArgs& a, hipStream_t st) {
     return true;
 }
 
+// ============================================================================================== edge probes
+// k_probe (fpm_last_probes / fpm_probes_at): one 64-lane wave owns one (hit, probe), a workgroup
+// four consecutive probes of one hit; grid = hits x ceil(n_probes / 4).  The wave composes its sampling matrix from the
+// hit's head and the probe's frame (probe_compose, f64, the host's lines), then lane u owns column u of the L x W
+// grid: W tap sets through warp_tap straight from global memory -- a probe's footprint is a few cache lines that
+// neighbouring probes of a contour share, so no LDS footprint is staged.  With L <= 32 the upper half-wave takes the
+// odd rows of column lane - 32 and the halves are folded once across lanes; the integers are the same either way.
+// The profile stays in registers: P[u] in lane u, D[i] in lane i from the 2 s cross-lane reads of the definition, the
+// neighbours D[i - 1] and D[i + 1] by two more (D[64] = 0 by definition: i <= L - s).  One edge is selected by a wave
+// maximum over an integer key that carries the index, so ties are resolved in the key and the result is order-free;
+// the winning lane (lane 0 when there is no edge) stores the 24-byte record.  FPM_PROBE_OUTSIDE comes from the four
+// corner samples' tap origins, tested where they are sampled and met by one ballot.  Nothing is shared between waves:
+// no LDS, no barrier, no atomic; a wave past n_probes leaves at once.  Every cross-lane read below is executed by all
+// 64 lanes: the loop bounds are kernel arguments.
+__global__ __launch_bounds__(256) void k_probe(const ProbeArgs c) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int groups = (c.n_probes + 3) >> 2;
+    const int hit = (int)(blockIdx.x / (unsigned)groups);
+    const int k = ((int)blockIdx.x - hit * groups) * 4 + wave;
+    if (k >= c.n_probes) return;
+    const PatchJob& J = c.jobs[hit];
+    const ProbeFrame& F = c.frames[k];
+    double N[6];
+    probe_compose(J.M, F.cp, F.sp, F.ox, F.oy, N);
+    const uint8_t* img = c.level0 + c.img_stride * (size_t)J.src;
+    const int L = c.L, W = c.W, s = c.s;
+    const bool split = L <= 32;
+    const int u = split ? (lane & 31) : lane;
+    const int v0 = split ? (lane >> 5) : 0, dv = split ? 2 : 1;
+    const int ad = rint_i(N[0] * u * kAbScale), bd = rint_i(N[3] * u * kAbScale);
+    int P = 0;
+    bool outside = false;
+    if (u < L) {
+        for (int v = v0; v < W; v += dv) {
+            const int X0 = rint_i((N[1] * v + N[2]) * kAbScale) + kRoundDelta;
+            const int Y0 = rint_i((N[4] * v + N[5]) * kAbScale) + kRoundDelta;
+            const int X = (X0 + ad) >> (kAbBits - kInterBits), Y = (Y0 + bd) >> (kAbBits - kInterBits);
+            P += warp_tap(img, c.sw, c.sh, c.sp, X, Y, 0);
+            if ((u == 0 || u == L - 1) && (v == 0 || v == W - 1)) {
+                const int sx = X >> kInterBits, sy = Y >> kInterBits;
+                outside = outside || sx < 0 || sx > c.sw - 2 || sy < 0 || sy > c.sh - 2;
+            }
+        }
+    }
+    if (split) P += __shfl_xor(P, 32);
+    if (lane >= L) P = 0;
+    const int flags = __ballot(outside) != 0ull ? kProbeOutside : 0;
+    const size_t job = (size_t)hit * (size_t)c.n_probes + (size_t)k;
+    if (c.profiles && lane < L) c.profiles[job * (size_t)L + lane] = P;
+    // D[i] in lane i, 0 outside s .. L - s
+    const bool in = lane >= s && lane <= L - s;
+    int D = 0;
+    for (int j = 0; j < s; ++j) {
+        const int hi = __shfl(P, (lane + j) & 63), lo = __shfl(P, (lane - 1 - j) & 63);
+        if (in) D += hi - lo;
+    }
+    const int dp = __shfl(D, (lane - 1) & 63);
+    int dn = __shfl(D, (lane + 1) & 63);
+    if (lane == 63) dn = 0;
+    const bool up = D >= c.thr && D > dp && D >= dn, down = -D >= c.thr && D < dp && D <= dn;
+    const bool e = in && ((c.polarity >= 0 && up) || (c.polarity <= 0 && down));
+    const int n_edges = __popcll(__ballot(e));
+    // the key of an edge is positive and carries its index: the maximum names one lane
+    int key = 0;
+    if (e) {
+        const int dist = 2 * lane - L, low = 127 - lane;
+        if (c.select == kProbeNearest) key = ((128 - (dist < 0 ? -dist : dist)) << 7) | low;
+        else if (c.select == kProbeStrongest) key = ((D < 0 ? -D : D) << 7) | low;
+        else if (c.select == kProbeFirst) key = low;
+        else key = lane;
+    }
+    int best = key;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) best = max(best, __shfl_xor(best, m));
+    if (best == 0) {
+        if (lane == 0) c.records[job] = ProbeRaw{0, 0, 0, 0, 0, flags};
+    } else if (e && key == best) {
+        c.records[job] = ProbeRaw{lane, n_edges, dp, D, dn, flags};
+    }
+}
+
+bool launch_probe(const ProbeArgs& a, hipStream_t st) {
+    if (a.njobs <= 0) return true;
+    if (a.n_probes < 1 || a.n_probes > kProbeMax || a.L < 4 || a.L > kProbeMaxLength || a.W < 1 || a.W > kProbeMaxWidth ||
+        a.s < 1 || a.s > kProbeMaxHalf || 2 * a.s > a.L || a.select < kProbeNearest || a.select > kProbeLast ||
+        a.polarity < -1 || a.polarity > 1 || !a.jobs || !a.frames || !a.records)
+        return false;
+    const int64_t grid = (int64_t)a.njobs * ((a.n_probes + 3) / 4);
+    if (grid > (int64_t)INT32_MAX) return false;
+    hipLaunchKernelGGL(k_probe, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return true;
+}
+
 // ============================================================================================== gray-value tools
 // k_patch_hist (fpm_last_histogram / fpm_histogram_at and the Otsu half of fpm_last_segment / fpm_segment_at, DESIGN.md
 // section 23): the 256-bin histogram of every (hit, rectangle) job's patch, none of them written.  A job has its own

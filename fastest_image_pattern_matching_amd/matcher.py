@@ -595,6 +595,245 @@ def caliper_derive(cal, lt_k, angle_k: float, raw) -> np.ndarray:
     return out
 
 
+# -- edge probes (fpm_probe_* / fpm_last_probes / fpm_probes_at / fpm_fit_*): an outline measured on every hit --------
+# fpm_probe, fpm_probe_params, fpm_probe_raw, fpm_probe_result and fpm_probe_summary, field for field
+PROBE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Probe._fields_], align=True)
+PROBE_PARAMS_DTYPE = np.dtype([("length", "<i4"), ("width", "<i4"), ("half", "<i4"), ("contrast", "<i4"),
+                               ("polarity", "<i4"), ("select", "<i4"), ("reserved", "<i4", (2,))], align=True)
+PROBE_RAW_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.ProbeRaw._fields_], align=True)
+PROBE_RESULT_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.ProbeResult._fields_], align=True)
+PROBE_SUMMARY_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.ProbeSummary._fields_], align=True)
+assert PROBE_DTYPE.itemsize == C.sizeof(L.Probe) == 24 and PROBE_PARAMS_DTYPE.itemsize == C.sizeof(L.ProbeParams) == 32
+assert PROBE_RAW_DTYPE.itemsize == C.sizeof(L.ProbeRaw) == 24 and PROBE_RESULT_DTYPE.itemsize == C.sizeof(L.ProbeResult) == 64
+assert PROBE_SUMMARY_DTYPE.itemsize == C.sizeof(L.ProbeSummary) == 64
+_PROBE_SELECT = {"nearest": L.PROBE_NEAREST, "strongest": L.PROBE_STRONGEST, "first": L.PROBE_FIRST, "last": L.PROBE_LAST}
+
+
+def probe(x: float, y: float, phi: float) -> np.ndarray:
+    """One edge probe as a PROBE_DTYPE record: the nominal edge point (x, y) in template coordinates, which is the
+    centre of the probe's sample grid, and the scan direction ``phi`` in degrees in the template's frame (0 = along
+    +x).  Raises ValueError for a value that is not finite.  Pure: no device."""
+    if not (np.isfinite(x) and np.isfinite(y) and np.isfinite(phi)):
+        raise ValueError("x, y and phi must be finite")
+    rec = np.zeros((), PROBE_DTYPE)
+    rec["x"], rec["y"], rec["phi"] = float(x), float(y), float(phi)
+    return rec
+
+
+def probe_params(length: int, width: int, half: int = 2, contrast: int = 12, polarity: int = 0,
+                 select="nearest") -> np.ndarray:
+    """The size and rules all probes of a call share, as a PROBE_PARAMS_DTYPE record: ``length`` 4 .. 64 samples along
+    the scan and ``width`` 1 .. 16 across it, ``half`` 1 .. 8 samples summed on each side of a boundary (2 half <=
+    length), the least step ``contrast`` 1 .. 255 in gray levels, ``polarity`` +1 (dark to bright along the scan), -1
+    or 0 (both), and ``select``: "nearest" (to the nominal point), "strongest", "first" or "last" along the scan, or
+    the L.PROBE_* code.  Raises ValueError outside the ranges of include/fpm.h.  Pure: no device."""
+    sel = _PROBE_SELECT.get(select, select) if isinstance(select, str) else select
+    vals = [int(v) for v in (length, width, half, contrast, polarity)]
+    if vals != [length, width, half, contrast, polarity]:
+        raise ValueError("length, width, half, contrast and polarity must be whole numbers")
+    length, width, half, contrast, polarity = vals
+    if not L.PROBE_MIN_LENGTH <= length <= L.PROBE_MAX_LENGTH or not 1 <= width <= L.PROBE_MAX_WIDTH:
+        raise ValueError(f"length {length} must be {L.PROBE_MIN_LENGTH} .. {L.PROBE_MAX_LENGTH}, "
+                         f"width {width} 1 .. {L.PROBE_MAX_WIDTH}")
+    if not 1 <= half <= L.PROBE_MAX_HALF or 2 * half > length:
+        raise ValueError(f"half {half} must be 1 .. {L.PROBE_MAX_HALF} with 2 half <= length")
+    if not 1 <= contrast <= 255 or polarity not in (-1, 0, 1):
+        raise ValueError("contrast must be 1 .. 255 and polarity +1, -1 or 0")
+    if sel not in _PROBE_SELECT.values():
+        raise ValueError(f"select {select!r} must be one of {sorted(_PROBE_SELECT)}")
+    rec = np.zeros((), PROBE_PARAMS_DTYPE)
+    rec["length"], rec["width"], rec["half"], rec["contrast"], rec["polarity"] = length, width, half, contrast, polarity
+    rec["select"] = int(sel)
+    return rec
+
+
+def _probes(probes, most=L.PROBE_MAX) -> np.ndarray:
+    """A contiguous PROBE_DTYPE array of one or more probes (records of probe(), or such an array)."""
+    if isinstance(probes, np.ndarray) and probes.dtype == PROBE_DTYPE:
+        arr = np.ascontiguousarray(probes).reshape(-1)
+    else:
+        arr = np.array([np.asarray(p, PROBE_DTYPE).reshape(()) for p in probes], PROBE_DTYPE).reshape(-1)
+    if not 1 <= arr.size <= most:
+        raise ValueError(f"1 .. {most} probes expected, got {arr.size}")
+    return arr
+
+
+def _probe_params_ptr(params):
+    arr = np.ascontiguousarray(np.asarray(params, PROBE_PARAMS_DTYPE)).reshape(-1)
+    if arr.size != 1:
+        raise ValueError("one probe_params record expected")
+    return arr, arr.ctypes.data_as(C.POINTER(L.ProbeParams))
+
+
+def probe_matrix(src_w: int, src_h: int, lt, angle: float, prb, params) -> np.ndarray:
+    """fpm_probe_matrix: the 2x3 matrix that takes sample (u, v) of probe ``prb`` on a hit at ptLT ``lt`` (as f32) and
+    ``angle`` (degrees) of a ``src_w`` x ``src_h`` source to source coordinates -- the hit's inverted patch matrix
+    composed with the probe's frame in the header's order.  Host only (no device)."""
+    arr = _probes([prb] if not (isinstance(prb, np.ndarray) and prb.ndim >= 1) else prb, 1)
+    pa, pp = _probe_params_ptr(params)
+    n = (C.c_double * 6)()
+    rc = L.load().fpm_probe_matrix(int(src_w), int(src_h), float(np.float32(lt[0])), float(np.float32(lt[1])),
+                                   float(angle), _ptr(arr, L.Probe), pp, n)
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_probe_matrix failed with {rc}")
+    return np.array(n[:], np.float64).reshape(2, 3)
+
+
+def probe_edges_host(profile, params) -> np.ndarray:
+    """fpm_probe_edges_host: the step, edge and select rules of include/fpm.h on a profile of ``params['length']``
+    integers (each 0 .. 255 width), as one PROBE_RAW_DTYPE record: index (0: no edge), n_edges (the true count), the
+    three steps, flags 0.  Host only (no device)."""
+    pa, pp = _probe_params_ptr(params)
+    prof = np.ascontiguousarray(profile, np.int32).reshape(-1)
+    if prof.size != int(pa[0]["length"]) or not np.array_equal(prof, np.asarray(profile).reshape(-1)):
+        raise ValueError("profile must hold params['length'] int32 values")
+    raw = np.zeros((), PROBE_RAW_DTYPE)
+    rc = L.load().fpm_probe_edges_host(_ptr(prof, C.c_int32), pp, raw.ctypes.data_as(C.POINTER(L.ProbeRaw)))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_probe_edges_host failed with {rc}")
+    return raw
+
+
+def probe_derive(probes, params, lt, angle: float, raw) -> np.ndarray:
+    """fpm_probe_derive: raw record i (PROBE_RAW_DTYPE, or rows of index, n_edges, d_prev, d, d_next, flags) of probe i
+    on a hit at ptLT ``lt`` (as f32) and ``angle`` as a PROBE_RESULT_DTYPE array: dev (the edge's signed displacement
+    from nominal along phi, template pixels), the contrast in gray levels, the edge point in template (tx, ty) and
+    source (sx, sy) coordinates.  Host only."""
+    arr = _probes(probes)
+    pa, pp = _probe_params_ptr(params)
+    if isinstance(raw, np.ndarray) and raw.dtype == PROBE_RAW_DTYPE:
+        r = np.ascontiguousarray(raw).reshape(-1)
+    else:
+        rows = np.asarray(raw, np.int64).reshape(-1, 6)
+        r = np.zeros(len(rows), PROBE_RAW_DTYPE)
+        for i, name in enumerate(PROBE_RAW_DTYPE.names):
+            r[name] = rows[:, i]
+    if len(r) != len(arr):
+        raise ValueError("one raw record per probe expected")
+    out = np.zeros(len(r), PROBE_RESULT_DTYPE)
+    rc = L.load().fpm_probe_derive(_ptr(arr, L.Probe), pp, float(np.float32(lt[0])), float(np.float32(lt[1])),
+                                   float(angle), _ptr(r, L.ProbeRaw), len(r), _ptr(out, L.ProbeResult))
+    if rc != L.FPM_OK:
+        raise ValueError(f"fpm_probe_derive failed with {rc}")
+    return out
+
+
+def _fit(entry, ctype, pts, trim, what):
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    out = ctype()
+    rc = entry(_ptr(p, C.c_double), len(p), float(trim), C.byref(out))
+    if rc != L.FPM_OK:
+        raise ValueError(f"{what} failed with {rc}")
+    return {name: getattr(out, name) for name, _ in ctype._fields_}
+
+
+def fit_line(pts, trim: float = 0.0) -> dict:
+    """fpm_fit_line: the total-least-squares line through the (n, 2) points ``pts`` -- (sx, sy) or (tx, ty) of found
+    probes -- as a dict: angle (the direction in degrees, in (-90, 90]), px, py (the point of the line nearest the
+    origin), rms and max_resid of the point distances, n_used, flags.  ``trim`` > 0 drops the points farther than
+    that from the first fit and fits the rest once more.  ValueError below 2 points or for non-finite input."""
+    return _fit(L.load().fpm_fit_line, L.LineFit, pts, trim, "fpm_fit_line")
+
+
+def fit_circle(pts, trim: float = 0.0) -> dict:
+    """fpm_fit_circle: the circle through the (n, 2) points ``pts`` -- Kasa's algebraic fit, then at most 8
+    Gauss-Newton steps on the geometric residual -- as a dict: cx, cy, r, rms and max_resid of the radial residuals,
+    n_used, flags (L.FIT_COLLINEAR: no circle, the numbers are 0; L.FIT_NOT_CONVERGED).  ``trim`` as fit_line.
+    ValueError below 3 points or for non-finite input."""
+    return _fit(L.load().fpm_fit_circle, L.CircleFit, pts, trim, "fpm_fit_circle")
+
+
+def circle_probes(cx: float, cy: float, r: float, n: int, outward: bool = True) -> np.ndarray:
+    """``n`` radial probes on the circle of centre (cx, cy) and radius ``r`` in template coordinates, evenly spaced
+    from 0 degrees on: probe k sits at the angle 360 k / n and scans outward (phi = that angle) or inward (phi + 180).
+    A PROBE_DTYPE array.  Pure numpy."""
+    if int(n) != n or n < 1 or not r > 0:
+        raise ValueError("n must be a whole number >= 1 and r > 0")
+    a = 360.0 * np.arange(int(n), dtype=np.float64) / int(n)
+    out = np.zeros(int(n), PROBE_DTYPE)
+    out["x"] = cx + r * np.cos(np.deg2rad(a))
+    out["y"] = cy + r * np.sin(np.deg2rad(a))
+    out["phi"] = a if outward else a + 180.0
+    return out
+
+
+def line_probes(p0, p1, n: int, normal_side: int = +1) -> np.ndarray:
+    """``n`` probes along the segment ``p0`` -> ``p1`` (template coordinates), at the fractions (k + 0.5) / n, each
+    scanning across it: phi = the segment's direction + 90 degrees for ``normal_side`` +1, - 90 for -1.  A PROBE_DTYPE
+    array.  Pure numpy."""
+    if int(n) != n or n < 1 or normal_side not in (-1, 1):
+        raise ValueError("n must be a whole number >= 1 and normal_side +1 or -1")
+    (x0, y0), (x1, y1) = (float(p0[0]), float(p0[1])), (float(p1[0]), float(p1[1]))
+    if x0 == x1 and y0 == y1:
+        raise ValueError("p0 and p1 must differ")
+    f = (np.arange(int(n), dtype=np.float64) + 0.5) / int(n)
+    out = np.zeros(int(n), PROBE_DTYPE)
+    out["x"] = x0 + f * (x1 - x0)
+    out["y"] = y0 + f * (y1 - y0)
+    out["phi"] = float(np.rad2deg(np.arctan2(y1 - y0, x1 - x0))) + 90.0 * normal_side
+    return out
+
+
+def contour_probes(template, step: float, min_contrast: float, mask=None) -> np.ndarray:
+    """Probes along the edges of the taught image ``template`` (2-D uint8), a PROBE_DTYPE array in row-major order of
+    the kept pixels.  The gradient is the 3 x 3 Sobel (gx, gy) / 8, in gray levels per pixel, on the interior pixels; a
+    pixel is an edge point when its gradient magnitude is at least ``min_contrast`` and a local maximum along the
+    gradient: not below the magnitude at the neighbour the gradient points to (its direction rounded to the nearest of
+    the 8), and above that of the opposite neighbour.  Edge points are thinned greedily in row-major order: one is
+    kept when it is at least ``step`` pixels from every point kept before.  phi = atan2(gy, gx) in degrees, the
+    direction from dark to bright.  ``mask`` (same shape, non-zero = use) only skips pixels while teaching.
+    Deterministic; pure numpy."""
+    t = np.asarray(template)
+    if t.ndim != 2 or t.dtype != np.uint8 or min(t.shape) < 3:
+        raise ValueError("template must be a 2-D uint8 image of at least 3 x 3")
+    if not step > 0 or not min_contrast > 0:
+        raise ValueError("step and min_contrast must be positive")
+    f = t.astype(np.int32)
+    h, w = f.shape
+    gx = np.zeros((h, w), np.int32)
+    gy = np.zeros((h, w), np.int32)
+    gx[1:-1, 1:-1] = (f[:-2, 2:] + 2 * f[1:-1, 2:] + f[2:, 2:]) - (f[:-2, :-2] + 2 * f[1:-1, :-2] + f[2:, :-2])
+    gy[1:-1, 1:-1] = (f[2:, :-2] + 2 * f[2:, 1:-1] + f[2:, 2:]) - (f[:-2, :-2] + 2 * f[:-2, 1:-1] + f[:-2, 2:])
+    mag2 = gx.astype(np.int64) ** 2 + gy.astype(np.int64) ** 2          # (8 |g|)^2, exact
+    ok = mag2 >= (8.0 * float(min_contrast)) ** 2
+    ok[0, :] = ok[-1, :] = ok[:, 0] = ok[:, -1] = False
+    if mask is not None:
+        mk = np.asarray(mask)
+        if mk.shape != t.shape:
+            raise ValueError("mask must have the template's shape")
+        ok &= mk != 0
+    ys, xs = np.nonzero(ok)
+    ang = np.arctan2(gy[ys, xs], gx[ys, xs])
+    k = np.rint(ang / (np.pi / 4)).astype(np.int64) % 8
+    dxs = np.array([1, 1, 0, -1, -1, -1, 0, 1])[k]
+    dys = np.array([0, 1, 1, 1, 0, -1, -1, -1])[k]
+    m = mag2[ys, xs]
+    peak = (m >= mag2[ys + dys, xs + dxs]) & (m > mag2[ys - dys, xs - dxs])
+    ys, xs = ys[peak], xs[peak]
+    kept_x, kept_y = [], []
+    s2 = float(step) ** 2
+    cell = max(int(np.ceil(step)), 1)
+    grid = {}
+    for y, x in zip(ys.tolist(), xs.tolist()):                          # nonzero's order is row-major
+        cy, cx = y // cell, x // cell
+        near = False
+        for gy_ in (cy - 1, cy, cy + 1):
+            for gx_ in (cx - 1, cx, cx + 1):
+                for (py, px) in grid.get((gy_, gx_), ()):
+                    if (py - y) ** 2 + (px - x) ** 2 < s2:
+                        near = True
+        if not near:
+            grid.setdefault((cy, cx), []).append((y, x))
+            kept_x.append(x)
+            kept_y.append(y)
+    out = np.zeros(len(kept_x), PROBE_DTYPE)
+    if kept_x:
+        ky, kx = np.array(kept_y), np.array(kept_x)
+        out["x"], out["y"] = kx, ky
+        out["phi"] = np.rad2deg(np.arctan2(gy[ky, kx].astype(np.float64), gx[ky, kx].astype(np.float64)))
+    return out
+
+
 # -- sub-pattern locators (fpm_locate_host / fpm_locate_derive / fpm_last_locate / fpm_locate_at) ---------------------
 # fpm_feature, fpm_locate_raw and fpm_locate_result, field for field
 FEATURE_DTYPE = np.dtype([(name, np.dtype(ct)) for name, ct in L.Feature._fields_], align=True)
@@ -1729,6 +1968,64 @@ class TemplateMatcher:
         """``(ms, launches, bytes)`` of k_caliper, collected under profile(True) and cleared by profile_reset
         (fpm_caliper_profile)."""
         return self._profile(self._lib.fpm_caliper_profile, fail="fpm_caliper_profile failed")
+
+    # -- edge probes: an outline measured on every hit, on the device (fpm_last_probes / fpm_probes_at) --------------
+    @staticmethod
+    def _probe_buffers(n, probes, params, profiles):
+        K = len(probes)
+        if n * K > L.PROBE_MAX_SLOTS:
+            raise ValueError(f"{n} hits x {K} probes above {L.PROBE_MAX_SLOTS} records")
+        summary = np.zeros(n, PROBE_SUMMARY_DTYPE)
+        results = np.zeros((n, K), PROBE_RESULT_DTYPE)
+        stride = int(params[0]["length"])
+        prof = np.zeros((n, K, stride), np.int32) if profiles else None
+        return summary, results, prof, stride
+
+    def last_probes(self, probes, params, source: int = -1, profiles: bool = False):
+        """The probes ``probes`` (records of probe(), or circle_probes / line_probes / contour_probes) with the shared
+        ``params`` (probe_params()) measured on every result of the last search, where the pixels are: one launch of
+        k_probe for all hits and probes, a job table of one entry per hit and one per probe (fpm_last_probes).
+        Returns ``(summary, results)``: a PROBE_SUMMARY_DTYPE array (n_hits,) -- n_found, n_missing, n_ambiguous (more
+        than one edge qualified), n_outside, worst (the probe with the largest |dev|, -1: none), sum_dev, sum_dev_sq,
+        max_abs_dev and the hit's pose -- and a PROBE_RESULT_DTYPE array (n_hits, K): index (0: no edge; the doubles
+        are then 0), n_edges, the step d, flags (L.PROBE_OUTSIDE: the probe leaves the source, border zeros may be in
+        its profile), dev (the edge's signed displacement from the nominal point along phi, in template pixels), the
+        contrast in gray levels and the edge point in template (tx, ty) and source (sx, sy) coordinates -- what
+        fit_line and fit_circle take.  Hits come in result order of ``source`` (-1: all sources, in source order),
+        sampled at the raw poses, or the aligned ones after align_last(adopt=True).  ``profiles=True`` adds the int32
+        profiles, (n_hits, K, length).  Under setBitwiseNot(True) the polarities are those of the inverted plane."""
+        arr = _probes(probes)
+        pa, pp = _probe_params_ptr(params)
+        pk = _ptr(arr, L.Probe)
+
+        def call(o, hits, n):
+            return self._lib.fpm_last_probes(self._ctx, int(source), pk, len(arr), pp, *o, hits, n)
+
+        def alloc(n):
+            summary, results, prof, stride = self._probe_buffers(n, arr, pa, profiles)
+            return (summary, results, prof), (_ptr(summary, L.ProbeSummary), _ptr(results, L.ProbeResult),
+                                              _ptr(prof, C.c_int32), stride)
+
+        summary, results, prof = self._last("last_probes", call, (None, None, None, 0), alloc)
+        return (summary, results, prof) if profiles else (summary, results)
+
+    def probes_at(self, src_index, lts, angles, probes, params, profiles: bool = False):
+        """last_probes at poses the caller supplies, on the staged sources (fpm_probes_at); poses as patches_at.
+        Needs staged sources, not a template or a search; nothing in the matcher changes."""
+        poses = _pose_args(src_index, lts, angles)
+        arr = _probes(probes)
+        pa, pp = _probe_params_ptr(params)
+        summary, results, prof, stride = self._probe_buffers(poses[3], arr, pa, profiles)
+        rc = self._lib.fpm_probes_at(self._ctx, *poses, _ptr(arr, L.Probe), len(arr), pp, _ptr(summary, L.ProbeSummary),
+                                     _ptr(results, L.ProbeResult), _ptr(prof, C.c_int32), stride)
+        if rc != L.FPM_OK:
+            self._patch_fail(rc, "probes_at")
+        return (summary, results, prof) if profiles else (summary, results)
+
+    def probe_profile(self):
+        """``(ms, launches, bytes)`` of k_probe, collected under profile(True) and cleared by profile_reset
+        (fpm_probe_profile)."""
+        return self._profile(self._lib.fpm_probe_profile, fail="fpm_probe_profile failed")
 
     # -- gray-value tools: histograms, Otsu and threshold blobs of every hit (fpm_*histogram* / fpm_*segment*) --------
     def _gray_rects(self, rects):

@@ -1014,6 +1014,174 @@ int fpm_last_locate(fpm_ctx* ctx, int32_t source, const fpm_feature* feats, int3
  * (no FPM_K_* index).  bytes = window pixels sampled + template pixels read + records and maps written. */
 int fpm_locate_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
 
+/* --- edge probes: thousands of short calipers per hit, with line and circle fits (no reference
+ * equivalent) ---------------------------------------------------------------------------------------------------------
+ * A caliper measures one edge; an outline needs a probe every pixel or two along it: a hole's diameter is a ring of
+ * radial probes and a circle fit, the straightness of a side a row of probes and a line fit, a burr or a chipped rim
+ * "the edge moved by d px here".  A probe is a short caliper that reports ONE edge.  All probes of a call share their
+ * size and rules (fpm_probe_params); a probe itself is a point and a direction.  The job table of a call is one entry
+ * per hit plus one entry per probe, 64 hits + 32 n_probes bytes, and the two are composed on the device.
+ * Probe: fpm_probe, 24 bytes, no padding.  (x, y) = the nominal edge point in template coordinates and the centre of the
+ * probe's sample grid; phi = the scan direction in degrees in the template's frame (0 = along +x); for a taught contour
+ * the direction of the gradient.  The point and the grid may lie outside the template and outside the source; pixels
+ * outside the source are 0, as in a patch.
+ * Parameters: fpm_probe_params, 32 bytes, one per call.  length L = 4 .. 64 samples along the scan; width W = 1 .. 16
+ * across it; half s = 1 .. 8 with 2 s <= L; contrast c = 1 .. 255 gray levels; polarity +1 (dark to bright along the
+ * scan), -1 or 0 (both); select = FPM_PROBE_NEAREST, _STRONGEST, _FIRST or _LAST; two reserved ints = 0.
+ * Limits.  n_probes = 1 .. 4096 (FPM_PROBE_MAX); hits x n_probes <= 2^22.  With s W 255 <= 32 640 every D fits 16 bits.
+ * Any violation, a non-finite field, or a sample beyond the samplers' 2^20 range: FPM_E_INVALID_ARG, nothing launched,
+ * nothing written.  The 2^20 check is made per hit on the four corners of the template-space bounding box of all
+ * probes' sample grids, through that hit's inverted matrix.
+ * Sampling matrix.  Per probe, once per call, in f64 with glibc cos / sin of phi * (pi / 180):
+ *     (cp, sp) = cos, sin;  hl = (L - 1) / 2;  hw = (W - 1) / 2
+ *     ox = x - (hl cp - hw sp);  oy = y - (hl sp + hw cp)               (the template point of sample (0, 0))
+ * Per hit, once: Minv = the inverted patch matrix of the template frame, fpm_patch_matrix for the rectangle origin
+ * (0, 0), inverted as cv::warpAffine inverts it -- what every per-hit tool samples the template's rectangle with.  The
+ * matrix N that takes sample (u, v) of probe k on that hit to source coordinates is the composition below, every
+ * product and every sum rounded once, in exactly this order (fpm_probe_matrix):
+ *     N0 = Minv0 cp + Minv1 sp            N3 = Minv3 cp + Minv4 sp
+ *     N1 = Minv1 cp - Minv0 sp            N4 = Minv4 cp - Minv3 sp
+ *     N2 = (Minv0 ox + Minv1 oy) + Minv2  N5 = (Minv3 ox + Minv4 oy) + Minv5
+ * The device evaluates the same expressions in f64 without contraction, so host, device and a restatement agree bit
+ * for bit.
+ * Pixels.  From N the pixels are the patch family's, kAbBits = 10, kInterBits = 5, kAbScale = 1024, kRoundDelta = 16:
+ *     ad[u] = rint(N0 u kAbScale), bd[u] = rint(N3 u kAbScale)
+ *     X0[v] = rint((N1 v + N2) kAbScale) + kRoundDelta, Y0[v] = rint((N4 v + N5) kAbScale) + kRoundDelta
+ *     X = (X0[v] + ad[u]) >> (kAbBits - kInterBits), Y = (Y0[v] + bd[u]) >> (kAbBits - kInterBits)
+ *     I(u, v) = the bilinear tap set of level 0 at (X, Y), border 0 (cv::remap's fixed-point rule, as in a patch)
+ * on the inverted plane under bitwise_not, whose polarities the probes therefore see.  A probe's pixels are NOT
+ * bit-equal to those of a caliper drawn at the same place: the pose convention differs on purpose (no f32 rounding of
+ * a per-probe lt, no cos(angle + phi)).  A probe with phi = 0 and ox = oy = 0 has N == Minv, so its pixels are
+ * fpm_patches_at's for the rectangle (0, 0, L, W).
+ * Profile, step, edges: the caliper's definitions, unchanged.  P[u] = sum over v of I(u, v); D[i] = (P[i] + .. + P[i + s
+ * - 1]) - (P[i - 1] + .. + P[i - s]) for i = s .. L - s and 0 elsewhere; with A = p D, index i is an edge of polarity p
+ * iff A[i] >= c s W and A[i] > A[i - 1] and A[i] >= A[i + 1]; polarity 0 is the union.
+ * Selection.  One edge per probe, by integers only.  NEAREST minimises |2 i - L| (boundary i lies at i - 0.5, the
+ * grid's centre at (L - 1) / 2); STRONGEST maximises |D[i]|; ties in both go to the lower index.  FIRST and LAST go by
+ * index.
+ * Raw record: fpm_probe_raw, 24 bytes: index, n_edges, d_prev = D[i - 1], d = D[i], d_next = D[i + 1], flags.  index = 0
+ * when no edge qualifies (valid indices are >= 1); the D fields are then 0.  n_edges is the true count.
+ * FPM_PROBE_OUTSIDE is set by the device, iff one of the four corner samples (0, 0), (L - 1, 0), (0, W - 1), (L - 1,
+ * W - 1) has its tap origin (X >> kInterBits, Y >> kInterBits) outside [0, sw - 2] x [0, sh - 2]: the sampler's border
+ * path, an exact integer rule (border zeros may be in the profile; a warning, not an error).
+ * Derivation (fpm_probe_derive): host only, f64, integers combined first, no fused multiply-add.  With g = sign(d):
+ *     a- = g d_prev, a0 = g d, a+ = g d_next;  den = (a- - a0) + (a+ - a0)
+ *     delta = 0.5 * (double)(a- - a+) / (double)den;  t = ((double)index - 0.5) + delta
+ *     contrast = (double)a0 / (double)(s W);  dev = t - hl     (signed displacement from nominal along phi, template px)
+ *     (tx, ty) = (ox + (t cp - hw sp), oy + (t sp + hw cp))
+ *     (sx, sy) = ((double)lt_x + (tx c - ty s), (double)lt_y + (tx s + ty c)),  (c, s) = cos, sin of the hit's angle
+ * the last line being the header's one convention for where a pose puts a template point.  A record that is no edge
+ * (d = 0, an index outside s .. L - s, n_edges outside 1 .. L, or not a- < a0 and a+ <= a0) is rejected; a record with
+ * index = 0 must have n_edges = 0 and zero D fields and gives a result whose doubles are 0.
+ * Result: fpm_probe_result, 64 bytes, no padding: index, n_edges, d, flags, then dev, contrast, tx, ty, sx, sy.
+ * Summary: fpm_probe_summary, 64 bytes, one per hit, from the hit's results in ascending probe index: n_found (index >=
+ * 1), n_missing, n_ambiguous (n_edges > 1), n_outside, worst (the probe with the largest |dev|, the earliest on ties,
+ * -1 if none is found), sum_dev, sum_dev_sq (each dev * dev rounded, then added), max_abs_dev, and the hit's pose.
+ * Launch.  k_probe, one per call: one 64-lane wave per (hit, probe), four probes of a hit per workgroup, never part of a
+ * search or of a captured graph.  Integer arithmetic from the pixels on: the results do not depend on any schedule.
+ * The calls change no search state.  Additive entries: FPM_ABI_VERSION is unchanged. */
+typedef struct fpm_probe {
+    double x, y;                 /* nominal edge point = centre of the sample grid, template coordinates */
+    double phi;                  /* scan direction, degrees, template frame                          */
+} fpm_probe;
+typedef struct fpm_probe_params {
+    int32_t length, width;       /* L samples along the scan, W across it                            */
+    int32_t half;                /* s: samples summed on each side of a boundary                     */
+    int32_t contrast;            /* c: least step in gray levels                                     */
+    int32_t polarity;            /* +1, -1 or 0 (both)                                               */
+    int32_t select;              /* FPM_PROBE_NEAREST .. FPM_PROBE_LAST                              */
+    int32_t reserved[2];         /* 0 */
+} fpm_probe_params;
+typedef struct fpm_probe_raw {
+    int32_t index, n_edges, d_prev, d, d_next, flags;
+} fpm_probe_raw;
+typedef struct fpm_probe_result {
+    int32_t index, n_edges, d, flags;
+    double dev;                  /* signed displacement from nominal along phi, template pixels      */
+    double contrast;             /* |d| / (s W): the step in gray levels                             */
+    double tx, ty;               /* the edge point in template coordinates                           */
+    double sx, sy;               /* and in source coordinates                                        */
+} fpm_probe_result;
+typedef struct fpm_probe_summary {
+    int32_t n_found, n_missing, n_ambiguous, n_outside;
+    int32_t worst;               /* probe index of the largest |dev|, -1 = none found                */
+    int32_t reserved;            /* 0 */
+    double sum_dev, sum_dev_sq, max_abs_dev;
+    float lt_x, lt_y;            /* the hit's pose                                                   */
+    double angle;
+} fpm_probe_summary;
+#define FPM_PROBE_NEAREST 0
+#define FPM_PROBE_STRONGEST 1
+#define FPM_PROBE_FIRST 2
+#define FPM_PROBE_LAST 3
+#define FPM_PROBE_OUTSIDE 1
+#define FPM_PROBE_MIN_LENGTH 4
+#define FPM_PROBE_MAX_LENGTH 64
+#define FPM_PROBE_MAX_WIDTH 16
+#define FPM_PROBE_MAX_HALF 8
+#define FPM_PROBE_MAX 4096               /* n_probes */
+#define FPM_PROBE_MAX_SLOTS (1 << 22)    /* hits * n_probes */
+
+/* host only, no context: the composed matrix N of one probe on a hit at (lt, angle) of a src_w x src_h source */
+int fpm_probe_matrix(int32_t src_w, int32_t src_h, float lt_x, float lt_y, double angle, const fpm_probe* probe,
+                     const fpm_probe_params* params, double n[6]);
+/* host only, no context: the step, edge and select rules on a caller's profile of params->length entries, each 0 ..
+ * 255 W (the reference form); out->flags = 0 */
+int fpm_probe_edges_host(const int32_t* profile, const fpm_probe_params* params, fpm_probe_raw* out);
+/* host only, no context: raw record i of probe i (n of each) on a hit at (lt, angle) into out[i], by the rule above;
+ * FPM_E_INVALID_ARG for a record that is no edge, nothing written then */
+int fpm_probe_derive(const fpm_probe* probes, const fpm_probe_params* params, float lt_x, float lt_y, double angle,
+                     const fpm_probe_raw* raw, int32_t n, fpm_probe_result* out);
+/* The probes at caller-supplied poses on the staged sources.  Poses and state rules as fpm_calipers_at: staged sources
+ * are needed, a template and a search are not.  summary: [pose]; results: [pose][probe]; profiles (may be NULL): int32
+ * [pose][probe][profile_stride] with profile_stride >= length, the entries from length on 0. */
+int fpm_probes_at(fpm_ctx* ctx, const int32_t* src_index, const float* lt, const double* angles, int32_t n_poses,
+                  const fpm_probe* probes, int32_t n_probes, const fpm_probe_params* params, fpm_probe_summary* summary,
+                  fpm_probe_result* results, int32_t* profiles, int32_t profile_stride);
+/* The probes over the hits of the last search in result order (source = -1: of all sources), at the context's last
+ * poses: the raw ones, or the aligned ones after FPM_ALIGN_ADOPT, exactly as fpm_last_compare.  source, cap (hits), *n,
+ * the count-only call (cap = 0 with null outputs) and every state rule are fpm_last_compare's. */
+int fpm_last_probes(fpm_ctx* ctx, int32_t source, const fpm_probe* probes, int32_t n_probes, const fpm_probe_params* params,
+                    fpm_probe_summary* summary, fpm_probe_result* results, int32_t* profiles, int32_t profile_stride,
+                    int32_t cap /* hits */, int32_t* n);
+/* Timing of k_probe, collected under fpm_profile_enable and cleared by fpm_profile_reset as fpm_caliper_profile's (no
+ * FPM_K_* index: FPM_K_COUNT is unchanged).  bytes = L W source pixels per (hit, probe) + the job table read + the
+ * records and profiles written. */
+int fpm_probe_profile(const fpm_ctx* ctx, double* ms, int64_t* launches, int64_t* bytes);
+
+/* Fits (host only, f64, no fused multiply-add): what turns a ring or a row of found probes into a diameter or a
+ * straightness.  pts = [n][2] doubles, (sx, sy) or (tx, ty) of the found records.  trim > 0: after the first fit the
+ * points with |residual| > trim are dropped and the fit is repeated once on the rest, in their order (when fewer than
+ * the least number remain the first fit stands and FPM_FIT_TRIM_STARVED is set); trim = 0: no rejection.
+ * FPM_E_INVALID_ARG below 2 points for the line and 3 for the circle, for a non-finite coordinate, or for a trim that is
+ * negative or not finite; nothing is written then.
+ * fpm_fit_line: total least squares.  mx = (x_0 + x_1 + ..) / m, my alike, sums in index order; with dx = x_i - mx, dy
+ * = y_i - my: sxx = sum dx dx, sxy = sum dx dy, syy = sum dy dy, in index order.  theta = 0.5 atan2(2 sxy, sxx - syy),
+ * the direction, angle = theta in degrees, in (-90, 90]; the signed residual of a point is dy cos theta - dx sin theta;
+ * (px, py) = the point of the line nearest the origin, m - (mx cos theta + my sin theta) (cos theta, sin theta).
+ * fpm_fit_circle: Kasa's algebraic fit on centred coordinates (u, v) = (x - mx, y - my): [suu suv; suv svv] (uc, vc) =
+ * 0.5 (suuu + suvv, svvv + svuu), r^2 = uc^2 + vc^2 + (suu + svv) / m; then at most 8 Gauss-Newton steps on the
+ * geometric residual d_i - r, stopped when every component of a step is at most 1e-10 in magnitude.
+ * FPM_FIT_COLLINEAR when the 2 x 2 determinant is at most 1e-12 (suu + svv)^2 (centre, radius, rms and max_resid are
+ * then 0); FPM_FIT_NOT_CONVERGED when the eighth step was still larger, or a step's 3 x 3 system was singular.
+ * rms = sqrt(sum r_i^2 / n_used), max_resid = the largest |r_i|, both over the points used. */
+typedef struct fpm_line_fit {
+    double angle;                /* direction, degrees, in (-90, 90]                                 */
+    double px, py;               /* the point of the line nearest the origin                         */
+    double rms, max_resid;
+    int32_t n_used, flags;
+} fpm_line_fit;
+typedef struct fpm_circle_fit {
+    double cx, cy, r;
+    double rms, max_resid;
+    int32_t n_used, flags;
+} fpm_circle_fit;
+#define FPM_FIT_NOT_CONVERGED 1
+#define FPM_FIT_COLLINEAR 2
+#define FPM_FIT_TRIM_STARVED 4
+int fpm_fit_line(const double* pts, int32_t n, double trim, fpm_line_fit* out);
+int fpm_fit_circle(const double* pts, int32_t n, double trim, fpm_circle_fit* out);
+
 /* --- angle sharding of one search (no reference equivalent: the reference loops over the
  * whole angle list on one thread, TemplateMatcher.cpp:157-211) ----------------------------------------------
  * A search splits at the reference's own seam: the top-layer sweep and every candidate's pyramid descent
